@@ -13,10 +13,18 @@ exchange + halo-tree build + solve + termination all-reduce (SURVEY.md section 8
 
 Prints ONE JSON line on rank 0.  Beside the contract's keys: `roofline` (dominant kernel, HBM bound,
 algorithmic bytes per SURVEY 8d, HIP-event kernel time; traffic and instruction counts from the committed
-rocprofv3 PMC passes if they were taken on THESE sources), `cpu_baseline` (the CPU checker's restatement on
-the host cores: rank 0, N = 1 only, bounded sample), `api_layout_writeback` (the solve with the reference's
-24-byte frameBuffer records), and for N > 1 `ranks`, `phase_ms`, `halo_points`, `halo_exchanges`.
-Exit status 1 (and "value": null) if the run's own parity spot check fails.
+rocprofv3 PMC passes if they were taken on THESE sources), and for N > 1 `ranks`, `phase_ms`, `halo_points`,
+`halo_exchanges`.
+
+A plain run sets up, warms up, times the steps and prints the line.  With --full it also measures and checks
+what the headline does not need: `cpu_baseline` (the CPU checker's restatement on the host cores: rank 0,
+N = 1 only, bounded sample) and the parity spot check of the benchmarked run against it, `api_layout_writeback`
+(the solve with the reference's 24-byte frameBuffer records), `dbscan_config3` (BASELINE config 3 on
+the same engine), `roofline.measured_copy_GBps`, `build_ms` (a second, steady-state build), and for a default
+N > 1 run the `weak` / `config4` sub-objects.  Exit status 1 (and "value": null) if one of those checks fails.
+
+--dump-outputs DIR writes the last timed step's results (a seeded sample of rows of at most DUMP_BYTES) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -35,6 +43,8 @@ N_POINTS = 10_000_000  # BASELINE.json configs[1] / configs[2]
 K = 10
 DB_EPS, DB_MINPTS = 0.01, 4
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 48 << 20  # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240611  # --dump-outputs: the rows sampled when all of them do not fit
 
 
 def algorithmic_bytes(n, k, total_intersections, total_active_rounds):
@@ -141,6 +151,23 @@ def copy_bandwidth(dev):
         best = t if best is None else min(best, t)
     del src, dst
     return 2 * (1 << 28) * 4 / (best * 1e-3) / 1e9
+
+
+def dump_outputs(directory, out, n, dev):
+    """--dump-outputs: the tensors of the last timed step (TrueKNN: idx, dist, intersections; RT-DBSCAN: labels, core),
+    one row per point, as DIR/<name>.npy -- float32 stays float32, every other type becomes float64 (exact for the
+    int32 / int64 / bool values these hold).  All rows if they fit in DUMP_BYTES, else a sorted sample of rows drawn
+    with DUMP_SEED; DIR/rows.npy names the rows either way."""
+    arrays = {name: t for name, t in out.items() if torch.is_tensor(t) and t.shape[0] == n}
+    row_bytes = 8 + sum((4 if t.dtype == torch.float32 else 8) * (t.numel() // n) for t in arrays.values())
+    m = min(n, DUMP_BYTES // row_bytes)
+    rows = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    sel = torch.from_numpy(rows).to(dev)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+    for name, t in arrays.items():
+        v = t.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), v if v.dtype == np.float32 else v.astype(np.float64))
 
 
 def sharded_trueknn_run(solver, dist, dev, backend, world, n_total, k, steps, warmup):
@@ -274,13 +301,20 @@ def main():
     ap.add_argument("--eps", type=float, default=DB_EPS)
     ap.add_argument("--min-pts", type=int, default=DB_MINPTS)
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 lane, 2 wave, 3 team")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks (CPU baseline and parity spot check, frameBuffer leg, RT-DBSCAN "
+                         "config-3 object, copy bandwidth, steady-state build time, the multi-rank sub-objects)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64; a seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity checks")
     ap.add_argument("--no-fb-leg", action="store_true",
-                    help="skip the api_layout_writeback solves (scripts/profile_gpu.sh: their launches write a 2.4 GB frameBuffer "
-                         "and must not be averaged into the PMC record of the benchmarked launch)")
-    ap.add_argument("--no-dbscan-leg", action="store_true", help="skip the RT-DBSCAN config-3 object of the default run")
+                    help="with --full: skip the api_layout_writeback solves (scripts/profile_gpu.sh: their launches write a 2.4 GB "
+                         "frameBuffer and must not be averaged into the PMC record of the benchmarked launch)")
+    ap.add_argument("--no-dbscan-leg", action="store_true", help="with --full: skip the RT-DBSCAN config-3 object")
     ap.add_argument("--sharded", action="store_true", help="use the Morton-tile / halo-exchange driver even for one rank")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     from owlraytracing_amd import _lib, datasets
     from owlraytracing_amd.trueknn import TrueKNN
@@ -306,6 +340,8 @@ def main():
     # ("kNN queries/sec (10M pts, k=10) at 1/2/4/8 MI355X": strong scaling), with N x 10 M (weak) and, at N = 8, configs[3]
     # (100 M points, strong) as sub-objects of the same line (the default used to time N x 10 M under the 10 M metric)
     default_multi = sharded and not dbscan and args.scaling is None and args.n is None
+    if sharded and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the one-GPU path's results (no --sharded, --gpus 1)")
     scaling = args.scaling or ("strong" if default_multi else "weak")
     n_arg = args.n if args.n is not None else N_POINTS
     n_total = n_arg if (scaling == "strong" or not sharded) else n_arg * world
@@ -335,7 +371,7 @@ def main():
         elapsed = run["ms_per_step"] * args.steps / 1e3
         for key in ("ranks", "phase_ms", "halo_points", "halo_exchanges"):
             extra[key] = run[key]
-        if default_multi and world > 1:
+        if default_multi and world > 1 and args.full:
             few = max(1, min(args.steps, 5))
             weak = sharded_trueknn_run(solver, dist, dev, backend, world, N_POINTS * world, k, few, 1)
             extra["weak"] = sub_object(weak, world, k, "weak")
@@ -361,7 +397,8 @@ def main():
         pts = torch.from_numpy(xyz_host).to(dev)
         eng = TrueKNN(device=local_rank)
         build_info = eng.build(pts)
-        build_info = eng.build(pts)  # second build: steady-state build time (first one pays allocations)
+        if args.full:
+            build_info = eng.build(pts)  # second build: steady-state build time (first one pays allocations)
         out = {}
         n_local = n_total
 
@@ -396,6 +433,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
             extra.update(sharded_dbscan_records(solver, dist, dev, backend, world, eps32, args.min_pts, infos, n_local, elapsed_own / args.steps * 1e3))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, n_total, dev)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = n_total * args.steps / elapsed
@@ -412,11 +451,12 @@ def main():
     line.update(extra)
     checks = {}  # named result checks of this run; ANY red one fails the run (run_failed)
     if not sharded:
-        line["build_ms"] = float(build_info["build_ms"])
+        if args.full:
+            line["build_ms"] = float(build_info["build_ms"])
         line["tree_bytes"] = int(build_info["device_bytes"])
-    if rank == 0:
+    if rank == 0 and args.full:
         line["roofline"]["measured_copy_GBps"] = copy_bandwidth(dev)
-    if rank == 0 and not sharded and not dbscan and not args.no_fb_leg:
+    if rank == 0 and not sharded and not dbscan and args.full and not args.no_fb_leg:
         # the reference's result layout (24-byte Neigh records, GeomTypes.h:22-28) is an artefact of
         # its API; its write-back cost is reported apart from the compact rows the step writes
         fb_ms = []
@@ -432,12 +472,12 @@ def main():
             "frameBuffer_bytes": 24 * k * n_total,
             "note": "one solve writing idx/dist/intersections AND the n*k 24-byte records the reference's host loop reads",
         }
-    if rank == 0 and not sharded and not dbscan and not args.no_dbscan_leg and n_total == N_POINTS:
-        # BASELINE config 3 in the same run (the driver only runs the default command): timed like the steps
+    if rank == 0 and not sharded and not dbscan and args.full and not args.no_dbscan_leg and n_total == N_POINTS:
+        # BASELINE config 3 in the same --full run (one command covers both configs): timed like the steps
         # above, per-kernel rooflines, a sampled eps-ball parity check by the CPU spec
         db_failed, line["dbscan_config3"] = dbscan_config3_leg(args, eng, dev)
         checks["dbscan_config3"] = not db_failed
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline:
         if dbscan:
             cb, ref, m = cpu_baseline_dbscan(xyz_host, eps32, args.min_pts)
             line["cpu_baseline"] = cb
@@ -724,7 +764,7 @@ def dbscan_config3_leg(args, eng, dev, steps=5, warmup=1):
         obj["parity_spot_check"] = (
             "core flags and labels of %d sampled points equal what the CPU spec derives from their recomputed eps-balls "
             "(oracle/dbscan_oracle.c:dbref_ball_check, %.1fs); all %d points against the threaded CPU spec: "
-            "tests/test_dbscan.py::test_config3_full_size and `bench.py --workload dbscan`" % (len(sample), time.perf_counter() - t0, n)
+            "tests/test_dbscan.py::test_config3_full_size and `bench.py --workload dbscan --full`" % (len(sample), time.perf_counter() - t0, n)
             if ok else "MISMATCH (%d of %d sampled points, first %d)" % (chk["violations"], len(sample), chk["first_bad"]))
         failed = not ok
         if failed:

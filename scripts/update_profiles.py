@@ -10,9 +10,9 @@ two passes per tknnDbscan call do different work), the first call is dropped (co
 is left must be ONE population -- position by position, the values may differ by a few per cent at most.  If they do
 not (round 2: three of nine team_kernel launches of the profiled command also wrote the 2.4 GB frameBuffer, and the
 "per launch" record was the mean of both kinds) the record is REFUSED: profile a command whose launches of that kernel
-all do the benchmarked work (bench.py --no-fb-leg).
+all do the benchmarked work (bench.py --full --no-fb-leg).
 
-Without --kernel: the bench line's roofline kernel, and the three traversal kernels of its dbscan_config3 object.
+Without --kernel: the bench line's roofline kernel, and the three traversal kernels of its dbscan_config3 object (bench.py --full).
 The record carries the fingerprint of the native sources it was measured on (owlraytracing_amd._lib
 .source_fingerprint); bench.py ignores a record whose fingerprint is not that of the sources it runs.
 """
@@ -76,7 +76,7 @@ def steady(runs, name, period=1, tol=None):
         if hi > 0 and (lo <= 0 or hi / lo - 1.0 > tol):
             raise MixedDispatches(
                 "%s differs by %.0f %% between launches of the profiled command (position %d of %d: %s): they do not all do the "
-                "benchmarked work -- profile `bench.py --no-fb-leg`, or a command without other uses of the kernel" % (
+                "benchmarked work -- profile `bench.py --full --no-fb-leg`, or a command without other uses of the kernel" % (
                     name, 100.0 * (hi / lo - 1.0) if lo > 0 else float("inf"), pos, period, ", ".join("%.6g" % v for v in col[:12])))
         medians.append(statistics.median(col))
     return sum(medians) / period, medians, len(calls) * period

@@ -131,3 +131,32 @@ def test_multi_rank_line_names_the_set_it_timed(monkeypatch):
     assert sub["metric"] == "kNN queries/sec (80M pts, k=10)" and sub["scaling"] == "weak" and sub["n_gpus"] == 8
     assert len(sub["ranks"]) == 8 and set(sub["phase_ms"]) == {"select", "exchange", "halo_build", "solve", "reduce"}
     json.dumps(sub)  # the sub-object goes into the JSON line as it is
+
+
+def test_dump_outputs_writes_float_rows_of_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every row while they fit, else the same seeded sample of rows in every run; float32 stays
+    float32, integer and bool results become float64 with their values intact, rows.npy names the rows."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    n, k = 1000, 4
+    g = torch.Generator().manual_seed(0)
+    out = {"idx": torch.randint(0, n, (n, k), dtype=torch.int32, generator=g), "dist": torch.rand((n, k), generator=g),
+           "intersections": torch.randint(0, 1 << 40, (n,), dtype=torch.int64, generator=g)}
+    bench.dump_outputs(str(tmp_path / "all"), out, n, "cpu")
+    rows = np.load(tmp_path / "all" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.arange(n))
+    for name, t in out.items():
+        v = np.load(tmp_path / "all" / (name + ".npy"))
+        assert v.dtype == (np.float32 if t.dtype == torch.float32 else np.float64)
+        assert np.array_equal(v, t.numpy())
+    row_bytes = 8 + 8 * k + 4 * k + 8
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * row_bytes)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, n, "cpu")
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert len(rows) == 100 and np.all(np.diff(rows) > 0) and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 100 * row_bytes + 4 * 128
+    for name, t in out.items():
+        assert np.array_equal(np.load(tmp_path / "a" / (name + ".npy")), t.numpy()[rows.astype(np.int64)])

@@ -360,13 +360,12 @@ def test_command_line_tool_with_a_sampled_start_radius(tmp_path):
 
 
 def test_reference_sample_configures_and_builds_through_the_cmake_module(tmp_path):
-    """cmake/owl_mi355x.cmake stands in for the reference's owl/cmake/configure_owl.cmake + configure_optix.cmake: the
-    UNCHANGED samples/s01-trueknn/CMakeLists.txt (cuda_compile_and_embed at :19-21, OWL_LIBRARIES at :27-30) configures
-    and builds against it -- hipcc cross-compiles deviceCode.cu for gfx950, no GPU needed.  Needs the reference tree
-    (present in the build container only)."""
-    ref_sample = "/root/reference/samples/s01-trueknn"
-    if not os.path.exists(os.path.join(ref_sample, "CMakeLists.txt")):
-        pytest.skip("no reference tree here")
+    """cmake/owl_mi355x.cmake stands in for the reference's owl/cmake/configure_owl.cmake + configure_optix.cmake: a
+    sample CMakeLists.txt in the reference's form (cuda_compile_and_embed(ptxCode deviceCode.cu), an executable of
+    hostCode.cpp + ${ptxCode} linked to ${OWL_LIBRARIES}, as samples/s01-trueknn/CMakeLists.txt:19-30 there) configures
+    and builds against it -- hipcc cross-compiles deviceCode.cu for gfx950, no GPU needed.  The sample is this
+    repository's samples/s02-rtdbscan, written in that form, so the test needs nothing outside the repository."""
+    sample = os.path.join(ROOT, "samples", "s02-rtdbscan")
     import shutil
     if not shutil.which("cmake") or not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("cmake or hipcc missing")
@@ -375,14 +374,14 @@ def test_reference_sample_configures_and_builds_through_the_cmake_module(tmp_pat
         pytest.skip("library not built")
     (tmp_path / "CMakeLists.txt").write_text(
         "cmake_minimum_required(VERSION 3.16)\nproject(owl_on_mi355x C CXX)\nenable_testing()\n"
-        "include(%s)\nadd_subdirectory(%s ${CMAKE_BINARY_DIR}/s01-trueknn)\n" % (os.path.join(ROOT, "cmake", "owl_mi355x.cmake"), ref_sample))
+        "include(%s)\nadd_subdirectory(%s ${CMAKE_BINARY_DIR}/s02-rtdbscan)\n" % (os.path.join(ROOT, "cmake", "owl_mi355x.cmake"), sample))
     build = tmp_path / "build"
     r = subprocess.run(["cmake", "-S", str(tmp_path), "-B", str(build), "-DCMAKE_BUILD_TYPE=Release"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     r = subprocess.run(["cmake", "--build", str(build), "-j", "4"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    exe = build / "s01-trueknn" / "sample01-trueknn"
+    exe = build / "s02-rtdbscan" / "sample02-rtdbscan"
     assert exe.exists()
-    # the embedded device code is a gfx950 code object under the symbol the sample declares (hostCode.cpp:52)
+    # the embedded device code is a gfx950 code object under the symbol the sample declares (hostCode.cpp:21)
     syms = subprocess.run(["nm", "-C", str(exe)], capture_output=True, text=True).stdout
     assert " ptxCode" in syms
