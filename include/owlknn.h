@@ -127,7 +127,8 @@ TKNN_API int tknnSolve(tknnEngine e, int k, float start_radius, int kernel, int 
 
 /* ---- sharded use: one engine per GPU owns a tile of a larger point set ----
  * tknnBuildIds: like tknnBuild, but point i is reported as d_ids[i] (a global index) in neighbour
- *   lists and excluded as "self" by that id; rows are still addressed by the local position i.
+ *   lists and excluded as "self" by that id; rows are still addressed by the local position i.  Ids are distinct
+ *   and non-negative (any int32 from 0 up); exact-distance ties order by id as they do by index without ids.
  * tknnSetHalo: a second, read-only point set (border points received from neighbouring tiles, with
  *   their global ids) that every query also searches; m = 0 removes it.
  * tknnSolveEx: tknnSolve with options: d_levels (n, may be NULL) receives the 0-based radius level at

@@ -341,6 +341,7 @@ void Engine::build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuil
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   halo_n_ = 0;
   boundary_valid_ = false;
+  ids_given_ = d_ids != nullptr;
   // Per-slot solve state first: if one of these allocations fails (a 100 M-point rebuild on a full
   // card) the engine must not be left "built" with null state arrays behind a stale capacity.
   if (n > state_cap_) {

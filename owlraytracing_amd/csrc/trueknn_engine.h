@@ -97,6 +97,8 @@ class Engine {
 
   int device_ = 0;
   Lbvh bvh_;
+  // the last build was given ids (tknnBuildIds with d_ids): neighbour lists then name points by id, not by input row
+  bool ids_given_ = false;
   Lbvh halo_;
   int64_t halo_n_ = 0;
   // A phase-1 solve (queries no halo point can reach) runs beside the halo exchange: tknnSetHalo may rebuild

@@ -230,7 +230,11 @@ struct TeamArgs {
   // 0.78 / 2.3 M rows in 2.5 / 7.2 ms; with longer turns 1.1 / 2.8 ms).  The walks keep 1: their queries differ too much in cost
   // (turns of up to 64 slots: the hand-over walk 4.0 -> 4.5 ms on that set, the k = 65 walk 173 -> 189 ms on 10 M uniform points).
   int grab;
-  const int32_t *row_slot;    // tie_fix_kernel: the sorted slot of row i (Lbvh::row_slot_device), or null: no look at the written row first
+  // tie_fix_kernel: the sorted slot of row i (Lbvh::row_slot_device), or null: no look at the written row first.  The look
+  // turns a written neighbour into its point through this table, which is indexed by input ROW: right only where a point's
+  // id is its row.  An engine built with ids (tknnBuildIds) names neighbours by the caller's id, so it gets null and every
+  // flagged row is walked (an id below n would otherwise fetch some other point and let a wrongly ordered row stand).
+  const int32_t *row_slot;
   // [0] (unused here) [kXcdCounter + 32 x] per-XCD packet counters [1] max levels [2] node tests [3] point tests [4] sum isect
   // [5] error flags (1 max_rounds) [6] sum levels [7] unfinished [8] handed over [9] min hand-over level
   unsigned long long *counters;
@@ -2483,7 +2487,8 @@ void Engine::launch_tie_fix(const SolveArgs &sa, const int32_t *slots, int32_t n
   // (10 M taxi-like points, k = 10 / 24, 0.78 / 2.3 M rows, 24 workgroups per CU: turns of 4 / 8 / 12 / 24 / 32 slots 2.55 / 1.42 / 1.08 /
   // 0.89 / 0.94 ms and 7.2 / 3.8 / 2.6 / 1.81 / 1.85 ms; 64 and more slots a turn: the waves' own chains of loads show, 2.8 ms and up)
   a.grab = grab_for(expected_rows, blocks, 6, 6);
-  a.row_slot = getenv("TKNN_TIE_LOOK") && !strcmp(getenv("TKNN_TIE_LOOK"), "0") ? nullptr : bvh_.row_slot_device();  // (A/B switch)
+  const bool look = !ids_given_ && !(getenv("TKNN_TIE_LOOK") && !strcmp(getenv("TKNN_TIE_LOOK"), "0"));  // (TKNN_TIE_LOOK=0: A/B switch)
+  a.row_slot = look ? bvh_.row_slot_device() : nullptr;
   a.counters = counters_;
   using FixEntry = void (*)(TeamArgs, const int32_t *, int32_t);
   static const FixEntry entries[2][4] = {{tie_fix_kernel<false, 1>, tie_fix_kernel<false, 2>, tie_fix_kernel<false, 3>, tie_fix_kernel<false, 4>},

@@ -6,6 +6,7 @@ import oracle
 from owlraytracing_amd import _lib, datasets
 
 from conftest import assert_rows_equal, assert_rows_match
+from tile_sets import lattice as _lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -220,18 +221,6 @@ def test_frame_buffer_only_solves_order_exact_ties_like_the_replay(kernel):
         for field in ("ind", "dist", "numNeighbors", "intersections"):
             assert np.array_equal(fb[field], want[field]), (name, field)
         eng.close()
-
-
-def _lattice(m, dims, seed, drop=0.2):
-    g = np.arange(m, dtype=np.float32) / np.float32(32)
-    if dims == 3:
-        xyz = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
-    else:
-        xy = np.stack(np.meshgrid(g, g, indexing="ij"), -1).reshape(-1, 2)
-        xyz = np.concatenate([xy, np.zeros((len(xy), 1), np.float32)], 1)
-    rng = np.random.default_rng(seed)
-    xyz = xyz[rng.random(len(xyz)) > drop]
-    return np.ascontiguousarray(xyz[rng.permutation(len(xyz))])
 
 
 _TIE_SETS = {}
