@@ -1576,13 +1576,7 @@ int64_t Engine::dbscan_noise(float eps, int min_pts, uint8_t *d_noise, hipStream
     scan_bytes = std::max(scan_bytes, flag_scan_bytes);
   }
   const size_t need = (((size_t)n * (4 + 4 + 4 + 4 + 1 + 1)) + 32 + 255) / 256 * 256;  // as dbscan_auto
-  if (need + scan_bytes > wave_ws_bytes_) {
-    if (wave_ws_) (void)hipFree(wave_ws_);
-    wave_ws_ = nullptr;
-    OWLMI_HIP(hipMalloc(&wave_ws_, need + scan_bytes));
-    wave_ws_bytes_ = need + scan_bytes;
-  }
-  char *ws = (char *)wave_ws_;
+  char *ws = (char *)workspace(need + scan_bytes);
   DbArgs a;
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
@@ -1633,13 +1627,7 @@ void Engine::dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, 
     OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, flag_scan_bytes, DbFlagIter(nullptr, DbFlagOf()), (int32_t *)nullptr, (int)n, s));
     scan_bytes = std::max(scan_bytes, flag_scan_bytes);
   }
-  if (need + scan_bytes > wave_ws_bytes_) {
-    if (wave_ws_) (void)hipFree(wave_ws_);
-    wave_ws_ = nullptr;
-    OWLMI_HIP(hipMalloc(&wave_ws_, need + scan_bytes));
-    wave_ws_bytes_ = need + scan_bytes;
-  }
-  char *ws = (char *)wave_ws_;
+  char *ws = (char *)workspace(need + scan_bytes);
   DbArgs a;
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
@@ -1944,13 +1932,7 @@ void Engine::dbscan_auto(float eps0, int min_pts, double max_noise, int max_roun
     scan_bytes = std::max(scan_bytes, flag_scan_bytes);
   }
   const size_t need = (((size_t)n * (4 + 4 + 4 + 4 + 1 + 1)) + 32 + 255) / 256 * 256;
-  if (need + scan_bytes > wave_ws_bytes_) {
-    if (wave_ws_) (void)hipFree(wave_ws_);
-    wave_ws_ = nullptr;
-    OWLMI_HIP(hipMalloc(&wave_ws_, need + scan_bytes));
-    wave_ws_bytes_ = need + scan_bytes;
-  }
-  char *ws = (char *)wave_ws_;
+  char *ws = (char *)workspace(need + scan_bytes);
   DbArgs a;
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();

@@ -270,15 +270,39 @@ void launch_repair(const RepairArgs &a, hipStream_t s) {
 
 }  // namespace
 
-int list_capacity_for(int k) {
-  static const int caps[] = {1, 2, 4, 5, 8, 10, 16, 24, 32, 64};
-  for (int c : caps)
-    if (k <= c) return c;
-  return -1;
+tknnSolveInfo solve_info(const KernelStats &st, float start_radius, int kernel, int list_capacity, float ms) {
+  tknnSolveInfo info;
+  std::memset(&info, 0, sizeof info);
+  info.rounds = (int)st.rounds;
+  info.final_radius = final_radius(start_radius, info.rounds);
+  info.node_tests = (int64_t)st.node_tests;
+  info.point_tests = (int64_t)st.point_tests;
+  info.total_intersections = (int64_t)st.intersections;
+  info.total_active_rounds = (int64_t)st.active_rounds;
+  info.solve_ms = ms;
+  info.dominant_kernel_ms = ms;
+  info.dominant_kernel_launches = 1;
+  info.kernel_used = kernel;
+  info.list_capacity = list_capacity;
+  info.unfinished = (int64_t)st.unfinished;
+  return info;
+}
+
+void merge_tail(tknnSolveInfo &into, const tknnSolveInfo &tail, float start_radius, bool count_launches) {
+  into.rounds = std::max(into.rounds, tail.rounds);
+  into.final_radius = final_radius(start_radius, into.rounds);
+  into.node_tests += tail.node_tests;
+  into.point_tests += tail.point_tests;
+  into.total_intersections += tail.total_intersections;
+  into.total_active_rounds += tail.total_active_rounds;
+  into.unfinished += tail.unfinished;
+  into.solve_ms += tail.solve_ms;
+  if (count_launches) into.dominant_kernel_launches += tail.dominant_kernel_launches;
 }
 
 Engine::Engine() {
   OWLMI_HIP(hipGetDevice(&device_));
+  OWLMI_HIP(hipDeviceGetAttribute(&cu_count_, hipDeviceAttributeMultiprocessorCount, device_));
   OWLMI_HIP(hipEventCreate(&ev_a_));
   OWLMI_HIP(hipEventCreate(&ev_b_));
   OWLMI_HIP(hipEventCreate(&ev_c_));
@@ -320,6 +344,30 @@ Engine::~Engine() {
   if (ev_side_a_) (void)hipEventDestroy(ev_side_a_);
   if (ev_side_b_) (void)hipEventDestroy(ev_side_b_);
   if (db_side_) (void)hipStreamDestroy(db_side_);
+}
+
+// Pointer and size are cleared before the allocation: if it fails (it throws), the next smaller request allocates
+// again instead of finding a null buffer behind a stale size.
+void *Engine::workspace(size_t bytes) {
+  if (bytes > wave_ws_bytes_) {
+    if (wave_ws_) (void)hipFree(wave_ws_);
+    wave_ws_ = nullptr;
+    wave_ws_bytes_ = 0;
+    OWLMI_HIP(hipMalloc(&wave_ws_, bytes));
+    wave_ws_bytes_ = bytes;
+  }
+  return wave_ws_;
+}
+
+int32_t *Engine::slot_list(int64_t n) {
+  if (n > slot_list_cap_) {
+    if (slot_list_) (void)hipFree(slot_list_);
+    slot_list_ = nullptr;
+    slot_list_cap_ = 0;
+    OWLMI_HIP(hipMalloc((void **)&slot_list_, ((size_t)n + 1) * sizeof(int32_t)));
+    slot_list_cap_ = n;
+  }
+  return slot_list_;
 }
 
 void Engine::set_halo(const float *d_xyz, const int32_t *d_ids, int64_t m, hipStream_t s) {
@@ -457,18 +505,7 @@ void Engine::lane_rounds(const SolveArgs &sa, int first_level, bool fresh, tknnS
     // (the kernel's counters are striped: [0] of every stripe = unfinished is reset per round, the others accumulate over the rounds)
     OWLMI_HIP(hipMemset2DAsync(counters_ + kStatBase, kStatStride * sizeof(unsigned long long), 0, sizeof(unsigned long long), kStatStripes, s));
     OWLMI_HIP(hipEventRecord(ev_a_, s));
-    switch (cap) {
-      case 1: launch_lane<1>(a, subtrees, s); break;
-      case 2: launch_lane<2>(a, subtrees, s); break;
-      case 4: launch_lane<4>(a, subtrees, s); break;
-      case 5: launch_lane<5>(a, subtrees, s); break;
-      case 8: launch_lane<8>(a, subtrees, s); break;
-      case 10: launch_lane<10>(a, subtrees, s); break;
-      case 16: launch_lane<16>(a, subtrees, s); break;
-      case 24: launch_lane<24>(a, subtrees, s); break;
-      case 32: launch_lane<32>(a, subtrees, s); break;
-      default: launch_lane<64>(a, subtrees, s); break;
-    }
+    ListCapacities::dispatch(cap, [&](auto c) { launch_lane<decltype(c)::value>(a, subtrees, s); });
     OWLMI_HIP(hipGetLastError());
     OWLMI_HIP(hipEventRecord(ev_b_, s));
     // hostCode.cpp:310-330: the host decides about another round from the result state
@@ -520,18 +557,7 @@ int64_t Engine::repair_exact(int k, float start_radius, const int32_t *d_levels,
   a.dist = d_dist;
   a.counters = counters_;
   OWLMI_HIP(hipMemsetAsync(counters_, 0, sizeof(unsigned long long), s));
-  switch (list_capacity_for(k)) {
-    case 1: launch_repair<1>(a, s); break;
-    case 2: launch_repair<2>(a, s); break;
-    case 4: launch_repair<4>(a, s); break;
-    case 5: launch_repair<5>(a, s); break;
-    case 8: launch_repair<8>(a, s); break;
-    case 10: launch_repair<10>(a, s); break;
-    case 16: launch_repair<16>(a, s); break;
-    case 24: launch_repair<24>(a, s); break;
-    case 32: launch_repair<32>(a, s); break;
-    default: launch_repair<64>(a, s); break;
-  }
+  ListCapacities::dispatch(list_capacity_for(k), [&](auto c) { launch_repair<decltype(c)::value>(a, s); });
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));
@@ -545,51 +571,32 @@ __global__ void __launch_bounds__(256) unfinished_mask_kernel(const int32_t *lev
 }
 
 void Engine::solve(const SolveArgs &sa, int kernel, tknnSolveInfo *info, hipStream_t s) {
-  if (bigk_supports(sa.k)) {
-    // 64 < k <= TKNN_MAX_K: the team walk with the lists in memory, rows final (three-word keys: no tie pass)
+  // 64 < k <= TKNN_MAX_K: the team walk with the lists in memory, rows final (three-word keys: no tie pass)
+  const bool bigk = bigk_supports(sa.k);
+  if (bigk) {
     if (kernel != TKNN_KERNEL_AUTO && kernel != TKNN_KERNEL_TEAM)
       throw ArgError{TKNN_E_UNSUPPORTED, "the lane and wave kernels keep their lists in registers: k <= 64 (k up to TKNN_MAX_K: TKNN_KERNEL_AUTO or TKNN_KERNEL_TEAM)"};
-    if (sa.d_start_radii && halo_count() > 0)
-      throw ArgError{TKNN_E_UNSUPPORTED, "tknnSolveEx: per-query start radii and a halo tree do not combine (the halo is exchanged for ONE radius)"};
-    if (sa.phase != 0) {
-      if (sa.phase == 3) {
-        if (!sa.d_levels) throw ArgError{TKNN_E_ARG, "tknnSolveEx: phase 3 (unfinished queries only) needs the d_levels of the call that left them"};
-        const int64_t n = bvh_.size();
-        hipLaunchKernelGGL(unfinished_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sa.d_levels, bvh_.view().prim_id, n, boundary_);
-        OWLMI_HIP(hipGetLastError());
-        boundary_valid_ = false;
-      } else if (!boundary_valid_) {
-        throw ArgError{TKNN_E_STATE, "tknnSolveEx: phase 1 / 2 need a tknnHaloSelect count pass since the last build (it marks the boundary queries)"};
-      }
+  } else {
+    if (kernel == TKNN_KERNEL_TEAM && !team_kernel_supports(sa.k))
+      throw ArgError{TKNN_E_UNSUPPORTED, "the team kernels hold up to four neighbours per lane of a 16-lane team: k <= 64"};
+    if (kernel == TKNN_KERNEL_AUTO) {
+      // team kernels for every k the engine takes (<= 64): they hand what it cannot hold (outliers, dense duplicates, start radii
+      // far too large) to lane rounds or the wave kernel by itself; measured fastest from r0 = 2e-5 to
+      // r0 = 0.04 on 10 M uniform points and on the clustered sets of profiles/
+      if (team_kernel_supports(sa.k))
+        kernel = TKNN_KERNEL_TEAM;
+      else
+        kernel = wave_kernel_available() ? TKNN_KERNEL_WAVE : TKNN_KERNEL_LANE;
     }
-    struct HaloOffBig {
-      bool &flag;
-      explicit HaloOffBig(bool &f, bool on) : flag(f) { flag = on; }
-      ~HaloOffBig() { flag = false; }
-    } halo_off_big(ignore_halo_, sa.phase == 1);
-    solve_bigk(sa, info, s);
-    return;
   }
-  if (kernel == TKNN_KERNEL_TEAM && !team_kernel_supports(sa.k))
-    throw ArgError{TKNN_E_UNSUPPORTED, "the team kernels hold up to four neighbours per lane of a 16-lane team: k <= 64"};
-  if (kernel == TKNN_KERNEL_AUTO) {
-    // team kernels for every k the engine takes (<= 64): they hand what it cannot hold (outliers, dense duplicates, start radii
-    // far too large) to lane rounds or the wave kernel by itself; measured fastest from r0 = 2e-5 to
-    // r0 = 0.04 on 10 M uniform points and on the clustered sets of profiles/
-    if (team_kernel_supports(sa.k))
-      kernel = TKNN_KERNEL_TEAM;
-    else
-      kernel = wave_kernel_available() ? TKNN_KERNEL_WAVE : TKNN_KERNEL_LANE;
-  }
-  // Rows whose order depends on how bit-identical fp32 distances are ordered: every kernel lists by
-  // (dist, index) and flags them in tie_; fix_ties redoes them in the reference's order, by the round in
-  // which each neighbour was first a candidate (deviceCode.cu:77-85 -- lists persist over rounds).
-  if (sa.d_start_radii && (kernel != TKNN_KERNEL_TEAM || bvh_.size() >= (1ll << 28)))
+  // per-query start radii and phases: the team kernels only (solve_team takes n < 2^28)
+  const bool team = bigk || (kernel == TKNN_KERNEL_TEAM && bvh_.size() < (1ll << 28));
+  if (sa.d_start_radii && !team)
     throw ArgError{TKNN_E_UNSUPPORTED, "tknnSolveEx: per-query start radii are served by the team kernels only (k <= 64)"};
   if (sa.d_start_radii && halo_count() > 0)
     throw ArgError{TKNN_E_UNSUPPORTED, "tknnSolveEx: per-query start radii and a halo tree do not combine (the halo is exchanged for ONE radius)"};
   if (sa.phase != 0) {
-    if (kernel != TKNN_KERNEL_TEAM || bvh_.size() >= (1ll << 28))
+    if (!team)
       throw ArgError{TKNN_E_UNSUPPORTED, "tknnSolveEx: phases (interior / boundary / unfinished queries) are served by the team kernels only"};
     if (sa.phase == 3) {
       // the queries an earlier call (allow_unfinished) left without a row: d_levels[row] < 0, marked per sorted slot
@@ -607,6 +614,13 @@ void Engine::solve(const SolveArgs &sa, int kernel, tknnSolveInfo *info, hipStre
     explicit HaloOff(bool &f, bool on) : flag(f) { flag = on; }
     ~HaloOff() { flag = false; }
   } halo_off(ignore_halo_, sa.phase == 1);
+  if (bigk) {
+    solve_bigk(sa, info, s);
+    return;
+  }
+  // Rows whose order depends on how bit-identical fp32 distances are ordered: every kernel lists by
+  // (dist, index) and flags them in tie_; fix_ties redoes them in the reference's order, by the round in
+  // which each neighbour was first a candidate (deviceCode.cu:77-85 -- lists persist over rounds).
   tknnSolveInfo mine;
   std::memset(&mine, 0, sizeof mine);
   bool solved = false;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "knn_device.h"
 #include "lbvh.h"
@@ -31,8 +32,63 @@ struct SolveArgs {
   int phase = 0;  // tknnSolveOptions.phase: 0 every query, 1 interior queries in the own tree only, 2 boundary queries
 };
 
+template <int... C>
+struct CapacityTable {
+  // smallest capacity >= k, or -1
+  static constexpr int smallest_for(int k) {
+    int cap = -1;
+    (void)((k <= C ? (cap = C, true) : false) || ...);
+    return cap;
+  }
+  // f(std::integral_constant<int, cap>{}): cap as a compile-time constant; one not in the table takes 64
+  template <class F>
+  static void dispatch(int cap, F &&f) {
+    if (!((cap == C ? (f(std::integral_constant<int, C>{}), true) : false) || ...)) f(std::integral_constant<int, 64>{});
+  }
+};
+// the register-list capacities the lane, wave and repair kernels are instantiated for
+using ListCapacities = CapacityTable<1, 2, 4, 5, 8, 10, 16, 24, 32, 64>;
+
 // smallest register-list capacity instantiated for k, or -1
-int list_capacity_for(int k);
+inline int list_capacity_for(int k) { return ListCapacities::smallest_for(k); }
+
+// counters_ words [1] .. [9] as the team and wave kernels leave them (TeamArgs::counters, WaveArgs::counters)
+struct KernelStats {
+  unsigned long long rounds = 0;         // [1] max levels
+  unsigned long long node_tests = 0;     // [2]
+  unsigned long long point_tests = 0;    // [3]
+  unsigned long long intersections = 0;  // [4] sum of the finished rows' intersections
+  unsigned long long flags = 0;          // [5] error flags: 1 max_rounds, 2 (wave kernel) LDS stack exhausted
+  unsigned long long active_rounds = 0;  // [6] sum of levels
+  unsigned long long unfinished = 0;     // [7]
+  unsigned long long handed_over = 0;    // [8] packet kernel: handed over; walks: stack exhausted (state untouched)
+  unsigned long long first_handover_level = 0;  // [9] packet kernel: min hand-over level
+  static KernelStats from_words(const unsigned long long *w) {
+    KernelStats st;
+    st.rounds = w[1];
+    st.node_tests = w[2];
+    st.point_tests = w[3];
+    st.intersections = w[4];
+    st.flags = w[5];
+    st.active_rounds = w[6];
+    st.unfinished = w[7];
+    st.handed_over = w[8];
+    st.first_handover_level = w[9];
+    return st;
+  }
+};
+
+// the radius of level `rounds - 1`: start_radius doubled in fp32 (hostCode.cpp:321)
+inline float final_radius(float start_radius, int rounds) {
+  float radius = start_radius;
+  for (int t = 1; t < rounds; t++) radius *= 2;
+  return radius;
+}
+// the info of one kernel launch (the tie fields: fix_ties)
+tknnSolveInfo solve_info(const KernelStats &st, float start_radius, int kernel, int list_capacity, float ms);
+// folds the info of a tail (the queries another launch handed over) into the solve's: the larger round count and
+// its radius, work, time and unfinished queries summed; launches only with `count_launches`
+void merge_tail(tknnSolveInfo &into, const tknnSolveInfo &tail, float start_radius, bool count_launches);
 
 // dbscan.hip: out[seg[i]] = min(out[seg[i]], val[i]) for seg[i] >= 0 (tknnSegmentMin)
 void db_segment_min(const int32_t *d_seg, const int64_t *d_val, int64_t n, int64_t *d_out, hipStream_t s);
@@ -89,13 +145,32 @@ class Engine {
   void fix_ties(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
   void reset_stat_stripes(hipStream_t s);
   void fetch_stat_stripes(hipStream_t s);
-  void fold_stat_stripes(bool with_min);
+  KernelStats fold_stat_stripes(bool with_min) const;
+  // trueknn_team.hip: a solve from level 0 without the packet kernel's prep launch (levels: preset to -1 if not null)
+  void reset_solve_state(int32_t *levels, hipStream_t s);
+  // trueknn_team.hip: a zeroed TeamArgs (the team kernels' argument block) with the fields every team launch reads ...
+  template <class A>
+  A team_args(const SolveArgs &sa) const;
+  // ... and the fields only the solves read (team_kernel, team_walk_kernel, bigk_walk_kernel; not tie_fix_kernel)
+  template <class A>
+  void set_solve_args(A &a, const SolveArgs &sa) const;
+  // trueknn_team.hip: team_walk_kernel over nslots sorted slots (slots null: every slot), lane rounds for what outgrew its stack
+  template <class A>
+  tknnSolveInfo walk(const SolveArgs &sa, A a, int nreg, const int32_t *slots, int32_t nslots, int lane_level,
+                     bool count_lane_launches, hipStream_t s);
+  // trueknn_team.hip: the sorted slots whose byte passes `flag`, ascending, into slot_list_; returns their count's device address
+  template <class Flag>
+  int32_t *compact_flagged_slots(const uint8_t *bytes, Flag flag, hipStream_t s);
   void launch_tie_fix(const SolveArgs &sa, const int32_t *slots, int32_t nslots, int blocks, hipStream_t s,
                       const int32_t *d_slot_count = nullptr, int64_t expected_rows = 0);
   int first_step_estimate(const SolveArgs &sa) const;
+  // wave_ws_ / slot_list_ (n slots + their count) grown to at least this size; a failed allocation leaves them empty
+  void *workspace(size_t bytes);
+  int32_t *slot_list(int64_t n);
   float scene_[6] = {0, 0, 0, 0, 0, 0};  // bounds of the built point set (host copy)
 
   int device_ = 0;
+  int cu_count_ = 0;  // compute units of device_ (the launches size their grids by it)
   Lbvh bvh_;
   // the last build was given ids (tknnBuildIds with d_ids): neighbour lists then name points by id, not by input row
   bool ids_given_ = false;

@@ -136,7 +136,7 @@ constexpr int kWalkBlocksPerCu = 4 * (TKNN_WALK_WAVES > 4 ? TKNN_WALK_WAVES : 4)
 constexpr int kXcdCounter = kCounters, kXcdCounterStride = 32;
 // ... and the packet kernel's end-of-wave statistics: five atomics per wave on one cache line, 20 000 at the end of a launch of the
 // benchmark, cost it 0.10 of 6.6 ms (measured by leaving them out).  Striped over the workgroups, a cache line per stripe (the layout
-// is Engine::kStatBase .. in trueknn_engine.h: behind RT-DBSCAN's words), folded by the host into h_counters_[1 .. 9]
+// is Engine::kStatBase .. in trueknn_engine.h: behind RT-DBSCAN's words), folded by the host (Engine::fold_stat_stripes)
 // (kStatStripes, kStatStride, kStatBase: knn_device.h)
 constexpr int kTeamStack = 192;     // wide-pyramid stack entries per wave
 constexpr int kQrecStride = 6;      // floats per LDS query record (layout below)
@@ -2356,28 +2356,44 @@ bool Engine::team_kernel_supports(int k) { return k >= 1 && k <= 64; }
 bool Engine::bigk_supports(int k) { return k > 64 && k <= TKNN_MAX_K; }
 
 // The team kernels' end-of-wave statistics live in stripes (kStatBase): zeroed before a launch of a walk (the packet kernel's
-// prep launch does it itself), copied behind h_counters_[16] after it and folded into h_counters_[1 .. 9] once the stream is idle
+// prep launch does it itself), copied behind h_counters_[16] after it and folded once the stream is idle
 void Engine::reset_stat_stripes(hipStream_t s) {
   OWLMI_HIP(hipMemsetAsync(counters_ + kStatBase, 0, kStatStripes * kStatStride * sizeof(unsigned long long), s));
 }
 void Engine::fetch_stat_stripes(hipStream_t s) {
   OWLMI_HIP(hipMemcpyAsync(h_counters_ + 16, counters_ + kStatBase, kStatStripes * kStatStride * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 }
-void Engine::fold_stat_stripes(bool with_min) {
-  for (int i = 1; i < 10; i++) h_counters_[i] = i == 9 && with_min ? ~0ull : 0ull;
+KernelStats Engine::fold_stat_stripes(bool with_min) const {
+  KernelStats sum;
+  if (with_min) sum.first_handover_level = ~0ull;
   for (int j = 0; j < kStatStripes; j++) {
-    const unsigned long long *st = h_counters_ + 16 + j * kStatStride;
-    h_counters_[1] = std::max(h_counters_[1], st[1]);
-    for (int i : {2, 3, 4, 6, 7, 8}) h_counters_[i] += st[i];
-    h_counters_[5] |= st[5];
-    if (with_min) h_counters_[9] = std::min(h_counters_[9], st[9]);
+    const KernelStats st = KernelStats::from_words(h_counters_ + 16 + j * kStatStride);
+    sum.rounds = std::max(sum.rounds, st.rounds);
+    sum.node_tests += st.node_tests;
+    sum.point_tests += st.point_tests;
+    sum.intersections += st.intersections;
+    sum.flags |= st.flags;
+    sum.active_rounds += st.active_rounds;
+    sum.unfinished += st.unfinished;
+    sum.handed_over += st.handed_over;
+    if (with_min) sum.first_handover_level = std::min(sum.first_handover_level, st.first_handover_level);
   }
+  return sum;
 }
 
-// k > 64: every query through bigk_walk_kernel, one query per team, the k-lists in memory (one per resident team)
-void Engine::solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
+void Engine::reset_solve_state(int32_t *levels, hipStream_t s) {
   const int64_t n = bvh_.size();
-  TeamArgs a;
+  OWLMI_HIP(hipMemsetAsync(tie_, 0, (size_t)n, s));
+  OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounters * sizeof(unsigned long long), s));
+  OWLMI_HIP(hipMemsetAsync(done_, 0, (size_t)n, s));
+  OWLMI_HIP(hipMemsetAsync(isect_sorted_, 0, (size_t)n * sizeof(int64_t), s));
+  OWLMI_HIP(hipMemsetAsync(next_level_, 0, (size_t)n * sizeof(int32_t), s));
+  if (levels) OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)n * sizeof(int32_t), s));
+}
+
+template <class A>
+A Engine::team_args(const SolveArgs &sa) const {
+  A a;
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
   a.halo = halo_view();
@@ -2386,79 +2402,70 @@ void Engine::solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
   a.start_radius = sa.start_radius;
   a.start_radii = sa.d_start_radii;
   a.k = sa.k;
-  a.max_rounds = sa.max_rounds;
-  a.allow_unfinished = sa.allow_unfinished ? 1 : 0;
-  // the first level that keeps a list whatever the level before has counted: where a box is expected to hold k / 2 others at the
-  // scene's mean density (a work estimate only; a per-query radius schedule has none: every level keeps its list)
-  a.first_step = sa.d_start_radii ? 0 : first_step_estimate(sa) - 1;
   a.out_idx = sa.d_idx;
   a.out_dist = sa.d_dist;
-  a.out_isect = sa.d_isect;
   a.out_fb = sa.d_fb;
-  a.out_level = sa.d_levels;
-  a.done = done_;
   a.tie = tie_;
   a.tie_list = tie_list_;
+  a.counters = counters_;
+  return a;
+}
+
+template <class A>
+void Engine::set_solve_args(A &a, const SolveArgs &sa) const {
+  a.max_rounds = sa.max_rounds;
+  a.allow_unfinished = sa.allow_unfinished ? 1 : 0;
+  a.out_isect = sa.d_isect;
+  a.out_level = sa.d_levels;
+  a.done = done_;
   a.skip = sa.phase ? boundary_ : nullptr;
   a.skip_is = sa.phase == 1 ? 1 : 0;
   a.isect_sorted = isect_sorted_;
   a.next_level = next_level_;
-  a.counters = counters_;
-  const bool with_halo = halo_count() > 0;
-  hipDeviceProp_t prop;
-  OWLMI_HIP(hipGetDeviceProperties(&prop, device_));
+}
+
+template <class Flag>
+int32_t *Engine::compact_flagged_slots(const uint8_t *bytes, Flag flag, hipStream_t s) {
+  const int64_t n = bvh_.size();
+  int32_t *slots = slot_list(n), *d_count = slots + n;
+  hipcub::CountingInputIterator<int32_t> iota(0);
+  hipcub::TransformInputIterator<bool, Flag, const uint8_t *> flags(bytes, flag);
+  size_t tmp_bytes = 0;
+  OWLMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, iota, flags, slots, d_count, (int)n, s));
+  OWLMI_HIP(hipcub::DeviceSelect::Flagged(workspace(tmp_bytes), tmp_bytes, iota, flags, slots, d_count, (int)n, s));
+  return d_count;
+}
+
+// k > 64: every query through bigk_walk_kernel, one query per team, the k-lists in memory (one per resident team)
+void Engine::solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
+  const int64_t n = bvh_.size();
+  TeamArgs a = team_args<TeamArgs>(sa);
+  set_solve_args(a, sa);
+  // the first level that keeps a list whatever the level before has counted: where a box is expected to hold k / 2 others at the
+  // scene's mean density (a work estimate only; a per-query radius schedule has none: every level keeps its list)
+  a.first_step = sa.d_start_radii ? 0 : first_step_estimate(sa) - 1;
+  a.grab = 1;
   int per_cu = 4;
-  const void *entry = with_halo ? (const void *)bigk_walk_kernel<true> : (const void *)bigk_walk_kernel<false>;
+  const void *entry = halo_count() > 0 ? (const void *)bigk_walk_kernel<true> : (const void *)bigk_walk_kernel<false>;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, entry, kTeamBlock, 0) != hipSuccess) per_cu = 4;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)prop.multiProcessorCount * std::max(1, per_cu)));
-  const int chunks = (sa.k + 15) / 16;
-  const size_t list_bytes = (size_t)blocks * 4 * (size_t)chunks * 16 * sizeof(BigKey);
-  if (list_bytes > wave_ws_bytes_) {
-    if (wave_ws_) (void)hipFree(wave_ws_);
-    wave_ws_ = nullptr;
-    wave_ws_bytes_ = 0;
-    OWLMI_HIP(hipMalloc(&wave_ws_, list_bytes));
-    wave_ws_bytes_ = list_bytes;
-  }
-  OWLMI_HIP(hipMemsetAsync(tie_, 0, (size_t)n, s));  // (three-word keys: no row is left to the tie pass)
-  OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounters * sizeof(unsigned long long), s));
-  OWLMI_HIP(hipMemsetAsync(done_, 0, (size_t)n, s));
-  OWLMI_HIP(hipMemsetAsync(isect_sorted_, 0, (size_t)n * sizeof(int64_t), s));
-  OWLMI_HIP(hipMemsetAsync(next_level_, 0, (size_t)n * sizeof(int32_t), s));
-  if (sa.d_levels && sa.phase < 2) OWLMI_HIP(hipMemsetAsync(sa.d_levels, 0xff, (size_t)n * sizeof(int32_t), s));  // (phases 2, 3 complete an earlier call's rows)
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)cu_count_ * std::max(1, per_cu)));
+  int chunks = (sa.k + 15) / 16;
+  BigKey *lists = (BigKey *)workspace((size_t)blocks * 4 * (size_t)chunks * 16 * sizeof(BigKey));
+  // (three-word keys: no row is left to the tie pass; phases 2, 3 complete an earlier call's rows and levels)
+  reset_solve_state(sa.phase < 2 ? sa.d_levels : nullptr, s);
   reset_stat_stripes(s);
   OWLMI_HIP(hipEventRecord(ev_a_, s));
-  {
-    BigKey *lists = (BigKey *)wave_ws_;
-    int ch = chunks;
-    a.grab = 1;
-    void *kargs[] = {(void *)&a, (void *)&lists, (void *)&ch};
-    OWLMI_HIP(hipLaunchKernel(entry, dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
-  }
+  void *kargs[] = {(void *)&a, (void *)&lists, (void *)&chunks};
+  OWLMI_HIP(hipLaunchKernel(entry, dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   fetch_stat_stripes(s);
   OWLMI_HIP(hipStreamSynchronize(s));
-  fold_stat_stripes(false);
+  const KernelStats st = fold_stat_stripes(false);
   float ms = 0;
   OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  if (h_counters_[8]) throw ArgError{TKNN_E_UNSUPPORTED, "k > 64: a query's walk outgrew its stack (a pyramid of more than six levels?)"};
-  tknnSolveInfo mine;
-  std::memset(&mine, 0, sizeof mine);
-  mine.rounds = (int)h_counters_[1];
-  mine.node_tests = (int64_t)h_counters_[2];
-  mine.point_tests = (int64_t)h_counters_[3];
-  mine.total_intersections = (int64_t)h_counters_[4];
-  mine.total_active_rounds = (int64_t)h_counters_[6];
-  mine.unfinished = (int64_t)h_counters_[7];
-  mine.solve_ms = ms;
-  mine.dominant_kernel_ms = ms;
-  mine.dominant_kernel_launches = 1;
-  mine.kernel_used = TKNN_KERNEL_TEAM;
-  mine.list_capacity = chunks * 16;
-  float radius = sa.start_radius;
-  for (int t = 1; t < mine.rounds; t++) radius *= 2;
-  mine.final_radius = radius;
+  if (st.handed_over) throw ArgError{TKNN_E_UNSUPPORTED, "k > 64: a query's walk outgrew its stack (a pyramid of more than six levels?)"};
+  const tknnSolveInfo mine = solve_info(st, sa.start_radius, TKNN_KERNEL_TEAM, chunks * 16, ms);
   if (mine.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
   ties_early_ = true;  // nothing flagged, nothing to redo
   early_tie_rows_ = early_tie_left_ = 0;
@@ -2469,27 +2476,13 @@ void Engine::solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
 
 void Engine::launch_tie_fix(const SolveArgs &sa, const int32_t *slots, int32_t nslots, int blocks, hipStream_t s, const int32_t *d_slot_count,
                             int64_t expected_rows) {
-  TeamArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.bvh = bvh_.view();
-  a.halo = halo_view();
-  a.wide[0] = bvh_.wide_view();
-  if (halo_count() > 0) a.wide[1] = halo_.wide_view();
-  a.start_radius = sa.start_radius;
-  a.start_radii = sa.d_start_radii;
-  a.k = sa.k;
-  a.out_idx = sa.d_idx;
-  a.out_dist = sa.d_dist;
-  a.out_fb = sa.d_fb;
-  a.tie = tie_;
-  a.tie_list = tie_list_;
+  TeamArgs a = team_args<TeamArgs>(sa);
   a.slot_count = d_slot_count;
   // (10 M taxi-like points, k = 10 / 24, 0.78 / 2.3 M rows, 24 workgroups per CU: turns of 4 / 8 / 12 / 24 / 32 slots 2.55 / 1.42 / 1.08 /
   // 0.89 / 0.94 ms and 7.2 / 3.8 / 2.6 / 1.81 / 1.85 ms; 64 and more slots a turn: the waves' own chains of loads show, 2.8 ms and up)
   a.grab = grab_for(expected_rows, blocks, 6, 6);
   const bool look = !ids_given_ && !(getenv("TKNN_TIE_LOOK") && !strcmp(getenv("TKNN_TIE_LOOK"), "0"));  // (TKNN_TIE_LOOK=0: A/B switch)
   a.row_slot = look ? bvh_.row_slot_device() : nullptr;
-  a.counters = counters_;
   using FixEntry = void (*)(TeamArgs, const int32_t *, int32_t);
   static const FixEntry entries[2][4] = {{tie_fix_kernel<false, 1>, tie_fix_kernel<false, 2>, tie_fix_kernel<false, 3>, tie_fix_kernel<false, 4>},
                                          {tie_fix_kernel<true, 1>, tie_fix_kernel<true, 2>, tie_fix_kernel<true, 3>, tie_fix_kernel<true, 4>}};
@@ -2511,16 +2504,11 @@ void Engine::fix_ties(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
     return;
   }
   const int64_t n = bvh_.size();
-  hipDeviceProp_t prop;
-  OWLMI_HIP(hipGetDeviceProperties(&prop, device_));
-  auto launch = [&](int blocks, const int32_t *slots, int32_t nslots, const int32_t *d_len = nullptr, int64_t expected = 0) {
-    launch_tie_fix(sa, slots, nslots, blocks, s, d_len, expected);
-  };
   OWLMI_HIP(hipMemsetAsync(counters_ + kTieCounter + 1, 0, 3 * sizeof(unsigned long long), s));  // work cursor, rows left
   // First go: the kernels' own list, count read on the device -- no host round trip before the launch;
   // the usual handful of rows (or none) costs one small launch behind the solve.
   OWLMI_HIP(hipEventRecord(ev_a_, s));
-  launch(std::min(prop.multiProcessorCount * 4, kTieListCap / 4), tie_list_, -1);  // a team per listed row
+  launch_tie_fix(sa, tie_list_, -1, std::min(cu_count_ * 4, kTieListCap / 4), s);  // a team per listed row
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_ + kTieCounter, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));
@@ -2530,29 +2518,12 @@ void Engine::fix_ties(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
   if (flagged > kTieListCap) {
     // more than the list holds (quantised coordinates, lattices): all flagged slots, compacted from tie_
     // (rows redone twice come out the same: the gate is the row's k-th distance, which no order changes)
-    if (n > slot_list_cap_) {
-      if (slot_list_) (void)hipFree(slot_list_);
-      slot_list_ = nullptr;
-      OWLMI_HIP(hipMalloc((void **)&slot_list_, ((size_t)n + 1) * sizeof(int32_t)));
-      slot_list_cap_ = n;
-    }
-    int32_t *d_count = slot_list_ + n;
-    hipcub::CountingInputIterator<int32_t> iota(0);
-    hipcub::TransformInputIterator<bool, HasTie, const uint8_t *> flags(tie_, HasTie{});
-    size_t tmp_bytes = 0;
-    OWLMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, iota, flags, slot_list_, d_count, (int)n, s));
-    if (tmp_bytes > wave_ws_bytes_) {
-      if (wave_ws_) (void)hipFree(wave_ws_);
-      wave_ws_ = nullptr;
-      OWLMI_HIP(hipMalloc(&wave_ws_, tmp_bytes));
-      wave_ws_bytes_ = tmp_bytes;
-    }
-    OWLMI_HIP(hipcub::DeviceSelect::Flagged(wave_ws_, tmp_bytes, iota, flags, slot_list_, d_count, (int)n, s));
+    const int32_t *d_count = compact_flagged_slots(tie_, HasTie{}, s);
     OWLMI_HIP(hipMemsetAsync(counters_ + kTieCounter + 1, 0, 3 * sizeof(unsigned long long), s));
     OWLMI_HIP(hipEventRecord(ev_a_, s));
     // the list's length is read on the device (d_count): `flagged` counts flag calls, an upper bound
-    launch((int)std::min<int64_t>((std::min<int64_t>(flagged, n) + 3) / 4, (int64_t)prop.multiProcessorCount * 24), slot_list_, -2, d_count,
-           std::min<int64_t>(flagged, n));
+    const int64_t rows = std::min<int64_t>(flagged, n);
+    launch_tie_fix(sa, slot_list_, -2, (int)std::min<int64_t>((rows + 3) / 4, (int64_t)cu_count_ * 24), s, d_count, rows);
     OWLMI_HIP(hipEventRecord(ev_b_, s));
     OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_ + kTieCounter, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     OWLMI_HIP(hipStreamSynchronize(s));
@@ -2584,22 +2555,46 @@ int Engine::first_step_estimate(const SolveArgs &sa) const {
   return 3;
 }
 
+// One query per team, each from the level its solve state holds: what exhausts its stack keeps that state untouched and goes
+// on to lane rounds from lane_level
+template <class A>
+tknnSolveInfo Engine::walk(const SolveArgs &sa, A a, int nreg, const int32_t *slots, int32_t nslots, int lane_level,
+                           bool count_lane_launches, hipStream_t s) {
+  using WalkEntry = void (*)(A, const int32_t *, int32_t);
+  static const WalkEntry walks[2][4] = {{team_walk_kernel<false, 1>, team_walk_kernel<false, 2>, team_walk_kernel<false, 3>, team_walk_kernel<false, 4>},
+                                        {team_walk_kernel<true, 1>, team_walk_kernel<true, 2>, team_walk_kernel<true, 3>, team_walk_kernel<true, 4>}};
+  OWLMI_HIP(hipMemsetAsync(counters_, 0, 16 * sizeof(unsigned long long), s));
+  reset_stat_stripes(s);
+  const int blocks = (int)std::min<int64_t>(((int64_t)nslots + 3) / 4, (int64_t)cu_count_ * kWalkBlocksPerCu);
+  a.grab = 1;  // (queries differ too much for longer turns: measured, see TeamArgs::grab)
+  void *kargs[] = {(void *)&a, (void *)&slots, (void *)&nslots};
+  OWLMI_HIP(hipEventRecord(ev_a_, s));
+  OWLMI_HIP(hipLaunchKernel((const void *)walks[halo_count() > 0 ? 1 : 0][nreg - 1], dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
+  OWLMI_HIP(hipGetLastError());
+  OWLMI_HIP(hipEventRecord(ev_b_, s));
+  fetch_stat_stripes(s);
+  OWLMI_HIP(hipStreamSynchronize(s));
+  const KernelStats st = fold_stat_stripes(false);
+  float ms = 0;
+  OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
+  tknnSolveInfo info = solve_info(st, sa.start_radius, TKNN_KERNEL_TEAM, 16 * nreg, ms);
+  if (info.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
+  if (st.handed_over) {
+    if (sa.d_start_radii)
+      throw ArgError{TKNN_E_UNSUPPORTED, "per-query start radii: a query's candidate walk outgrew the team walk's stack (the lane rounds that take over otherwise use one radius per launch)"};
+    tknnSolveInfo rest;
+    std::memset(&rest, 0, sizeof rest);
+    continue_lane(sa, lane_level, &rest, s);
+    merge_tail(info, rest, sa.start_radius, count_lane_launches);
+  }
+  return info;
+}
+
 bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
   const int64_t n = bvh_.size();
   if (n >= (1ll << 28)) return false;  // leaf blocks are addressed by 32-bit byte offsets; the caller takes the wave kernel
-  TeamArgs a;
-  a.bvh = bvh_.view();
-  a.halo = halo_view();
-  a.wide[0] = bvh_.wide_view();
-  if (halo_count() > 0)
-    a.wide[1] = halo_.wide_view();
-  else
-    std::memset(&a.wide[1], 0, sizeof(a.wide[1]));
-  a.start_radius = sa.start_radius;
-  a.start_radii = sa.d_start_radii;
-  a.k = sa.k;
-  a.max_rounds = sa.max_rounds;
-  a.allow_unfinished = sa.allow_unfinished ? 1 : 0;
+  TeamArgs a = team_args<TeamArgs>(sa);
+  set_solve_args(a, sa);
   a.first_step = sa.d_start_radii ? 1 : first_step_estimate(sa);  // (the estimate is from ONE start radius and the mean density)
   {
     // the first gather also lists the blocks of the level after its step unless the boxes of the step's last level are
@@ -2617,91 +2612,24 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     if (halo_count() > 0) dims = 3;
     a.tie_span = dims >= 3 ? 1.73206f : (dims == 2 ? 1.41422f : 1.00001f);
   }
-  a.diag = 0;
   if (TKNN_DIAG_BUILD)
     if (const char *d = getenv("TKNN_TEAM_DIAG")) a.diag = atoi(d);
   a.ngroups = (int32_t)((n + 63) / 64);
-  a.out_idx = sa.d_idx;
-  a.out_dist = sa.d_dist;
-  a.out_isect = sa.d_isect;
-  a.out_fb = sa.d_fb;
-  a.out_level = sa.d_levels;
-  a.done = done_;
-  a.tie = tie_;
-  a.tie_list = tie_list_;
-  a.slot_count = nullptr;
-  a.skip = sa.phase ? boundary_ : nullptr;
-  a.skip_is = sa.phase == 1 ? 1 : 0;
-  a.isect_sorted = isect_sorted_;
-  a.next_level = next_level_;
-  a.counters = counters_;
 
-  hipDeviceProp_t prop;
-  OWLMI_HIP(hipGetDeviceProperties(&prop, device_));
-  int per_cu = 2;
-  static_assert(kDbStripes * 8 >= 8 * kXcdCounterStride, "the packet counters borrow the words of RT-DBSCAN's striped statistics");
   const int nreg = nreg_for(sa.k);  // list registers per lane
-  const size_t lds = (size_t)kTeamBlock / 64 * (size_t)(nreg == 1 ? TeamLayout<1>::kTeamLds : (nreg == 2 ? TeamLayout<2>::kTeamLds
-                                                         : (nreg == 3 ? TeamLayout<3>::kTeamLds : TeamLayout<4>::kTeamLds)));
-  const bool with_halo = halo_count() > 0;
-  const int nreg_at = nreg - 1;  // index into the tables of instantiations
   const char *walk_all = getenv("TKNN_TEAM_WALK_ALL");    // measurements only: k > 32 without the packet kernel
   if (sa.k > 32 && walk_all && atoi(walk_all)) {
     // (33 <= k <= 64 as it was before the packet kernel had four list registers per lane:) every
     // query goes through the team walk, four list registers per lane, from level 0
-    OWLMI_HIP(hipMemsetAsync(tie_, 0, (size_t)n, s));
-    OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounters * sizeof(unsigned long long), s));
-    OWLMI_HIP(hipMemsetAsync(done_, 0, (size_t)n, s));
-    OWLMI_HIP(hipMemsetAsync(isect_sorted_, 0, (size_t)n * sizeof(int64_t), s));
-    OWLMI_HIP(hipMemsetAsync(next_level_, 0, (size_t)n * sizeof(int32_t), s));
-    if (sa.d_levels) OWLMI_HIP(hipMemsetAsync(sa.d_levels, 0xff, (size_t)n * sizeof(int32_t), s));
-    const int walk_blocks = (int)std::min<int64_t>((n + 3) / 4, (int64_t)prop.multiProcessorCount * kWalkBlocksPerCu);
-    a.grab = 1;  // (queries differ too much for longer turns: measured, see TeamArgs::grab)
-    reset_stat_stripes(s);
-    OWLMI_HIP(hipEventRecord(ev_a_, s));
-    if (with_halo)
-      hipLaunchKernelGGL((team_walk_kernel<true, 4>), dim3(walk_blocks), dim3(kTeamBlock), 0, s, a, (const int32_t *)nullptr, (int32_t)n);
-    else
-      hipLaunchKernelGGL((team_walk_kernel<false, 4>), dim3(walk_blocks), dim3(kTeamBlock), 0, s, a, (const int32_t *)nullptr, (int32_t)n);
-    OWLMI_HIP(hipGetLastError());
-    OWLMI_HIP(hipEventRecord(ev_b_, s));
-    fetch_stat_stripes(s);
-    OWLMI_HIP(hipStreamSynchronize(s));
-    fold_stat_stripes(false);
-    float ms = 0;
-    OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-    tknnSolveInfo mine;
-    std::memset(&mine, 0, sizeof mine);
-    mine.rounds = (int)h_counters_[1];
-    mine.node_tests = (int64_t)h_counters_[2];
-    mine.point_tests = (int64_t)h_counters_[3];
-    mine.total_intersections = (int64_t)h_counters_[4];
-    mine.total_active_rounds = (int64_t)h_counters_[6];
-    mine.unfinished = (int64_t)h_counters_[7];
-    mine.solve_ms = ms;
-    mine.dominant_kernel_ms = ms;
-    mine.dominant_kernel_launches = 1;
-    mine.kernel_used = TKNN_KERNEL_TEAM;
-    mine.list_capacity = 64;
-    if (mine.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
-    if (h_counters_[8]) {  // stacks exhausted: those queries' state is untouched, lane rounds take them
-      tknnSolveInfo rest;
-      std::memset(&rest, 0, sizeof rest);
-      continue_lane(sa, 0, &rest, s);
-      mine.rounds = std::max(mine.rounds, rest.rounds);
-      mine.node_tests += rest.node_tests;
-      mine.point_tests += rest.point_tests;
-      mine.total_intersections += rest.total_intersections;
-      mine.total_active_rounds += rest.total_active_rounds;
-      mine.unfinished += rest.unfinished;
-      mine.solve_ms += rest.solve_ms;
-    }
-    float radius = sa.start_radius;
-    for (int t = 1; t < mine.rounds; t++) radius *= 2;
-    mine.final_radius = radius;
-    if (info) *info = mine;
+    reset_solve_state(sa.d_levels, s);
+    const tknnSolveInfo all = walk(sa, a, 4, nullptr, (int32_t)n, 0, /*count_lane_launches=*/false, s);
+    if (info) *info = all;
     return true;
   }
+  int per_cu = 2;
+  static_assert(kDbStripes * 8 >= 8 * kXcdCounterStride, "the packet counters borrow the words of RT-DBSCAN's striped statistics");
+  const size_t lds = (size_t)kTeamBlock / 64 * (size_t)(nreg == 1 ? TeamLayout<1>::kTeamLds : (nreg == 2 ? TeamLayout<2>::kTeamLds
+                                                         : (nreg == 3 ? TeamLayout<3>::kTeamLds : TeamLayout<4>::kTeamLds)));
   const bool full_list = sa.k == 16 * nreg;  // no spare list entry to see a tie with the row's last in
   using TeamEntry = void (*)(TeamArgs);
   static const TeamEntry entries[2][4][2] = {
@@ -2709,7 +2637,7 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
        {team_kernel<false, 3, false>, team_kernel<false, 3, true>}, {team_kernel<false, 4, false>, team_kernel<false, 4, true>}},
       {{team_kernel<true, 1, false>, team_kernel<true, 1, true>}, {team_kernel<true, 2, false>, team_kernel<true, 2, true>},
        {team_kernel<true, 3, false>, team_kernel<true, 3, true>}, {team_kernel<true, 4, false>, team_kernel<true, 4, true>}}};
-  const TeamEntry entry = entries[with_halo ? 1 : 0][nreg_at][full_list ? 1 : 0];
+  const TeamEntry entry = entries[halo_count() > 0 ? 1 : 0][nreg - 1][full_list ? 1 : 0];
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)entry, kTeamBlock, lds) != hipSuccess) per_cu = 2;
   // (the query divides the CU's LDS by the byte; the hardware hands it out in granules: scripts/microbench/lds_granule.hip --
   // a launch of more workgroups than fit would leave the surplus waiting for a slot and then for the last packets)
@@ -2717,12 +2645,12 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
   if (const char *cap = getenv("TKNN_TEAM_WAVES_PER_CU"))  // measurements only: how the packet kernel's time scales with the waves in flight
     per_cu = std::max(1, std::min(per_cu, atoi(cap)));
   const int64_t want = (a.ngroups + kTeamBlock / 64 - 1) / (kTeamBlock / 64);
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)prop.multiProcessorCount * per_cu));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cu_count_ * per_cu));
 
   // one launch instead of six fills (each costs a few microseconds of its own on the stream): done = 1,
   // tie = 0, all counters 0 except [9] (min hand-over level) = ~0, levels = -1
   // (phases 2 and 3 complete the rows and levels an earlier call has begun: levels are preset once, by phase 0 or 1)
-  hipLaunchKernelGGL(team_prep_kernel, dim3(prop.multiProcessorCount * 4), dim3(256), 0, s, done_, tie_, n, counters_, sa.phase >= 2 ? nullptr : sa.d_levels);
+  hipLaunchKernelGGL(team_prep_kernel, dim3(cu_count_ * 4), dim3(256), 0, s, done_, tie_, n, counters_, sa.phase >= 2 ? nullptr : sa.d_levels);
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   {
     void *kargs[] = {(void *)&a};
@@ -2732,17 +2660,16 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   // the tie pass over the rows this kernel has flagged and listed, count read on the device: launched
   // before the host knows anything, so the usual handful costs no round trip of its own
-  launch_tie_fix(sa, tie_list_, -1, std::min(prop.multiProcessorCount * 4, kTieListCap / 4), s);
+  launch_tie_fix(sa, tie_list_, -1, std::min(cu_count_ * 4, kTieListCap / 4), s);
   OWLMI_HIP(hipEventRecord(ev_c_, s));
   static_assert(kStatBase == Engine::kStatBase && kStatStripes == Engine::kStatStripes && kStatStride == Engine::kStatStride, "one layout");
   fetch_stat_stripes(s);
   OWLMI_HIP(hipMemcpyAsync(h_counters_ + 10, counters_ + kTieCounter, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));
-  h_counters_[0] = 0;
-  fold_stat_stripes(true);
+  const KernelStats st = fold_stat_stripes(true);
   float ms = 0;
   OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  if (h_counters_[8] == 0 && h_counters_[10] <= (unsigned long long)kTieListCap) {  // nothing handed over, every flagged row listed
+  if (st.handed_over == 0 && h_counters_[10] <= (unsigned long long)kTieListCap) {  // nothing handed over, every flagged row listed
     ties_early_ = true;
     early_tie_rows_ = (int64_t)h_counters_[10];
     early_tie_left_ = (int64_t)h_counters_[12];
@@ -2756,7 +2683,7 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     unsigned long long wave_steps = 0;
     OWLMI_HIP(hipMemcpy(&wave_steps, counters_ + 15, sizeof wave_steps, hipMemcpyDeviceToHost));
     fprintf(stderr, "[team diag] block steps: %.3g wave steps x 4 teams for %.3g listed blocks (lockstep efficiency %.1f%%)\n",
-            (double)wave_steps, (double)h_counters_[3] / LBVH_BLOCK, 100.0 * ((double)h_counters_[3] / LBVH_BLOCK) / (4.0 * (double)wave_steps));
+            (double)wave_steps, (double)st.point_tests / LBVH_BLOCK, 100.0 * ((double)st.point_tests / LBVH_BLOCK) / (4.0 * (double)wave_steps));
     if (a.diag & 16) {
       unsigned long long g[2];
       OWLMI_HIP(hipMemcpy(g, counters_ + 26, sizeof g, hipMemcpyDeviceToHost));
@@ -2784,25 +2711,9 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
             100 * t[0] / tot, 100 * t[1] / tot, 100 * t[2] / tot, 100 * t[3] / tot, 100 * t[4] / tot);
   }
 #endif
-  if (h_counters_[5] & 1ull) throw RoundsExceeded{};
-  if (info) {
-    const int rounds = (int)h_counters_[1];
-    info->rounds = rounds;
-    float radius = sa.start_radius;
-    for (int t = 1; t < rounds; t++) radius *= 2;
-    info->final_radius = radius;
-    info->node_tests = (int64_t)h_counters_[2];
-    info->point_tests = (int64_t)h_counters_[3];
-    info->total_intersections = (int64_t)h_counters_[4];
-    info->total_active_rounds = (int64_t)h_counters_[6];
-    info->solve_ms = ms;
-    info->dominant_kernel_ms = ms;
-    info->dominant_kernel_launches = 1;
-    info->kernel_used = TKNN_KERNEL_TEAM;
-    info->list_capacity = 16 * nreg;
-    info->unfinished = (int64_t)h_counters_[7];
-  }
-  const unsigned long long handed = h_counters_[8];
+  if (st.flags & 1ull) throw RoundsExceeded{};
+  if (info) *info = solve_info(st, sa.start_radius, TKNN_KERNEL_TEAM, 16 * nreg, ms);
+  const unsigned long long handed = st.handed_over;
   if (handed) {
     // Stragglers whose candidate lists outgrew the LDS lists (outliers of a clustered set, whose boxes
     // grow over whole clusters; dense duplicates): team_walk_kernel, one query per team, from the level
@@ -2818,75 +2729,13 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     const bool by_wave = !sa.d_start_radii && wave_kernel_available() &&
                          (force ? !strcmp(force, "wave") : (handed * 4ull >= (unsigned long long)n && sa.k <= 32));
     const bool by_walk = !by_wave && !(force && !strcmp(force, "lane"));
-    const int first_handover_level = (int)h_counters_[9];
+    const int first_handover_level = (int)st.first_handover_level;
     if (by_wave) {
       solve_wave(sa, &tail, s, /*only_unfinished=*/true);
     } else if (by_walk) {
-      // one query per team (team_walk_kernel): the stragglers' sorted slots as a compact ascending list
-      if (n > slot_list_cap_) {
-        if (slot_list_) (void)hipFree(slot_list_);
-        slot_list_ = nullptr;
-        OWLMI_HIP(hipMalloc((void **)&slot_list_, ((size_t)n + 1) * sizeof(int32_t)));
-        slot_list_cap_ = n;
-      }
-      int32_t *d_count = slot_list_ + n;
-      hipcub::CountingInputIterator<int32_t> iota(0);
-      hipcub::TransformInputIterator<bool, NotDone, const uint8_t *> flags(done_, NotDone{});
-      size_t tmp_bytes = 0;
-      OWLMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, iota, flags, slot_list_, d_count, (int)n, s));
-      if (tmp_bytes > wave_ws_bytes_) {
-        if (wave_ws_) (void)hipFree(wave_ws_);
-        wave_ws_ = nullptr;
-        OWLMI_HIP(hipMalloc(&wave_ws_, tmp_bytes));
-        wave_ws_bytes_ = tmp_bytes;
-      }
-      OWLMI_HIP(hipcub::DeviceSelect::Flagged(wave_ws_, tmp_bytes, iota, flags, slot_list_, d_count, (int)n, s));
-      OWLMI_HIP(hipMemsetAsync(counters_, 0, 16 * sizeof(unsigned long long), s));
-      reset_stat_stripes(s);
-      const int walk_blocks = (int)std::min<int64_t>((int64_t)(handed + 3) / 4, (int64_t)prop.multiProcessorCount * kWalkBlocksPerCu);
-      OWLMI_HIP(hipEventRecord(ev_a_, s));
-      {
-        using WalkEntry = void (*)(TeamArgs, const int32_t *, int32_t);
-        static const WalkEntry walks[2][4] = {{team_walk_kernel<false, 1>, team_walk_kernel<false, 2>, team_walk_kernel<false, 3>, team_walk_kernel<false, 4>},
-                                              {team_walk_kernel<true, 1>, team_walk_kernel<true, 2>, team_walk_kernel<true, 3>, team_walk_kernel<true, 4>}};
-        const int32_t *slots = slot_list_;
-        int32_t nslots = (int32_t)handed;
-        a.grab = 1;
-        void *kargs[] = {(void *)&a, (void *)&slots, (void *)&nslots};
-        OWLMI_HIP(hipLaunchKernel((const void *)walks[with_halo ? 1 : 0][nreg_at], dim3(walk_blocks), dim3(kTeamBlock), kargs, 0, s));
-      }
-      OWLMI_HIP(hipGetLastError());
-      OWLMI_HIP(hipEventRecord(ev_b_, s));
-      fetch_stat_stripes(s);
-      OWLMI_HIP(hipStreamSynchronize(s));
-      fold_stat_stripes(false);
-      float walk_ms = 0;
-      OWLMI_HIP(hipEventElapsedTime(&walk_ms, ev_a_, ev_b_));
-      tail.rounds = (int)h_counters_[1];
-      tail.node_tests = (int64_t)h_counters_[2];
-      tail.point_tests = (int64_t)h_counters_[3];
-      tail.total_intersections = (int64_t)h_counters_[4];
-      tail.total_active_rounds = (int64_t)h_counters_[6];
-      tail.unfinished = (int64_t)h_counters_[7];
-      tail.solve_ms = walk_ms;
-      tail.dominant_kernel_launches = 1;
-      const unsigned long long left = h_counters_[8];  // stack exhausted: state untouched, lane rounds take them
-      if (tail.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
-      if (left && sa.d_start_radii)
-        throw ArgError{TKNN_E_UNSUPPORTED, "per-query start radii: a query's candidate walk outgrew the team walk's stack (the lane rounds that take over otherwise use one radius per launch)"};
-      if (left) {
-        tknnSolveInfo rest;
-        std::memset(&rest, 0, sizeof rest);
-        continue_lane(sa, first_handover_level, &rest, s);
-        tail.rounds = std::max(tail.rounds, rest.rounds);
-        tail.node_tests += rest.node_tests;
-        tail.point_tests += rest.point_tests;
-        tail.total_intersections += rest.total_intersections;
-        tail.total_active_rounds += rest.total_active_rounds;
-        tail.unfinished += rest.unfinished;
-        tail.solve_ms += rest.solve_ms;
-        tail.dominant_kernel_launches += rest.dominant_kernel_launches;
-      }
+      // the stragglers' sorted slots as a compact ascending list
+      compact_flagged_slots(done_, NotDone{}, s);
+      tail = walk(sa, a, nreg, slot_list_, (int32_t)handed, first_handover_level, /*count_lane_launches=*/true, s);
     } else {
       if (sa.d_start_radii) throw ArgError{TKNN_E_UNSUPPORTED, "per-query start radii are served by the team kernels only (TKNN_TEAM_TAIL=lane)"};
       continue_lane(sa, first_handover_level, &tail, s);
@@ -2895,18 +2744,7 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
       fprintf(stderr, "[team] %llu of %lld queries handed over from level %d on: team kernel %.2f ms, %s %.2f ms (%d launches)\n",
               handed, (long long)n, first_handover_level, ms, by_wave ? "wave kernel" : (by_walk ? "team walk" : "lane rounds"), tail.solve_ms,
               tail.dominant_kernel_launches);
-    if (info) {
-      info->rounds = std::max(info->rounds, tail.rounds);
-      float radius = sa.start_radius;
-      for (int t = 1; t < info->rounds; t++) radius *= 2;
-      info->final_radius = radius;
-      info->node_tests += tail.node_tests;
-      info->point_tests += tail.point_tests;
-      info->total_intersections += tail.total_intersections;
-      info->total_active_rounds += tail.total_active_rounds;
-      info->solve_ms += tail.solve_ms;
-      info->unfinished += tail.unfinished;
-    }
+    if (info) merge_tail(*info, tail, sa.start_radius, /*count_launches=*/false);
   }
   return true;
 }

@@ -407,46 +407,23 @@ void Engine::solve_wave(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s,
   a.out_fb = sa.d_fb;
   a.counters = counters_;
 
-  hipDeviceProp_t prop;
-  OWLMI_HIP(hipGetDeviceProperties(&prop, device_));
   int per_cu = 1;
-  switch (cap) {
-    case 1: per_cu = max_blocks_per_cu<1>(); break;
-    case 2: per_cu = max_blocks_per_cu<2>(); break;
-    case 4: per_cu = max_blocks_per_cu<4>(); break;
-    case 5: per_cu = max_blocks_per_cu<5>(); break;
-    case 8: per_cu = max_blocks_per_cu<8>(); break;
-    case 10: per_cu = max_blocks_per_cu<10>(); break;
-    case 16: per_cu = max_blocks_per_cu<16>(); break;
-    case 24: per_cu = max_blocks_per_cu<24>(); break;
-    case 32: per_cu = max_blocks_per_cu<32>(); break;
-    default: per_cu = max_blocks_per_cu<64>(); break;
-  }
+  ListCapacities::dispatch(cap, [&](auto c) { per_cu = max_blocks_per_cu<decltype(c)::value>(); });
   const int64_t want = (a.ngroups + kWaveBlock / 64 - 1) / (kWaveBlock / 64);
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)prop.multiProcessorCount * per_cu));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)cu_count_ * per_cu));
 
   OWLMI_HIP(hipMemsetAsync(counters_, 0, 16 * sizeof(unsigned long long), s));
   if (sa.d_levels && !only_unfinished) OWLMI_HIP(hipMemsetAsync(sa.d_levels, 0xff, (size_t)n * sizeof(int32_t), s));
   OWLMI_HIP(hipEventRecord(ev_a_, s));
-  switch (cap) {
-    case 1: launch_wave<1>(a, blocks, s); break;
-    case 2: launch_wave<2>(a, blocks, s); break;
-    case 4: launch_wave<4>(a, blocks, s); break;
-    case 5: launch_wave<5>(a, blocks, s); break;
-    case 8: launch_wave<8>(a, blocks, s); break;
-    case 10: launch_wave<10>(a, blocks, s); break;
-    case 16: launch_wave<16>(a, blocks, s); break;
-    case 24: launch_wave<24>(a, blocks, s); break;
-    case 32: launch_wave<32>(a, blocks, s); break;
-    default: launch_wave<64>(a, blocks, s); break;
-  }
+  ListCapacities::dispatch(cap, [&](auto c) { launch_wave<decltype(c)::value>(a, blocks, s); });
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipEventRecord(ev_b_, s));
-  OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_, 10 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));
   float ms = 0;
   OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  if ((h_counters_[5] & 2ull) || wave_force_redo_) {  // (TKNN_WAVE_FORCE_REDO: tests take this path without a pathological tree)
+  const KernelStats st = KernelStats::from_words(h_counters_);  // (the wave kernel's words are not striped)
+  if ((st.flags & 2ull) || wave_force_redo_) {  // (TKNN_WAVE_FORCE_REDO: tests take this path without a pathological tree)
     // LDS node stack exhausted on some packet (pathologically deep tree): redo with the lane kernel
     if (only_unfinished) {
       continue_lane(sa, 0, info, s);  // done[] still names the stragglers; rows are simply rewritten
@@ -458,24 +435,8 @@ void Engine::solve_wave(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s,
     }
     return;
   }
-  if (h_counters_[5] & 1ull) throw RoundsExceeded{};
-  if (info) {
-    const int rounds = (int)h_counters_[1];
-    info->rounds = rounds;
-    float radius = sa.start_radius;
-    for (int t = 1; t < rounds; t++) radius *= 2;
-    info->final_radius = radius;
-    info->node_tests = (int64_t)h_counters_[2];
-    info->point_tests = (int64_t)h_counters_[3];
-    info->total_intersections = (int64_t)h_counters_[4];
-    info->total_active_rounds = (int64_t)h_counters_[6];
-    info->solve_ms = ms;
-    info->dominant_kernel_ms = ms;
-    info->dominant_kernel_launches = 1;
-    info->kernel_used = TKNN_KERNEL_WAVE;
-    info->list_capacity = cap;
-    info->unfinished = (int64_t)h_counters_[7];
-  }
+  if (st.flags & 1ull) throw RoundsExceeded{};
+  if (info) *info = solve_info(st, sa.start_radius, TKNN_KERNEL_WAVE, cap, ms);
 }
 
 }  // namespace owlmi
