@@ -185,11 +185,21 @@ TKNN_API int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32
 /* ---- exact kNN on request ---------------------------------------------------
  * tknnSolve reproduces the reference, whose rows are box-candidate kNN, not exact kNN: a query
  * that finished with box half-width r_q never saw points outside that box, although its k-th
- * distance d_k may exceed r_q (15-20 % of rows on uniform data).  tknnRepairExact rewrites exactly
- * those rows (d_k > r_q) with the true k nearest neighbours, same (dist, index) order, by one more
- * traversal with radius d_k.  Opt-in post-processing: it is never applied by tknnSolve, so parity
- * with the reference is unaffected.  Inputs: the rows and d_levels of a tknnSolveEx call and the
- * start radius it used; intersections / frameBuffer images are not touched. */
+ * distance d_k may exceed r_q (15-20 % of rows on uniform data); and candidates at bit-identical
+ * distances keep the reference's order (first round seen, then index), which at the k-th place can
+ * keep another point than (dist, index) order does, whatever d_k and r_q are.
+ * tknnRepairExact walks every row with d_levels[row] >= 0 once more, over the box of half-width
+ * d_k * 1.000001 + 2^-74, and rewrites it with the true k nearest neighbours of the engine's points
+ * (own and halo) in (dist, index) order -- index = id on trees built with ids; distances are the
+ * solve's fp32 formula.  That holds where squared offsets are subnormal or flush to zero as well
+ * (coordinates closer than about 1e-19): the 2^-74 covers their rounding.  Rows with level -1 and
+ * rows whose d_k is not finite (squared distances that overflow fp32) are left as they are.  The walk
+ * does not depend on r_q: start_radius is only checked (finite, > 0), and rows of a solve with
+ * per-query start radii are served the same way.  *repaired (may be NULL) receives the number of rows
+ * whose contents changed.
+ * Opt-in post-processing: it is never applied by tknnSolve, so parity with the reference is
+ * unaffected.  Inputs: the rows and d_levels of a tknnSolveEx call (k <= 64); intersections and
+ * frameBuffer images are not touched. */
 TKNN_API int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_levels,
                              int32_t *d_idx, float *d_dist, int64_t *repaired, void *stream);
 

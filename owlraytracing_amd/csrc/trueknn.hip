@@ -11,6 +11,7 @@
 #include "trueknn_engine.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -205,17 +206,19 @@ void launch_lane(const LaneRoundArgs &a, bool subtrees, hipStream_t s) {
 // ---- exact-kNN repair (opt-in, never part of tknnSolve) ----------------
 // The reference's rows are box-candidate kNN: a query that finished with radius r_q only ever saw
 // points inside its L-inf box, so when its k-th distance d_k exceeds r_q a closer point may sit
-// outside the box (15-20 % of rows on uniform data).  Every true neighbour has
-// Euclidean distance <= d_k, hence lies in the box of half-width d_k: one more traversal with
-// that radius, same (dist, index) order, gives the exact row.
+// outside the box (15-20 % of rows on uniform data).  Rows with d_k <= r_q are not exact
+// either: candidates at equal distances keep the replay's order (first round seen, then index), and
+// at the k-th place that order may keep another point than (dist, index) order does.  So every
+// finished row is walked again.  Every true neighbour has Euclidean distance <= d_k, hence lies in
+// the box of half-width d_k: one more traversal with that radius, (dist, index) order, gives the
+// exact row.  The walk needs no r_q, so rows solved with per-query start radii are served alike.
 struct RepairArgs {
   LbvhView bvh, halo;
   int k;
-  float start_radius;
-  const int32_t *levels;  // per caller row: level at which the query finished
+  const int32_t *levels;  // per caller row: level at which the query finished, -1: unfinished (row not written)
   int32_t *idx;           // n*k rows, read (d_k) and rewritten
   float *dist;
-  unsigned long long *counters;  // [0] rows repaired
+  unsigned long long *counters;  // [0] rows whose contents changed
 };
 
 template <int K>
@@ -224,13 +227,15 @@ __global__ void __launch_bounds__(kLaneBlock) repair_kernel(RepairArgs a) {
   if (t >= a.bvh.n) return;
   const LbvhPoint q = a.bvh.points[t];
   const int32_t row = a.bvh.prim_id[t];
-  const int32_t level = a.levels[row];
-  if (level < 0) return;
-  float rq = a.start_radius;
-  for (int i = 0; i < level; i++) rq *= 2;
-  const float dk = a.dist[(int64_t)row * a.k + a.k - 1];
-  if (!(dk > rq)) return;  // the ball of radius d_k is inside the box already searched
-  const float r = dk * 1.000001f;  // the rounded box test must not cut a point at distance d_k
+  if (a.levels[row] < 0) return;
+  const int64_t base = (int64_t)row * a.k;
+  const float dk = a.dist[base + a.k - 1];
+  if (!(dk <= FLT_MAX)) return;  // NaN query, or a row without k finite distances: no box to walk
+  // The rounded box test must not cut a point at computed distance <= d_k.  Its exact offset on every
+  // axis is at most sqrt(d_k^2 (1 + 4 ulp) + 3 * 2^-150): each square rounds by a relative half ulp, or
+  // by up to 2^-150 where it is subnormal.  d_k * 1.000001 covers the first term, + 2^-74 the second
+  // (sqrt(3) * 2^-75 < 2^-74), so that rows of points closer than 1e-19 stay exact too.
+  const float r = dk * 1.000001f + 0x1p-74f;
   KList<K> list;
   list.clear();
   for (int tree = 0; tree < 2; tree++) {
@@ -252,14 +257,19 @@ __global__ void __launch_bounds__(kLaneBlock) repair_kernel(RepairArgs a) {
       }
     }
   }
-  const int64_t base = (int64_t)row * a.k;
+  bool changed = false;
 #pragma unroll
   for (int j = 0; j < K; j++)
     if (j < a.k) {
-      a.idx[base + j] = knn_key_prim(list.key[j]);
-      a.dist[base + j] = knn_key_dist(list.key[j]);
+      const int32_t i = knn_key_prim(list.key[j]);
+      const float d = knn_key_dist(list.key[j]);
+      if (i != a.idx[base + j] || __float_as_uint(d) != __float_as_uint(a.dist[base + j])) {
+        a.idx[base + j] = i;
+        a.dist[base + j] = d;
+        changed = true;
+      }
     }
-  atomicAdd(&a.counters[0], 1ull);
+  if (changed) atomicAdd(&a.counters[0], 1ull);
 }
 
 template <int K>
@@ -545,13 +555,11 @@ void Engine::lane_rounds(const SolveArgs &sa, int first_level, bool fresh, tknnS
   }
 }
 
-int64_t Engine::repair_exact(int k, float start_radius, const int32_t *d_levels, int32_t *d_idx, float *d_dist,
-                             hipStream_t s) {
+int64_t Engine::repair_exact(int k, const int32_t *d_levels, int32_t *d_idx, float *d_dist, hipStream_t s) {
   RepairArgs a;
   a.bvh = bvh_.view();
   a.halo = halo_view();
   a.k = k;
-  a.start_radius = start_radius;
   a.levels = d_levels;
   a.idx = d_idx;
   a.dist = d_dist;
@@ -842,8 +850,8 @@ int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_le
     if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRepairExact: call tknnBuild first"};
     if (k <= 0 || k > TKNN_MAX_K_REGISTERS) throw owlmi::ArgError{TKNN_E_ARG, "tknnRepairExact: k out of range (1 .. 64: the repair pass keeps its lists in registers)"};
     if (!(start_radius > 0.f) || !std::isfinite(start_radius))
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnRepairExact: start_radius must be the one the rows were solved with"};
-    const int64_t n = e->impl.repair_exact(k, start_radius, d_levels, d_idx, d_dist, (hipStream_t)stream);
+      throw owlmi::ArgError{TKNN_E_ARG, "tknnRepairExact: start_radius must be finite and > 0"};
+    const int64_t n = e->impl.repair_exact(k, d_levels, d_idx, d_dist, (hipStream_t)stream);
     if (repaired) *repaired = n;
   });
 }

@@ -112,8 +112,8 @@ class Engine {
                    const int64_t *d_offsets, float *d_rows, hipStream_t s, const int64_t *d_caps = nullptr);
   double expected_box_population(float radius) const;
   void solve(const SolveArgs &sa, int kernel, tknnSolveInfo *info, hipStream_t s);
-  // rewrites the rows whose k-th distance exceeds their final box half-width with exact kNN; returns how many
-  int64_t repair_exact(int k, float start_radius, const int32_t *d_levels, int32_t *d_idx, float *d_dist, hipStream_t s);
+  // rewrites every finished row with the exact kNN (a walk of the box of half-width d_k); returns how many rows changed
+  int64_t repair_exact(int k, const int32_t *d_levels, int32_t *d_idx, float *d_dist, hipStream_t s);
   // dbscan.hip; with core_label (per row: the label the caller gave each core point, < 0 for others) only
   // the assignment runs: core points keep their label, others take the smallest among their core neighbours
   void dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, tknnDbscanInfo *info,

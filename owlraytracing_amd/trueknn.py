@@ -200,9 +200,24 @@ class TrueKNN:
         return out
 
     def repair_exact(self, result, k, start_radius):
-        """Turn the rows of ``solve(..., want_levels=True)`` into exact kNN in place (opt-in; the
-        reference's box-candidate rows are what ``solve`` returns).  Returns the number of rows rewritten."""
+        """Turn the finished rows of ``solve(..., want_levels=True)`` into exact kNN in (dist, index) order, in place (opt-in;
+        the reference's box-candidate rows are what ``solve`` returns).  Returns the number of rows whose contents changed.
+        ``result`` must hold contiguous ``idx`` (n,k) int32, ``dist`` (n,k) float32 and ``levels`` (n,) int32 on the
+        engine's device: the pass writes n*k entries through their pointers."""
         torch = self._torch
+        n, k = self.n, int(k)
+        if "levels" not in result or result["levels"] is None:
+            raise ValueError("repair_exact needs the levels of the solve (solve(..., want_levels=True))")
+        for name, shape, dtype in (("idx", (n, k), torch.int32), ("dist", (n, k), torch.float32), ("levels", (n,), torch.int32)):
+            t = result.get(name)
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("repair_exact: result[%r] must be a tensor" % name)
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError("repair_exact: result[%r] must be %s %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
+            if t.device != self.device:
+                raise ValueError("repair_exact: result[%r] is on %s, the engine on %s" % (name, t.device, self.device))
+            if not t.is_contiguous():
+                raise ValueError("repair_exact: result[%r] must be contiguous (it is written in place)" % name)
         n_fixed = ctypes.c_int64(0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.tknnRepairExact(

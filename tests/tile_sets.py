@@ -117,3 +117,11 @@ def tie_order_needs_level(idx, dist):
     id)) -- a row the tie pass must take the level key for."""
     plain = np.lexsort((idx, dist), axis=1)
     return (plain != np.arange(idx.shape[1])[None, :]).any(axis=1)
+
+
+def repair_boundary_case():
+    """(xyz, r0, k) of a row that is not exact kNN although d_k <= r_q and its own distances are all distinct: query 0 at
+    the origin sees (3, 4, 0) at level 0 (box 4.5), and (5, 0, 0) and (0, 0, 4.9) only at level 1 (box 9).  The replay
+    keeps [3, 2] (2 was a candidate first); (dist, index) order keeps [3, 1].  Three far-away points finish on their own."""
+    xyz = np.float32([[0, 0, 0], [5, 0, 0], [3, 4, 0], [0, 0, 4.9], [50, 50, 50], [51, 50, 50], [50, 52, 50]])
+    return xyz, 4.5, 2
