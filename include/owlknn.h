@@ -70,7 +70,8 @@ enum {
   TKNN_KERNEL_AUTO = 0,
   TKNN_KERNEL_LANE = 1,  /* one query per lane, stackless rope traversal, one launch per round    */
   TKNN_KERNEL_WAVE = 2,  /* one 64-query packet per wave, persistent, all rounds in one launch    */
-  TKNN_KERNEL_TEAM = 3   /* 16-lane teams, lanes = candidates of one query's leaf blocks           */
+  TKNN_KERNEL_TEAM = 3,  /* 16-lane teams, lanes = candidates of one query's leaf blocks           */
+  TKNN_KERNEL_QUERY = 4  /* reported by tknnQuery in info->kernel_used; not a selector tknnSolve takes */
 };
 
 typedef struct {
@@ -202,6 +203,45 @@ TKNN_API int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32
  * frameBuffer images are not touched. */
 TKNN_API int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_levels,
                              int32_t *d_idx, float *d_dist, int64_t *repaired, void *stream);
+
+/* ---- queries that are not in the set ------------------------------------------------------------------
+ * tknnSolve answers for the points of the built set P.  tknnQuery answers for m arbitrary points Q (any fp32
+ * triples, any order, inside the bounds of P or not) against the tree of P, built once.
+ * Row j is the row the reference's loop gives to q_j in the set P + {q_j}, q_j being the query there: at level L
+ * the radius is start_radius doubled L times in fp32; the candidates are the points p of P with
+ * fl(p - r) <= q_j <= fl(p + r) on every axis; the query finishes at the first level with at least k candidates;
+ * its row is the k best candidates of that level in the order (fp32 distance, level at which the candidate was
+ * first a candidate, index) -- index = id on trees built with ids.  There is no self to skip: a point of P that
+ * coincides with q_j is an ordinary neighbour at distance 0, so n >= k is enough.
+ *   d_levels[j]        that level (0-based), -1 if unfinished
+ *   d_intersections[j] candidates summed over the levels the query traced (the reference's counter for q_j in
+ *                      P + {q_j} also counts the query's own box once per level: that is left out)
+ *   exact != 0         every finished row is rewritten with the true k nearest points of P in (dist, index)
+ *                      order, as tknnRepairExact does for the points of the set (levels and intersections stay)
+ * Rows are addressed by the caller's index j whatever order the engine works in; d_queries is not referred to
+ * after the call returns; the tree and the state of tknnSolve are not modified.  info is filled as for a solve
+ * (kernel_used = TKNN_KERNEL_QUERY; dominant_kernel_ms = the traversal of the ordered queries, solve_ms - that
+ * - tie_ms = ordering them (plus the exact pass); tie_rows = rows redone for the order of bit-identical distances).
+ * Errors, in this order: NULL engine / options / d_queries with m > 0: TKNN_E_ARG; not built: TKNN_E_STATE;
+ * k < 1, k > n, radius not finite-positive, m < 0, allow_unfinished without d_levels: TKNN_E_ARG; k >
+ * TKNN_MAX_K_REGISTERS: TKNN_E_UNSUPPORTED; a halo tree is set: TKNN_E_UNSUPPORTED (queries over tiles are not
+ * served yet); max_rounds reached without allow_unfinished: TKNN_E_ROUNDS.  m = 0 succeeds with a zeroed info.
+ * A query with a NaN coordinate never finishes (and NaN points of P are nobody's candidates). */
+typedef struct {
+  const float *d_queries;   /* m packed fp32 triples (2-D data: z = 0) */
+  int64_t m;
+  int32_t k;                /* 1 .. TKNN_MAX_K_REGISTERS, and k <= n */
+  float start_radius;       /* finite, > 0 */
+  int32_t max_rounds;       /* as tknnSolve */
+  int32_t allow_unfinished; /* as tknnSolveEx: level -1, row not written, info->unfinished counts */
+  int32_t exact;            /* 0: the reference's semantics above.  1: rows rewritten as exact kNN */
+  int32_t reserved_;
+  int32_t *d_idx;           /* m*k, may be NULL */
+  float *d_dist;            /* m*k, may be NULL */
+  int64_t *d_intersections; /* m, may be NULL */
+  int32_t *d_levels;        /* m, may be NULL (required with allow_unfinished) */
+} tknnQueryOptions;
+TKNN_API int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info, void *stream);
 
 /* ---- RT-DBSCAN over the same tree -------------------------------------
  * The reference tree holds no RT-DBSCAN source (README.md:8-9 mentions the method only), so the

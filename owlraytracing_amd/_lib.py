@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OWL_MI355X_LIB") or os.path.join(_HERE, "libowl_mi355x.so")  # override: diagnostic builds
 
 KERNEL_AUTO, KERNEL_LANE, KERNEL_WAVE, KERNEL_TEAM = 0, 1, 2, 3
+KERNEL_QUERY = 4  # info["kernel_used"] of tknnQuery; not a selector for solve
 MAX_K = 1024  # include/owlknn.h TKNN_MAX_K (k <= 64: register lists; above: the team walk with the lists in memory)
 
 
@@ -58,6 +59,23 @@ class SolveOptions(ctypes.Structure):
         ("d_fb", ctypes.c_void_p),
         ("d_levels", ctypes.c_void_p),
         ("d_start_radii", ctypes.c_void_p),
+    ]
+
+
+class QueryOptions(ctypes.Structure):
+    _fields_ = [
+        ("d_queries", ctypes.c_void_p),
+        ("m", ctypes.c_int64),
+        ("k", ctypes.c_int32),
+        ("start_radius", ctypes.c_float),
+        ("max_rounds", ctypes.c_int32),
+        ("allow_unfinished", ctypes.c_int32),
+        ("exact", ctypes.c_int32),
+        ("reserved_", ctypes.c_int32),
+        ("d_idx", ctypes.c_void_p),
+        ("d_dist", ctypes.c_void_p),
+        ("d_intersections", ctypes.c_void_p),
+        ("d_levels", ctypes.c_void_p),
     ]
 
 
@@ -110,6 +128,7 @@ SIGNATURES = {
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tknnRepairExact": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]),
+    "tknnQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(QueryOptions), ctypes.POINTER(SolveInfo), ctypes.c_void_p]),
     "tknnDbscan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnDbscanAssign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,

@@ -856,6 +856,43 @@ int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_le
   });
 }
 
+int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info, void *stream) {
+  if (!e || !options || (options->m > 0 && !options->d_queries)) {
+    g_last_error = "tknnQuery: engine, options and (for m > 0) the queries are required";
+    return TKNN_E_ARG;
+  }
+  return guarded_on(e, [&] {
+    const tknnQueryOptions &o = *options;
+    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnQuery: call tknnBuild first"};
+    if (o.k < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: k must be positive"};
+    if ((int64_t)o.k > e->impl.size()) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: need n >= k (no query can finish otherwise)"};
+    if (!(o.start_radius > 0.f) || !std::isfinite(o.start_radius))
+      throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: start_radius must be finite and > 0"};
+    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: need 0 <= m < 2^31-1"};
+    if (o.allow_unfinished && !o.d_levels)
+      throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: allow_unfinished needs d_levels (they say which rows were written)"};
+    if (o.k > TKNN_MAX_K_REGISTERS)
+      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnQuery: k out of range (1 .. 64: the query kernels keep their lists in registers)"};
+    if (e->impl.has_halo())
+      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnQuery: a halo tree is set (queries over tiles are not served yet)"};
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (o.m == 0) return;
+    owlmi::QueryArgs qa;
+    qa.d_queries = o.d_queries;
+    qa.m = o.m;
+    qa.k = o.k;
+    qa.start_radius = o.start_radius;
+    qa.max_rounds = o.max_rounds > 0 ? std::min(o.max_rounds, 127) : 64;  // as tknnSolveEx
+    qa.allow_unfinished = o.allow_unfinished != 0;
+    qa.exact = o.exact != 0;
+    qa.d_idx = o.d_idx;
+    qa.d_dist = o.d_dist;
+    qa.d_isect = o.d_intersections;
+    qa.d_levels = o.d_levels;
+    e->impl.query(qa, info, (hipStream_t)stream);
+  });
+}
+
 int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
                tknnDbscanInfo *info, void *stream) {
   if (!e || !d_labels) {

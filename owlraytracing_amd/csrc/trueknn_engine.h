@@ -32,6 +32,21 @@ struct SolveArgs {
   int phase = 0;  // tknnSolveOptions.phase: 0 every query, 1 interior queries in the own tree only, 2 boundary queries
 };
 
+// tknnQueryOptions as the engine takes it (max_rounds already resolved)
+struct QueryArgs {
+  const float *d_queries = nullptr;
+  int64_t m = 0;
+  int k = 0;
+  float start_radius = 0;
+  int max_rounds = 64;
+  bool allow_unfinished = false;
+  bool exact = false;
+  int32_t *d_idx = nullptr;
+  float *d_dist = nullptr;
+  int64_t *d_isect = nullptr;
+  int32_t *d_levels = nullptr;
+};
+
 template <int... C>
 struct CapacityTable {
   // smallest capacity >= k, or -1
@@ -123,6 +138,9 @@ class Engine {
   void db_read_stats(hipStream_t s);
   void dbscan_auto(float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, hipStream_t s);
+  // trueknn_query.hip: TrueKNN rows for m points that are not in the tree (tknnQuery); per-slot solve state is not touched
+  void query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s);
+  bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }
   int64_t size() const { return bvh_.size(); }

@@ -1,0 +1,602 @@
+// trueknn_query.hip -- TrueKNN for query points that are NOT in the tree (tknnQuery, include/owlknn.h).
+//
+// Row j is the row the reference's loop (samples/s01-trueknn/hostCode.cpp:285-340 around deviceCode.cu:62-153)
+// gives to q_j in the set P + {q_j}: radius levels from start_radius, doubled in fp32; the candidates of a level
+// are the points of P whose box holds q_j; the first level with >= k candidates finishes the query; its row is
+// the k best in (distance, level at which first a candidate, index) order.  There is no self to skip.
+//
+// The self-solve's packet kernel lives on queries being tree slots (64 consecutive sorted slots share leaf
+// blocks).  External queries have no slot, so:
+//   1. query_code_kernel + a radix sort: the queries in the Morton order of the tree's own quantisation, so that
+//      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
+//   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
+//      shape of team_walk_kernel (trueknn_team.hip) without anything that is per slot;
+//   3. query_lane_kernel: one query per lane, rope traversal, keys that carry the level -- for the few queries
+//      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
+//   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).
+#include "knn_thresholds.h"  // knn_gate_from_worst
+#include "team_lanes.h"
+#include "trueknn_engine.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+namespace owlmi {
+
+namespace {
+
+constexpr int kQueryBlock = 64;       // one wave per workgroup, four teams
+constexpr int kQueryStack = 384;      // stack entries per team, as kWalkStack: up to 63 siblings wait on each of <= 6 levels
+constexpr int kQueryBlocksPerCu = 16;  // 7.3 KB of LDS each: far inside what a CU holds
+constexpr int kQueryMergeAt = 12;     // buffered candidates of some team that trigger a merge (TKNN_MERGE_AT)
+constexpr int kLaneBlock = 256;
+constexpr int kCountedSubtree = 32;   // smallest subtree the lane kernel tries to count instead of walking
+constexpr int kCodeBits = 30;         // ten bits per axis order 10 M queries well enough, and sort in half the passes
+
+// words of the call's own counters (in the workspace, zeroed per pass)
+enum { kWsCursor = 0, kWsRedo = 1, kWsTies = 2, kWsFailed = 3, kWsWords = 8 };
+
+struct QueryKernelArgs {
+  LbvhView bvh;
+  LbvhWideView wide;
+  const float *queries;   // m packed triples, caller order
+  const uint32_t *order;  // m: the query processed at sorted position i
+  int32_t m;
+  float start_radius;
+  int k;
+  int max_rounds;
+  int exact;              // 1: one level of half-width d_k per finished row, (dist, index) order, no statistics
+  int force_redo;         // TKNN_QUERY_FORCE_FALLBACK (tests): the walk leaves every query to the lane kernel
+  int32_t *out_idx;       // m*k (may be null)
+  float *out_dist;        // m*k (may be null; never with exact)
+  int64_t *out_isect;     // m (may be null)
+  int32_t *levels;        // m, preset to -1 (never null: the engine's own if the caller has none)
+  int32_t *redo;          // m: queries left to the lane kernel
+  unsigned long long *ws;     // kWsWords counters
+  unsigned long long *stats;  // the engine's statistics stripes (kStatBase)
+};
+
+struct WideLevel {  // per pyramid level, in LDS: lanes of different teams are at different levels
+  const LbvhBox *boxes;
+  int32_t count;
+  int32_t pad_;
+};
+
+// ---- 1. the order ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t spread10(uint32_t v) {
+  v &= 0x3ffu;
+  v = (v | (v << 16)) & 0x030000ffu;
+  v = (v | (v << 8)) & 0x0300f00fu;
+  v = (v | (v << 4)) & 0x030c30c3u;
+  v = (v | (v << 2)) & 0x09249249u;
+  return v;
+}
+
+// The tree's quantisation (cubic cells over the scene box, one scale for all axes: lbvh.hip) at ten bits per
+// axis; queries outside the box are clamped to its faces, queries with a NaN coordinate sort last.
+__global__ void __launch_bounds__(kLaneBlock) query_code_kernel(const float *__restrict__ queries, int32_t m, const float *__restrict__ scene,
+                                                               uint32_t *__restrict__ codes, uint32_t *__restrict__ order) {
+  const int32_t i = blockIdx.x * kLaneBlock + threadIdx.x;
+  if (i >= m) return;
+  const float c[3] = {queries[3 * (int64_t)i], queries[3 * (int64_t)i + 1], queries[3 * (int64_t)i + 2]};
+  const float ext = fmaxf(fmaxf(scene[3] - scene[0], scene[4] - scene[1]), scene[5] - scene[2]);
+  const float scale = (ext > 0.f && ext < INFINITY) ? 1023.0f / ext : 0.f;
+  uint32_t cell[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    float t = (c[a] - scene[a]) * scale;
+    t = fminf(fmaxf(t, 0.f), 1023.0f);  // NaN -> 0 via fmaxf
+    cell[a] = (uint32_t)t;
+  }
+  uint32_t code = (spread10(cell[0]) << 2) | (spread10(cell[1]) << 1) | spread10(cell[2]);
+  if (c[0] != c[0] || c[1] != c[1] || c[2] != c[2]) code = 1u << kCodeBits;
+  codes[i] = code;
+  order[i] = (uint32_t)i;
+}
+
+// ---- 2. the walk -------------------------------------------------------------------------------------------
+// A team walks the 64-ary pyramid for one query: its 16 lanes test 16 child boxes at a time and push the
+// survivors on the team's LDS stack; a leaf block is 16 points = 16 lanes.  A child box inside the part of the
+// query's box where the candidate test is certain, and beyond the list's gate, is counted instead of walked.
+// Candidates wait in the team's LDS buffer and are merged into the sorted register list sixteen at a time
+// (t_merge_rows).  Teams of a wave loop in lock step, so there is no __syncthreads, only t_wave_sync.
+template <int NREG>
+__global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_eu(4))) query_walk_kernel(QueryKernelArgs a) {
+  __shared__ int32_t stack_mem[4 * kQueryStack];
+  __shared__ WideLevel levels[LBVH_WIDE_LEVELS];
+  __shared__ unsigned long long cand_mem[4 * kCandCapacity];
+  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
+  int32_t *stack = stack_mem + team * kQueryStack;
+  if (lane < LBVH_WIDE_LEVELS) {
+    levels[lane].boxes = a.wide.level[lane];
+    levels[lane].count = a.wide.count[lane];
+  }
+  t_wave_sync();
+  const LbvhWideView &wv = a.wide;
+  const int32_t clean_end = a.bvh.n - (a.bvh.nan_count ? *a.bvh.nan_count : 0);  // NaN points sort last
+  unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
+  unsigned int unfinished = 0, failed = 0, tied_rows = 0;
+  int max_level = 0;
+  for (;;) {
+    int got = 0;
+    if (lane == 0) got = (int)atomicAdd(&a.ws[kWsCursor], 4ull);
+    const int base = __builtin_amdgcn_readfirstlane(got);
+    if (base >= a.m) break;
+    const bool has_q = base + team < a.m;
+    const int32_t qi = has_q ? (int32_t)a.order[base + team] : 0;
+    LbvhPoint q;
+    q.x = a.queries[3 * (int64_t)qi], q.y = a.queries[3 * (int64_t)qi + 1], q.z = a.queries[3 * (int64_t)qi + 2];
+    q.id = -1;  // ids of the tree's points are non-negative: nothing is "self"
+    int level = 0;
+    int64_t isect = 0;
+    float r = a.start_radius;
+    bool active = has_q;
+    if (a.exact) {
+      // every neighbour at distance <= d_k lies in the box of half-width d_k (the bound: repair_kernel, trueknn.hip)
+      active = has_q && a.levels[qi] >= 0;
+      const float dk = active ? a.out_dist[(int64_t)qi * a.k + a.k - 1] : 0.f;
+      active = active && dk <= FLT_MAX;
+      r = dk * 1.000001f + 0x1p-74f;
+    }
+    while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
+      const float mg = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + 2.0f * r) * 4.76837158203125e-07f;  // 2^-21
+      const float in_below = r - mg, in_upto = r + mg;
+      // boxes that can hold a candidate meet [q - r - 2M, q + r + 2M]; every point of a box inside
+      // [q - r + 2M, q + r - 2M] certainly is one
+      const float rl = r + 2.0f * mg, rs = r - 2.0f * mg;
+      uint32_t part = 0;  // my lane's share of the candidate count of this level
+      uint32_t bd[NREG], bi[NREG];  // register j of lane t holds list entry 16 j + t
+#pragma unroll
+      for (int j = 0; j < NREG; j++) {
+        bd[j] = 0x7f7fffffu;  // KNN_EMPTY_KEY = {FLT_MAX, 0}
+        bi[j] = 0u;
+      }
+      float tau2 = INFINITY;
+      bool overflow = false;
+      const bool full = a.k == 16 * NREG;  // no spare list entry to see a tie with the row's last in
+      uint32_t left_out = 0xffffffffu;
+      auto kth_dist = [&]() -> float {
+        uint32_t reg = bd[0];
+#pragma unroll
+        for (int j = 1; j < NREG; j++) reg = ((a.k - 1) >> 4) == j ? bd[j] : reg;
+        return __uint_as_float(t_lane_read(reg, (team << 4) + ((a.k - 1) & 15)));
+      };
+      unsigned long long *my_cand = cand_mem + team * kCandCapacity;
+      uint32_t fill_n = 0;
+      auto merge_buffer = [&]() {
+        t_wave_sync();
+        t_merge_rows<NREG>(bd, bi, left_out, full, my_cand, fill_n, tl);
+        t_wave_sync();
+        fill_n = 0;
+        tau2 = knn_gate_from_worst(kth_dist());
+      };
+      int sp = 0;
+      if (active && wv.levels > 0) {
+        if (tl == 0) stack[0] = (wv.levels << 26) | 0;  // virtual root above the top level
+        sp = 1;
+      }
+      t_wave_sync();
+      while (__ballot(sp > 0) != 0ull) {
+        const bool work = sp > 0;
+        const int32_t e = work ? stack[sp - 1] : (1 << 26);
+        if (work) sp--;
+        const int lvl = (e >> 26) - 1;  // level of the children
+        const int32_t first_child = (e & 0x3ffffff) * 64;
+        const WideLevel wl = levels[lvl];
+        // the virtual root has the top level's few boxes as its children
+        const int32_t nchild = lvl == wv.levels - 1 ? (first_child == 0 ? wl.count : 0) : wl.count;
+        LbvhBox bx4[4];  // the node's 64 child boxes, all four loads in flight at once
+#pragma unroll
+        for (int chunk = 0; chunk < 4; chunk++) {
+          const int32_t c = first_child + 16 * chunk + tl;
+          bx4[chunk] = LbvhBox{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+          if (work && c < nchild) bx4[chunk] = wl.boxes[c];
+        }
+#pragma unroll
+        for (int chunk = 0; chunk < 4; chunk++) {
+          const int32_t c = first_child + 16 * chunk + tl;
+          const bool valid = work && c < nchild;
+          const LbvhBox bx = bx4[chunk];
+          const bool ov = valid & (bx.lo[0] <= q.x + rl) & (bx.hi[0] >= q.x - rl) & (bx.lo[1] <= q.y + rl) &
+                          (bx.hi[1] >= q.y - rl) & (bx.lo[2] <= q.z + rl) & (bx.hi[2] >= q.z - rl);
+          node_tests += valid ? 1u : 0u;
+          bool counted = false;
+          if (ov) {
+            const bool inside = (bx.lo[0] >= q.x - rs) & (bx.hi[0] <= q.x + rs) & (bx.lo[1] >= q.y - rs) &
+                                (bx.hi[1] <= q.y + rs) & (bx.lo[2] >= q.z - rs) & (bx.hi[2] <= q.z + rs);
+            if (inside) {
+              const float gx = fmaxf(fmaxf(bx.lo[0] - q.x, q.x - bx.hi[0]), 0.f), gy = fmaxf(fmaxf(bx.lo[1] - q.y, q.y - bx.hi[1]), 0.f),
+                          gz = fmaxf(fmaxf(bx.lo[2] - q.z, q.z - bx.hi[2]), 0.f);
+              const float m2 = (gx * gx + gy * gy) + gz * gz;  // <= every point's squared distance, up to rounding
+              const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
+              const int64_t first = (int64_t)c * span;
+              if (m2 * 0.999995f > tau2 && first + span <= (int64_t)clean_end) {
+                part += (uint32_t)span;
+                counted = true;
+              }
+            }
+          }
+          const bool keep = ov && !counted;
+          const uint32_t keep_mine = (uint32_t)(__ballot(keep) >> (team * 16)) & 0xffffu;
+          if (lvl > 0) {
+            if (sp + __popc(keep_mine) > kQueryStack) {
+              overflow = true;
+            } else {
+              if (keep) stack[sp + __popc(keep_mine & ((1u << tl) - 1u))] = (lvl << 26) | c;
+              sp += __popc(keep_mine);
+            }
+          } else {
+            // children are leaf blocks: lanes become the 16 points of one block at a time
+            uint32_t todo = keep_mine;
+            while (__ballot(todo != 0u) != 0ull) {
+              const bool has_b = todo != 0u;
+              const int32_t b = first_child + 16 * chunk + (has_b ? __ffs((int)todo) - 1 : 0);
+              todo &= todo - 1u;
+              LbvhPoint p = {__uint_as_float(0x7fc00000u), 0.f, 0.f, -1};
+              if (has_b) p = a.bvh.points[(int64_t)b * LBVH_BLOCK + tl];  // (padded with NaN sentinels to whole blocks: lbvh.hip)
+              point_tests += has_b ? 1u : 0u;
+              const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+              const float t = has_b ? fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz)) : __uint_as_float(0x7fc00000u);
+              unsigned long long in_m = __ballot(t <= in_below);
+              const unsigned long long maybe_m = __ballot(t <= in_upto) & ~in_m;
+              if (maybe_m) in_m |= maybe_m & __ballot(knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z));
+              part = t_count(part, in_m);
+              const float d2 = t_dist2(dx, dy, dz);
+              const unsigned long long pm = in_m & __ballot(d2 <= tau2);
+              if (pm) {
+                const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
+                if ((mine16 >> tl) & 1u) my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)p.id;
+                fill_n += __popc(mine16);
+                if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
+              }
+            }
+            // a tighter gate for what comes next as soon as a handful of candidates wait
+            if (__ballot(fill_n >= (uint32_t)kQueryMergeAt) != 0ull) merge_buffer();
+          }
+        }
+        t_wave_sync();
+      }
+      if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
+      if (full) {
+        // the smallest key left out by any merge, where the tie test below looks for it: lane 15
+        uint32_t v = left_out;
+        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128 /*row_ror:8*/, 0xf, 0xf, false));
+        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124 /*row_ror:4*/, 0xf, 0xf, false));
+        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x122 /*row_ror:2*/, 0xf, 0xf, false));
+        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x121 /*row_ror:1*/, 0xf, 0xf, false));
+        left_out = v;
+      }
+      // ---- the level's outcome, per team ----
+      const uint32_t cnt = t_team_sum(part);  // no self: every candidate is a neighbour
+      const bool fin = active && !overflow && (a.exact || cnt >= (uint32_t)a.k);
+      // Does the row depend on how bit-identical distances are ordered?  The list holds (dist, index) order; the
+      // reference's is (dist, first level, index).  At level 0 they are the same; later, only where two tied
+      // candidates can have become candidates at different levels (tie_may_straddle).
+      bool tie = false;
+      if (!a.exact && level > 0) {
+        const float qmax = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z));
+#pragma unroll
+        for (int reg = 0; reg < NREG; reg++) {
+          uint32_t before = t_team_shr1(bd[reg]);
+          if (reg > 0) before |= t_dpp<0x121>(bd[reg - 1]) & (tl == 0 ? 0xffffffffu : 0u);
+          bool t = ((reg > 0) | (tl >= 1)) & (16 * reg + tl <= a.k) & (bd[reg] == before);
+          t |= reg == NREG - 1 && full && tl == 15 && left_out == bd[reg];
+          t = t && fin && tie_may_straddle(__uint_as_float(bd[reg]), a.start_radius, r, qmax, 1.73206f);
+          tie |= t;
+        }
+      }
+      const bool tied = ((uint32_t)(__ballot(tie) >> (team * 16)) & 0xffffu) != 0u;
+      if (active && (overflow || a.force_redo || (fin && tied))) {
+        // left to the lane kernel, which starts the query from level 0: nothing of it is written or counted here
+        if (tl == 0) {
+          a.redo[atomicAdd(&a.ws[kWsRedo], 1ull)] = qi;
+          if (overflow || a.force_redo)
+            failed++;
+          else
+            tied_rows++;
+        }
+        active = false;
+      } else if (active) {
+        isect += cnt;
+        if (fin) {
+#pragma unroll
+          for (int reg = 0; reg < NREG; reg++) {
+            const int j = tl + 16 * reg;
+            if (j >= a.k) continue;
+            const int64_t o = (int64_t)qi * a.k + j;
+            if (a.out_idx) a.out_idx[o] = knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]);
+            if (a.out_dist) a.out_dist[o] = __uint_as_float(bd[reg]);
+          }
+          if (tl == 0 && !a.exact) {
+            if (a.out_isect) a.out_isect[qi] = isect;
+            a.levels[qi] = level;
+            isect_sum += (unsigned long long)isect;
+            levels_sum += (unsigned long long)(level + 1);
+          }
+          if (!a.exact) max_level = max(max_level, level + 1);
+          active = false;
+        } else {
+          level++;
+          r = r * 2.0f;  // hostCode.cpp:321
+          if (level >= a.max_rounds) {  // out of rounds: the caller decides (allow_unfinished)
+            if (tl == 0) {
+              unfinished++;
+              levels_sum += (unsigned long long)level;
+            }
+            max_level = max(max_level, level);
+            active = false;
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long isum = t_wave_sum(isect_sum), lsum = t_wave_sum(levels_sum), nt = t_wave_sum(node_tests),
+                           pt = t_wave_sum(point_tests), usum = t_wave_sum((unsigned long long)unfinished),
+                           fsum = t_wave_sum((unsigned long long)failed), tsum = t_wave_sum((unsigned long long)tied_rows);
+  const int ml = (int)t_wave_max((float)max_level);
+  if (lane == 0) {
+    if (fsum) atomicAdd(&a.ws[kWsFailed], fsum);
+    if (tsum) atomicAdd(&a.ws[kWsTies], tsum);
+    if (!a.exact) {
+      unsigned long long *st = a.stats + (blockIdx.x & (kStatStripes - 1)) * kStatStride;
+      atomicMax(&st[1], (unsigned long long)ml);
+      atomicAdd(&st[2], nt);
+      atomicAdd(&st[3], pt);
+      atomicAdd(&st[4], isum);
+      atomicAdd(&st[6], lsum);
+      if (usum) atomicAdd(&st[7], usum);
+    }
+  }
+}
+
+// ---- 3. one query per lane -----------------------------------------------------------------------------------
+// A sorted list of (distance, level at which first a candidate, index) keys in registers: the reference's
+// order (its lists persist over rounds, deviceCode.cu:77-85, so of two candidates at the same distance the one
+// listed in an earlier round stays in front).
+template <int K>
+struct LevelList {
+  uint32_t d[K];   // fp32 bits of the distance (non-negative: bits order like values)
+  uint64_t li[K];  // level << 32 | index
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      d[j] = 0x7f7fffffu;  // KNN_EMPTY_KEY: a candidate at distance FLT_MAX never enters
+      li[j] = 0ull;
+    }
+  }
+  __device__ __forceinline__ bool less(uint32_t cd, uint64_t cli, int j) const { return cd < d[j] || (cd == d[j] && cli < li[j]); }
+  __device__ __forceinline__ void insert(uint32_t cd, uint64_t cli) {
+    if (!less(cd, cli, K - 1)) return;
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) {
+      const bool shift = less(cd, cli, j - 1), here = less(cd, cli, j);
+      d[j] = shift ? d[j - 1] : (here ? cd : d[j]);
+      li[j] = shift ? li[j - 1] : (here ? cli : li[j]);
+    }
+    const bool first = less(cd, cli, 0);
+    d[0] = first ? cd : d[0];
+    li[0] = first ? cli : li[0];
+  }
+  __device__ __forceinline__ int32_t prim(int j) const { return d[j] == 0x7f7fffffu && li[j] == 0ull ? -1 : (int32_t)(uint32_t)li[j]; }
+};
+
+// The queries of a list (redo, its length on the device), each from level 0, all levels in the lane's own loop.
+template <int K>
+__global__ void __launch_bounds__(kLaneBlock) query_lane_kernel(QueryKernelArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * kLaneBlock + threadIdx.x;
+  const bool has_q = t < (int64_t)a.ws[kWsRedo];
+  const int32_t qi = has_q ? a.redo[t] : 0;
+  const LbvhView &tv = a.bvh;
+  const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
+  const float qx = a.queries[3 * (int64_t)qi], qy = a.queries[3 * (int64_t)qi + 1], qz = a.queries[3 * (int64_t)qi + 2];
+  float r = a.start_radius;
+  bool active = has_q;
+  if (a.exact) {
+    active = has_q && a.levels[qi] >= 0;
+    const float dk = active ? a.out_dist[(int64_t)qi * a.k + a.k - 1] : 0.f;
+    active = active && dk <= FLT_MAX;
+    r = dk * 1.000001f + 0x1p-74f;
+  }
+  unsigned long long node_tests = 0, point_tests = 0, isect_sum = 0, levels_sum = 0, unfinished = 0;
+  int max_level = 0, level = 0;
+  int64_t isect = 0;
+  LevelList<K> list;
+  while (active) {
+    list.clear();
+    int32_t cnt = 0;
+    int32_t ref = tv.root;
+    while (ref != LBVH_END) {
+      if (ref >= 0) {
+        const LbvhNode nd = tv.nodes[ref];
+        node_tests++;
+        // conservative: rounding is monotone, so a point of the node passes only if the node's corners do (lane_round_kernel)
+        const bool hit = (nd.lo[0] - r <= qx) & (qx <= nd.hi[0] + r) & (nd.lo[1] - r <= qy) & (qy <= nd.hi[1] + r) &
+                         (nd.lo[2] - r <= qz) & (qz <= nd.hi[2] + r);
+        // The same monotonicity the other way round: if even the largest centre passes the lower test and the smallest the
+        // upper one, every point of the node is a candidate; if the node also lies beyond the list's gate none of them can
+        // enter the list or tie with its last entry, and the subtree is counted, not walked (lane_round_kernel, trueknn.hip)
+        const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
+        if (hit && last - first + 1 >= kCountedSubtree && (nd.hi[0] - r <= qx) & (qx <= nd.lo[0] + r) & (nd.hi[1] - r <= qy) &
+                                                           (qy <= nd.lo[1] + r) & (nd.hi[2] - r <= qz) & (qz <= nd.lo[2] + r)) {
+          const float gx = fmaxf(fmaxf(nd.lo[0] - qx, qx - nd.hi[0]), 0.f), gy = fmaxf(fmaxf(nd.lo[1] - qy, qy - nd.hi[1]), 0.f),
+                      gz = fmaxf(fmaxf(nd.lo[2] - qz, qz - nd.hi[2]), 0.f);
+          const float m2 = (gx * gx + gy * gy) + gz * gz;  // <= every point's squared distance, up to rounding
+          if (m2 * 0.999995f > knn_gate_from_worst(__uint_as_float(list.d[K - 1])) && last < clean_end) {
+            cnt += last - first + 1;
+            ref = tv.rope_node[ref];
+            continue;
+          }
+        }
+        ref = hit ? lbvh_left_ref(ref, nd) : tv.rope_node[ref];
+      } else {
+        const int32_t slot = ~ref;
+        const LbvhPoint p = tv.points[slot];
+        point_tests++;
+        if (knn_in_box(p.x, p.y, p.z, r, qx, qy, qz)) {
+          cnt++;
+          // the first level whose box held the query (not beyond this one: its test has just passed)
+          uint32_t first = 0;
+          if (!a.exact)
+            for (float rr = a.start_radius; (int)first < level && !knn_in_box(p.x, p.y, p.z, rr, qx, qy, qz); rr = rr * 2.0f) first++;
+          const float d = knn_sqrt(knn_dist2(p.x, p.y, p.z, qx, qy, qz));
+          list.insert(__float_as_uint(d), ((uint64_t)first << 32) | (uint32_t)p.id);
+        }
+        ref = tv.rope_leaf[slot];
+      }
+    }
+    isect += cnt;
+    if (a.exact || cnt >= a.k) {
+      const int64_t base = (int64_t)qi * a.k;
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (j < a.k) {
+          if (a.out_idx) a.out_idx[base + j] = list.prim(j);
+          if (a.out_dist) a.out_dist[base + j] = __uint_as_float(list.d[j]);
+        }
+      if (!a.exact) {
+        if (a.out_isect) a.out_isect[qi] = isect;
+        a.levels[qi] = level;
+        isect_sum = (unsigned long long)isect;
+        levels_sum = (unsigned long long)(level + 1);
+        max_level = level + 1;
+      }
+      active = false;
+    } else {
+      level++;
+      r = r * 2.0f;
+      if (level >= a.max_rounds) {
+        unfinished = 1;
+        levels_sum = (unsigned long long)level;
+        max_level = level;
+        active = false;
+      }
+    }
+  }
+  if (a.exact) return;
+  // (all lanes of the wave are here)
+  const unsigned long long nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests), isum = t_wave_sum(isect_sum),
+                           lsum = t_wave_sum(levels_sum), usum = t_wave_sum(unfinished);
+  const int ml = (int)t_wave_max((float)max_level);
+  if ((threadIdx.x & 63) == 0 && nt) {
+    unsigned long long *st = a.stats + (blockIdx.x & (kStatStripes - 1)) * kStatStride;
+    atomicMax(&st[1], (unsigned long long)ml);
+    atomicAdd(&st[2], nt);
+    atomicAdd(&st[3], pt);
+    atomicAdd(&st[4], isum);
+    atomicAdd(&st[6], lsum);
+    if (usum) atomicAdd(&st[7], usum);
+  }
+}
+
+using WalkEntry = void (*)(QueryKernelArgs);
+const WalkEntry kWalks[4] = {query_walk_kernel<1>, query_walk_kernel<2>, query_walk_kernel<3>, query_walk_kernel<4>};
+inline int query_nreg(int k) { return k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 48 ? 3 : 4)); }
+
+}  // namespace
+
+// One pass of both kernels over the sorted queries: the walk, then the lane kernel for what the walk left.
+// Returns {queries left to the lane kernel for their stack, ... for their ties}; the events bracket the two launches.
+static void query_pass(QueryKernelArgs &a, int cu_count, unsigned long long *h_words, hipEvent_t after_walk, hipEvent_t after_lane,
+                       unsigned long long &failed, unsigned long long &tied, hipStream_t s) {
+  OWLMI_HIP(hipMemsetAsync(a.ws, 0, kWsWords * sizeof(unsigned long long), s));
+  const int blocks = (int)std::min<int64_t>(((int64_t)a.m + 3) / 4, (int64_t)cu_count * kQueryBlocksPerCu);
+  void *kargs[] = {(void *)&a};
+  OWLMI_HIP(hipLaunchKernel((const void *)kWalks[query_nreg(a.k) - 1], dim3(blocks), dim3(kQueryBlock), kargs, 0, s));
+  OWLMI_HIP(hipGetLastError());
+  OWLMI_HIP(hipEventRecord(after_walk, s));
+  OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kWsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  OWLMI_HIP(hipStreamSynchronize(s));
+  const unsigned long long redo = h_words[kWsRedo];
+  failed = h_words[kWsFailed];
+  tied = h_words[kWsTies];
+  if (redo) {
+    const unsigned lane_blocks = (unsigned)((redo + kLaneBlock - 1) / kLaneBlock);
+    ListCapacities::dispatch(list_capacity_for(a.k), [&](auto cap) {
+      hipLaunchKernelGGL(query_lane_kernel<decltype(cap)::value>, dim3(lane_blocks), dim3(kLaneBlock), 0, s, a);
+    });
+    OWLMI_HIP(hipGetLastError());
+  }
+  OWLMI_HIP(hipEventRecord(after_lane, s));
+}
+
+void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
+  const int64_t m = qa.m;
+  const int k = qa.k;
+  // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | levels | distances | sort space
+  auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  uint32_t *null_u32 = nullptr;
+  size_t sort_bytes = 0;
+  OWLMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, null_u32, null_u32, null_u32, null_u32, (int)m, 0, kCodeBits + 1, s));
+  const bool own_levels = qa.d_levels == nullptr, own_dist = qa.exact && qa.d_dist == nullptr;
+  const size_t words_b = align(kWsWords * sizeof(unsigned long long)), col_b = align((size_t)m * sizeof(uint32_t)),
+               dist_b = own_dist ? align((size_t)m * k * sizeof(float)) : 0;
+  char *ws = (char *)workspace(words_b + 6 * col_b + dist_b + align(sort_bytes));
+  unsigned long long *d_words = (unsigned long long *)ws;
+  uint32_t *codes = (uint32_t *)(ws + words_b), *codes_alt = (uint32_t *)(ws + words_b + col_b), *order_in = (uint32_t *)(ws + words_b + 2 * col_b),
+           *order = (uint32_t *)(ws + words_b + 3 * col_b);
+  int32_t *redo = (int32_t *)(ws + words_b + 4 * col_b);
+  int32_t *levels = own_levels ? (int32_t *)(ws + words_b + 5 * col_b) : qa.d_levels;
+  float *dist = own_dist ? (float *)(ws + words_b + 6 * col_b) : qa.d_dist;
+  void *sort_tmp = ws + words_b + 6 * col_b + dist_b;
+
+  QueryKernelArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.bvh = bvh_.view();
+  a.wide = bvh_.wide_view();
+  a.queries = qa.d_queries;
+  a.order = order;
+  a.m = (int32_t)m;
+  a.start_radius = qa.start_radius;
+  a.k = k;
+  a.max_rounds = qa.max_rounds;
+  if (const char *e = getenv("TKNN_QUERY_FORCE_FALLBACK")) a.force_redo = atoi(e) != 0;
+  a.out_idx = qa.d_idx;
+  a.out_dist = dist;
+  a.out_isect = qa.d_isect;
+  a.levels = levels;
+  a.redo = redo;
+  a.ws = d_words;
+  a.stats = counters_ + kStatBase;
+
+  OWLMI_HIP(hipEventRecord(ev_a_, s));
+  OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)m * sizeof(int32_t), s));
+  reset_stat_stripes(s);
+  hipLaunchKernelGGL(query_code_kernel, dim3((unsigned)((m + kLaneBlock - 1) / kLaneBlock)), dim3(kLaneBlock), 0, s, qa.d_queries, (int32_t)m,
+                     bvh_.scene_device(), codes, order_in);
+  OWLMI_HIP(hipGetLastError());
+  OWLMI_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, codes, codes_alt, order_in, order, (int)m, 0, kCodeBits + 1, s));
+  OWLMI_HIP(hipEventRecord(ev_b_, s));
+  unsigned long long failed = 0, tied = 0, failed_exact = 0, tied_exact = 0;
+  query_pass(a, cu_count_, h_counters_, ev_c_, ev_d_, failed, tied, s);
+  fetch_stat_stripes(s);
+  OWLMI_HIP(hipStreamSynchronize(s));
+  KernelStats st = fold_stat_stripes(false);
+  st.handed_over = failed;
+  if (qa.exact && !(st.unfinished && !qa.allow_unfinished)) {
+    a.exact = 1;
+    query_pass(a, cu_count_, h_counters_, ev_e_, ev_f_, failed_exact, tied_exact, s);
+    OWLMI_HIP(hipStreamSynchronize(s));
+    st.handed_over += failed_exact;
+  } else {
+    OWLMI_HIP(hipEventRecord(ev_f_, s));
+    OWLMI_HIP(hipStreamSynchronize(s));
+  }
+  float total_ms = 0, walk_ms = 0, lane_ms = 0;
+  OWLMI_HIP(hipEventElapsedTime(&total_ms, ev_a_, ev_f_));
+  OWLMI_HIP(hipEventElapsedTime(&walk_ms, ev_b_, ev_c_));
+  OWLMI_HIP(hipEventElapsedTime(&lane_ms, ev_c_, ev_d_));
+  if (info) {
+    *info = solve_info(st, qa.start_radius, TKNN_KERNEL_QUERY, 16 * query_nreg(k), total_ms);
+    info->dominant_kernel_ms = walk_ms;  // the walk over the sorted queries; solve_ms also holds the order, the lane pass and the exact pass
+    info->tie_rows = (int64_t)tied;
+    info->tie_ms = lane_ms;
+  }
+  if (st.unfinished && !qa.allow_unfinished) throw RoundsExceeded{};
+}
+
+}  // namespace owlmi

@@ -226,6 +226,65 @@ class TrueKNN:
                 ctypes.byref(n_fixed), self._stream()))
         return int(n_fixed.value)
 
+    def query(self, queries, k, start_radius, max_rounds=64, exact=False, allow_unfinished=False, want_levels=False,
+              out=None, stream=None):
+        """TrueKNN rows for points that are NOT in the built set (tknnQuery): row j is what the reference's loop gives
+        q_j in the set P + {q_j}; a point of P at distance 0 is an ordinary neighbour.  ``queries``: numpy (m,2|3) or a
+        contiguous float32 CUDA tensor (m,3) on the engine's device.  Returns dict(idx (m,k) int32, dist (m,k) float32,
+        intersections (m,) int64[, levels (m,) int32], info).  ``exact``: rows rewritten as the true k nearest points
+        in (dist, index) order.  ``out`` may carry preallocated contiguous tensors of those names."""
+        torch = self._torch
+        k = int(k)
+        if isinstance(queries, np.ndarray):
+            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
+                raise ValueError("query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
+            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
+        if not isinstance(queries, torch.Tensor):
+            raise ValueError("query: queries must be a numpy array or a torch tensor")
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
+        if queries.device != self.device:
+            raise ValueError("query: queries are on %s, the engine on %s" % (queries.device, self.device))
+        if not queries.is_contiguous():
+            raise ValueError("query: queries must be contiguous (packed fp32 triples)")
+        m = int(queries.shape[0])
+        out = dict(out or {})
+        shapes = {"idx": ((m, k), torch.int32), "dist": ((m, k), torch.float32), "intersections": ((m,), torch.int64),
+                  "levels": ((m,), torch.int32)}
+        for name, t in out.items():
+            if name not in shapes:
+                raise ValueError("query: out[%r] is not an output of query" % name)
+            shape, dtype = shapes[name]
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("query: out[%r] must be a tensor" % name)
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError("query: out[%r] must be %s %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
+            if t.device != self.device:
+                raise ValueError("query: out[%r] is on %s, the engine on %s" % (name, t.device, self.device))
+            if not t.is_contiguous():
+                raise ValueError("query: out[%r] must be contiguous (it is written in place)" % name)
+        with torch.cuda.device(self.device):
+            names = ["idx", "dist", "intersections"] + (["levels"] if want_levels or allow_unfinished else [])
+            for name in names:
+                if name not in out:
+                    shape, dtype = shapes[name]
+                    out[name] = torch.empty(tuple(max(d, 0) for d in shape), dtype=dtype, device=self.device)
+            opt = _lib.QueryOptions()
+            opt.m, opt.k, opt.start_radius = m, k, float(start_radius)
+            opt.max_rounds, opt.allow_unfinished, opt.exact = int(max_rounds), int(bool(allow_unfinished)), int(bool(exact))
+            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
+            spare = torch.empty((1,), dtype=torch.int64, device=self.device) if m == 0 else None
+            opt.d_queries = queries.data_ptr() if m > 0 else None
+            for field, name in (("d_idx", "idx"), ("d_dist", "dist"), ("d_intersections", "intersections"), ("d_levels", "levels")):
+                t = out.get(name)
+                setattr(opt, field, None if t is None else (t.data_ptr() if t.numel() > 0 else spare.data_ptr() if spare is not None else None))
+            info = _lib.SolveInfo()
+            launch_on = self._stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
+            _lib.check(self._lib.tknnQuery(self._h, ctypes.byref(opt), ctypes.byref(info), launch_on))
+        self.last_info = info.as_dict()
+        out["info"] = self.last_info
+        return out
+
     def dbscan(self, eps, min_pts, want_counts=False):
         """RT-DBSCAN over the built tree: dict(labels int32 (n,), core bool (n,), [counts], info)."""
         torch = self._torch
@@ -321,6 +380,19 @@ def trueknn(points, k, start_radius, **kw):
     try:
         eng.build(points)
         r = eng.solve(k, start_radius, **kw)
+        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
+        res["build_info"] = eng.build_info
+        return res
+    finally:
+        eng.close()
+
+
+def trueknn_query(points, queries, k, start_radius, **kw):
+    """One-shot helper: build over ``points``, answer for ``queries`` (TrueKNN.query), results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points)
+        r = eng.query(queries, k, start_radius, **kw)
         res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
         res["build_info"] = eng.build_info
         return res

@@ -2,10 +2,13 @@
 """Command line of the reference sample, served by the fused engine:
 
     tools/trueknn_cli.py <points.csv> <n> <dim> <start_radius|auto> <k> <timefile> [--out rows.npz]
+                         [--queries <queries.csv> [--exact]]
 
 Arguments as samples/s01-trueknn/hostCode.cpp:66-73; prints the same "Build time" / "True KNN time"
 / "Total time" lines (hostCode.cpp:211,344-347) and appends the total to <timefile> (:349-356).
 `auto` takes the start radius from owlraytracing_amd.radius.sample_start_radius.
+With --queries the rows are those of the points in that file (same format, every line of it) against the set, not of
+the set itself (TrueKNN.query), and they are printed: one line "j: idx ... | dist ..." per query; --exact asks for exact kNN.
 """
 import argparse
 import os
@@ -26,6 +29,8 @@ def main():
     ap.add_argument("timefile")
     ap.add_argument("--out", default=None, help="write idx/dist/intersections/levels as .npz (tools/compare_reference_dump.py --rows reads it)")
     ap.add_argument("--kernel", type=int, default=0)
+    ap.add_argument("--queries", default=None, help="CSV of query points (same reader as the points): answer for them instead of the set itself")
+    ap.add_argument("--exact", action="store_true", help="with --queries: exact kNN rows in (dist, index) order")
     a = ap.parse_args()
 
     from owlraytracing_amd import datasets
@@ -38,7 +43,19 @@ def main():
     eng = TrueKNN()
     b = eng.build(pts)
     print("Build time: %g seconds." % (b["build_ms"] / 1e3))
-    r = eng.solve(a.k, r0, kernel=a.kernel, want_levels=True)
+    if a.exact and not a.queries:
+        ap.error("--exact goes with --queries")
+    if a.queries:
+        with open(a.queries) as fh:
+            m = sum(1 for line in fh if line.strip())
+        qs = datasets.pad_to_3d(datasets.read_csv_points(a.queries, m, a.dim))
+        print("#owl.sample(main):  num queries: %d" % len(qs))
+        r = eng.query(qs, a.k, r0, exact=a.exact, want_levels=True)
+        idx, dist = r["idx"].cpu().numpy(), r["dist"].cpu().numpy()
+        for j in range(len(qs)):
+            print("%d: %s | %s" % (j, " ".join(str(int(v)) for v in idx[j]), " ".join(repr(float(v)) for v in dist[j])))
+    else:
+        r = eng.solve(a.k, r0, kernel=a.kernel, want_levels=True)
     info = r["info"]
     print("Rounds: %d  start radius %g  final radius %g" % (info["rounds"], r0, info["final_radius"]))
     print("True KNN time: %g seconds." % (info["solve_ms"] / 1e3))
