@@ -48,7 +48,7 @@ struct AccelHeader {
 };
 struct UserGroupAccel {
   AccelHeader h;
-  LbvhView bvh;  // box flavour: boxes[] are what the bounds program wrote, in Morton order
+  LbvhView bvh;  // box flavour: boxes[] are what the bounds program wrote, in curve order
   const GeomRecord *geoms;
 };
 struct Instance {
@@ -72,7 +72,7 @@ struct LaunchDesc {  // the single argument of every __raygen__ kernel
   const void *raygen_data;
   const MissRecord *miss;
   // null, or a permutation of the launch indices (1-D launches): thread t runs launch index order[t].  OptiX promises no
-  // order among the indices of a launch; the host hands out the Morton order of the traced geometry's primitives when a launch
+  // order among the indices of a launch; the host hands out the curve order of the traced geometry's primitives when a launch
   // has as many indices as that geometry has primitives (index i = "the query at primitive i" in the neighbour-query
   // programs this backend is for), so that the threads of a wave walk the same part of the tree
   const int32_t *order;

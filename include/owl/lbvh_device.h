@@ -4,7 +4,7 @@
  * owl/include/owl/owl_device.h:150-174 optixTrace).  Shared by the engine kernels
  * (owlraytracing_amd/csrc) and by user device programs compiled against owl/owl_device.h.
  *
- * Tree: Karras radix tree over Morton-sorted primitives.  Internal node i (0 <= i < n-1) covers
+ * Tree: Karras radix tree over curve-sorted primitives.  Internal node i (0 <= i < n-1) covers
  * the sorted range [min(i,other), max(i,other)] and splits it after position `split`:
  *   left  child covers [first, split]   -> internal node `split`   unless first == split (leaf)
  *   right child covers [split+1, last]  -> internal node `split+1` unless last == split+1 (leaf)
@@ -35,7 +35,7 @@ struct LbvhBox { /* 24 bytes = owl::box3f, what a bounds program writes */
   float hi[3];
 };
 
-/* 64-ary box pyramid over fixed blocks of LBVH_BLOCK Morton-consecutive points ("wide" view of the
+/* 64-ary box pyramid over fixed blocks of LBVH_BLOCK curve-consecutive points ("wide" view of the
  * same sorted order, one node = the 64 children a wave tests in one step):
  *   level[0][b] = box of points [LBVH_BLOCK*b, LBVH_BLOCK*(b+1));  level[l][j] = box of
  *   level[l-1][64j .. 64j+63];  the top level has <= 64 entries. */
@@ -51,8 +51,8 @@ struct LbvhView {
   const LbvhNode *nodes;    /* n-1 */
   const int32_t *rope_node; /* n-1 */
   const int32_t *rope_leaf; /* n */
-  const LbvhPoint *points;  /* n, Morton order (point sets)            | one of these two */
-  const LbvhBox *boxes;     /* n, Morton order (general primitive AABBs) | is non-null       */
+  const LbvhPoint *points;  /* n, curve order (point sets)            | one of these two */
+  const LbvhBox *boxes;     /* n, curve order (general primitive AABBs) | is non-null       */
   const int32_t *prim_id;   /* n: caller's primitive index of sorted slot */
   int32_t n;
   int32_t root; /* 0, or ~0 when n == 1 */

@@ -6,7 +6,7 @@
  *   reference                                               here
  *   ------------------------------------------------------  --------------------------------
  *   owlDeviceBufferCreate(Sphere[n])  hostCode.cpp:165-166   tknnBuild: points already in HBM
- *   owlUserGeomGroupCreate + owlGroupBuildAccel (+ instance  tknnBuild: HIP LBVH (Morton sort +
+ *   owlUserGeomGroupCreate + owlGroupBuildAccel (+ instance  tknnBuild: HIP LBVH (curve-key sort +
  *     group)  hostCode.cpp:201-206 -> bounds program           radix tree) over the centres; the
  *     deviceCode.cu:38-56 + optixAccelBuild                    radius is applied at test time
  *     (owl/UserGeomGroup.cpp:161-217)
@@ -109,7 +109,7 @@ TKNN_API int tknnCreate(tknnEngine *out);
 TKNN_API void tknnDestroy(tknnEngine e);
 
 /* Build the LBVH over n points.  d_xyz: n packed fp32 triples (the Sphere buffer, 12 B each; 2-D
- * data carries z = 0 as in hostCode.cpp:115-118).  The engine keeps its own Morton-ordered copy;
+ * data carries z = 0 as in hostCode.cpp:115-118).  The engine keeps its own curve-ordered copy;
  * d_xyz may be freed afterwards. */
 TKNN_API int tknnBuild(tknnEngine e, const float *d_xyz, int64_t n, tknnBuildInfo *info, void *stream);
 

@@ -534,7 +534,7 @@ __device__ __forceinline__ void db_union_body(const DbArgs &a, int32_t t, unsign
 }
 
 __global__ void __launch_bounds__(kDbBlock) db_union_kernel(DbArgs a) {
-  // The 256 Morton-consecutive points of a workgroup mostly share a tight node and meet the same
+  // The 256 curve-consecutive points of a workgroup mostly share a tight node and meet the same
   // neighbouring tight nodes: every (my group, other group) pair would be united hundreds of times,
   // each a pair of union-find walks through global atomics.  A direct-mapped LDS table of the pairs
   // this workgroup has already taken care of drops the repeats (a stale or raced entry only costs a
@@ -683,7 +683,7 @@ __global__ void __launch_bounds__(kDbBlock) db_uniform_kernel(DbArgs a, const in
   }
 }
 
-// Persistent waves, each working on one PACKET of 64 consecutive groups of the list at a time (Morton neighbours: they
+// Persistent waves, each working on one PACKET of 64 consecutive groups of the list at a time (curve neighbours: they
 // meet the same nodes).  The wave walks the tree ONCE for the packet, in two alternating roles:
 //   lanes = nodes: up to 64 references are popped from the wave's LDS stack and their boxes (a leaf's is its point)
 //                  loaded at once and put into LDS;
@@ -1003,7 +1003,7 @@ __global__ void __launch_bounds__(kDbUnionBlock) __attribute__((amdgpu_waves_per
     int32_t low = a_last;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) low = min(low, __shfl_xor(low, off));
-    // Bounding boxes of the packet's groups, one per 32 lanes (Morton neighbours; two boxes hug a packet that lies across
+    // Bounding boxes of the packet's groups, one per 32 lanes (curve neighbours; two boxes hug a packet that lies across
     // a jump of the Z curve better than one), widened by the reach: a popped node that meets neither can be reached by no
     // group and is dropped where it is popped -- 64 nodes per instruction -- instead of costing a turn of the test loop
     // below, which deals with one node at a time (47 % of the kernel's wave time, half of it on nodes no group reaches).
@@ -1730,7 +1730,7 @@ void Engine::dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, 
     OWLMI_HIP(hipEventRecord(ev_d_, s));
     hipLaunchKernelGGL(db_union_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a);
   } else {
-    // per-slot group references where the ranks go afterwards, the list itself (slot order = Morton order: neighbours in
+    // per-slot group references where the ranks go afterwards, the list itself (slot order = curve order: neighbours in
     // the list are neighbours in space) where the root flags go; its length in counters_[8], the XCDs' cursors behind the statistics' stripes
     int32_t *group_at = a.rank, *groups = is_root;
     unsigned long long *n_groups = counters_ + 8;

@@ -4,7 +4,7 @@
 // replicates everything); this replaces a per-peer, per-cell host loop of tensor operations that
 // cost more than the solve itself.
 //
-// Two kernels over the tile's Morton-sorted points (the engine's own LBVH arrays):
+// Two kernels over the tile's curve-sorted points (the engine's own LBVH arrays):
 //   1. one thread per 16-point leaf block: the block's box against all peer boxes -> a 64-bit mask
 //      of the peers the block may have points for (almost all blocks: 0);
 //   2. one thread per point of a block with a non-zero mask: the point against the boxes of those

@@ -1,4 +1,4 @@
-// lbvh.h -- host API of the HIP LBVH builder (Morton sort + Karras radix tree + fence-free fit).
+// lbvh.h -- host API of the HIP LBVH builder (curve-key sort + Karras radix tree + fence-free fit).
 // Replaces what the reference delegates to optixAccelBuild (owl/UserGeomGroup.cpp:161-217 BUILD,
 // :75-76/:199 UPDATE on refit).  Device layout: include/owl/lbvh_device.h.
 #pragma once
@@ -63,6 +63,7 @@ class Lbvh {
   const int32_t *block_paths_device() const { return point_mode_ && n_ > 1 ? block_paths_ : nullptr; }
   // point trees: row_slot[row] = the sorted slot of the caller's row `row` (the inverse of prim_id), n entries
   const int32_t *row_slot_device() const { return point_mode_ && built_ ? reinterpret_cast<const int32_t *>(order_) : nullptr; }
+  int curve() const { return curve_; }  // CURVE_HILBERT / CURVE_MORTON (curve_key.h): the key the tree was sorted by
   int64_t size() const { return n_; }
   bool built() const { return built_; }
   void clear() { built_ = false; }  // marks the tree unusable (a failed rebuild); memory stays reserved
@@ -83,6 +84,7 @@ class Lbvh {
 
   int64_t n_ = 0, cap_ = 0;
   bool built_ = false, point_mode_ = false;
+  int curve_ = 0;
   size_t bytes_ = 0;
   float *scene_ = nullptr;     // 6 floats + partials
   float *partials_ = nullptr;  // kPartialBlocks*6

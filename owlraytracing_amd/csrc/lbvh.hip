@@ -1,8 +1,9 @@
 // lbvh.hip -- LBVH construction for gfx950.
 //
 // Pipeline (all on the caller's stream, no host synchronisation, no inter-workgroup hand-offs):
-//   scene bounds (2-stage reduction) -> 63-bit Morton codes -> radix sort (hipCUB) -> gather into
-//   Morton order -> Karras radix tree (one thread per internal node) -> bounding boxes + ropes.
+//   scene bounds (2-stage reduction) -> 63-bit curve keys (curve_key.h: the Hilbert index of the point's cell;
+//   TKNN_CURVE=morton: the Z curve) -> radix sort (hipCUB) -> gather into sorted order -> Karras radix tree
+//   (one thread per internal node) -> bounding boxes + ropes.
 //
 // Boxes are NOT fitted bottom-up with atomic "second arrival" counters: on an 8-XCD part that
 // needs an agent-scope release/acquire per tree level per thread (the XCD L2s are not coherent
@@ -12,7 +13,12 @@
 // reads what an earlier launch wrote, and the result is deterministic.
 #include "lbvh.h"
 
+#include "curve_key.h"
+
 #include <hipcub/hipcub.hpp>
+
+#include <cstdlib>
+#include <cstring>
 
 namespace owlmi {
 namespace {
@@ -96,23 +102,15 @@ __global__ void __launch_bounds__(kBlock) scene_final_kernel(const float *__rest
   }
 }
 
-// ---- Morton codes ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t spread21(uint64_t v) {
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-
+// ---- sort keys -------------------------------------------------------------------------------
+// 21 levels of cubic cells over the scene box, 3 bits per level, the coarsest level first (curve_key.h).  Karras
+// needs no more of the key than that: a common prefix of 3 m bits is a common level-m cell.
 template <bool POINTS>
 __global__ void __launch_bounds__(kBlock) morton_kernel(const float *__restrict__ xyz,
                                                        const LbvhBox *__restrict__ boxes, int64_t n,
                                                        const float *__restrict__ scene,
                                                        uint64_t *__restrict__ codes,
-                                                       uint32_t *__restrict__ order) {
+                                                       uint32_t *__restrict__ order, int curve) {
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   float c[3];
@@ -125,19 +123,9 @@ __global__ void __launch_bounds__(kBlock) morton_kernel(const float *__restrict_
     for (int a = 0; a < 3; a++) c[a] = 0.5f * q.lo[a] + 0.5f * q.hi[a];
   }
   float ext = fmaxf(fmaxf(scene[3] - scene[0], scene[4] - scene[1]), scene[5] - scene[2]);
-  // cubic cells: one scale for all axes; degenerate scenes (all points equal) map to cell 0
-  float scale = (ext > 0.f && ext < INFINITY) ? 2097151.0f / ext : 0.f;
-  uint64_t q[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    float t = (c[a] - scene[a]) * scale;
-    t = fminf(fmaxf(t, 0.f), 2097151.0f);  // NaN -> 0 via fmaxf
-    q[a] = (uint64_t)t;
-  }
-  uint64_t code = (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
   // a primitive with a NaN coordinate sorts after every real one (bit 63): such points are nobody's
   // candidates, and kernels that add up whole subtrees need to know where they are
-  if (c[0] != c[0] || c[1] != c[1] || c[2] != c[2]) code = 1ull << 63;
+  uint64_t code = curve_point_key(curve, c[0], c[1], c[2], scene[0], scene[1], scene[2], ext, 21);
   codes[i] = code;
   order[i] = (uint32_t)i;
 }
@@ -176,7 +164,7 @@ __global__ void __launch_bounds__(kBlock) gather_kernel(const float *__restrict_
     p.z = xyz[3 * (int64_t)src + 2];
     // a point with any NaN coordinate is nobody's candidate (every closed-box comparison with NaN is
     // false) and finds none; store it as all-NaN so that kernels may test |c - q| per axis first
-    // (morton_kernel sorts them last: they are the last *nan_count points of the sorted order)
+    // (morton_kernel's key sorts them last: they are the last *nan_count points of the sorted order)
     if (p.x != p.x || p.y != p.y || p.z != p.z) {
       p.x = p.y = p.z = __uint_as_float(0x7fc00000u);
       atomicAdd(nan_count, 1);
@@ -364,6 +352,12 @@ __global__ void __launch_bounds__(kBlock) fit_kernel(LbvhNode *__restrict__ node
   }
 }
 
+// TKNN_CURVE=morton: the Z curve instead of the Hilbert curve (A/B measurements); read once per build of a tree
+inline int curve_from_env() {
+  const char *e = getenv("TKNN_CURVE");
+  return e && !strcmp(e, "morton") ? CURVE_MORTON : CURVE_HILBERT;
+}
+
 inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 template <typename T>
@@ -509,12 +503,13 @@ void Lbvh::build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, 
   reserve(n);
   n_ = n;
   point_mode_ = true;
+  curve_ = curve_from_env();
   int pb = (int)std::min<int64_t>(kPartialBlocks, (n + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(scene_partial_kernel<true>, dim3(pb), dim3(kBlock), 0, stream, d_xyz,
                      (const LbvhBox *)nullptr, n, partials_);
   hipLaunchKernelGGL(scene_final_kernel, dim3(1), dim3(kBlock), 0, stream, partials_, pb, scene_);
   hipLaunchKernelGGL(morton_kernel<true>, dim3(blocks_for(n)), dim3(kBlock), 0, stream, d_xyz,
-                     (const LbvhBox *)nullptr, n, scene_, codes_, order_);
+                     (const LbvhBox *)nullptr, n, scene_, codes_, order_, curve_);
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipMemsetAsync(nan_count(), 0, sizeof(int32_t), stream));
   sort_and_tree(stream);
@@ -536,12 +531,13 @@ void Lbvh::build_from_boxes(const LbvhBox *d_boxes, int64_t n, hipStream_t strea
   reserve(n);
   n_ = n;
   point_mode_ = false;
+  curve_ = curve_from_env();
   int pb = (int)std::min<int64_t>(kPartialBlocks, (n + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(scene_partial_kernel<false>, dim3(pb), dim3(kBlock), 0, stream,
                      (const float *)nullptr, d_boxes, n, partials_);
   hipLaunchKernelGGL(scene_final_kernel, dim3(1), dim3(kBlock), 0, stream, partials_, pb, scene_);
   hipLaunchKernelGGL(morton_kernel<false>, dim3(blocks_for(n)), dim3(kBlock), 0, stream,
-                     (const float *)nullptr, d_boxes, n, scene_, codes_, order_);
+                     (const float *)nullptr, d_boxes, n, scene_, codes_, order_, curve_);
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipMemsetAsync(nan_count(), 0, sizeof(int32_t), stream));
   sort_and_tree(stream);

@@ -839,7 +839,7 @@ void launch(RayGen &rg, int dx, int dy, Params *lp, bool sync) {
   desc.raygen_data = rg.data.ptr;
   desc.miss = (const rec::MissRecord *)c.miss_records.ptr;
   // The order of a launch's indices is the backend's to choose (LaunchDesc::order): a 1-D launch with as many indices as
-  // the context's one built user geometry group has primitives runs them in that group's Morton order -- in the
+  // the context's one built user geometry group has primitives runs them in that group's curve order -- in the
   // neighbour-query programs index i is the query AT primitive i, and 64 neighbouring queries walk the same nodes
   // (the reference's unchanged sample, 1 M points: 8.8 -> 8.0 ms per launch; the rest is the sample's own intersection
   // program keeping its k best by insertion into 24-byte records in global memory).  OWL_LAUNCH_ORDER=0: index = thread.

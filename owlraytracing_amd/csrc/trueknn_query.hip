@@ -7,13 +7,14 @@
 //
 // The self-solve's packet kernel lives on queries being tree slots (64 consecutive sorted slots share leaf
 // blocks).  External queries have no slot, so:
-//   1. query_code_kernel + a radix sort: the queries in the Morton order of the tree's own quantisation, so that
+//   1. query_code_kernel + a radix sort: the queries along the tree's own curve (curve_key.h) over the tree's own quantisation, so that
 //      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
 //   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
 //      shape of team_walk_kernel (trueknn_team.hip) without anything that is per slot;
 //   3. query_lane_kernel: one query per lane, rope traversal, keys that carry the level -- for the few queries
 //      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
 //   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).
+#include "curve_key.h"
 #include "knn_thresholds.h"  // knn_gate_from_worst
 #include "team_lanes.h"
 #include "trueknn_engine.h"
@@ -68,33 +69,16 @@ struct WideLevel {  // per pyramid level, in LDS: lanes of different teams are a
 };
 
 // ---- 1. the order ------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t spread10(uint32_t v) {
-  v &= 0x3ffu;
-  v = (v | (v << 16)) & 0x030000ffu;
-  v = (v | (v << 8)) & 0x0300f00fu;
-  v = (v | (v << 4)) & 0x030c30c3u;
-  v = (v | (v << 2)) & 0x09249249u;
-  return v;
-}
-
 // The tree's quantisation (cubic cells over the scene box, one scale for all axes: lbvh.hip) at ten bits per
-// axis; queries outside the box are clamped to its faces, queries with a NaN coordinate sort last.
+// axis, along the curve the tree was sorted by (the key is hierarchical: ten levels order the queries as the first ten
+// of the tree's 21 order its points); queries outside the box are clamped to its faces, queries with a NaN coordinate sort last.
 __global__ void __launch_bounds__(kLaneBlock) query_code_kernel(const float *__restrict__ queries, int32_t m, const float *__restrict__ scene,
-                                                               uint32_t *__restrict__ codes, uint32_t *__restrict__ order) {
+                                                               uint32_t *__restrict__ codes, uint32_t *__restrict__ order, int curve) {
   const int32_t i = blockIdx.x * kLaneBlock + threadIdx.x;
   if (i >= m) return;
   const float c[3] = {queries[3 * (int64_t)i], queries[3 * (int64_t)i + 1], queries[3 * (int64_t)i + 2]};
   const float ext = fmaxf(fmaxf(scene[3] - scene[0], scene[4] - scene[1]), scene[5] - scene[2]);
-  const float scale = (ext > 0.f && ext < INFINITY) ? 1023.0f / ext : 0.f;
-  uint32_t cell[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    float t = (c[a] - scene[a]) * scale;
-    t = fminf(fmaxf(t, 0.f), 1023.0f);  // NaN -> 0 via fmaxf
-    cell[a] = (uint32_t)t;
-  }
-  uint32_t code = (spread10(cell[0]) << 2) | (spread10(cell[1]) << 1) | spread10(cell[2]);
-  if (c[0] != c[0] || c[1] != c[1] || c[2] != c[2]) code = 1u << kCodeBits;
+  const uint32_t code = (uint32_t)curve_point_key(curve, c[0], c[1], c[2], scene[0], scene[1], scene[2], ext, kCodeBits / 3);
   codes[i] = code;
   order[i] = (uint32_t)i;
 }
@@ -567,7 +551,7 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)m * sizeof(int32_t), s));
   reset_stat_stripes(s);
   hipLaunchKernelGGL(query_code_kernel, dim3((unsigned)((m + kLaneBlock - 1) / kLaneBlock)), dim3(kLaneBlock), 0, s, qa.d_queries, (int32_t)m,
-                     bvh_.scene_device(), codes, order_in);
+                     bvh_.scene_device(), codes, order_in, bvh_.curve());
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, codes, codes_alt, order_in, order, (int)m, 0, kCodeBits + 1, s));
   OWLMI_HIP(hipEventRecord(ev_b_, s));

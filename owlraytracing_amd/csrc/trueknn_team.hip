@@ -4,10 +4,10 @@
 // 64 lanes; on MI355X it is VALU-issue-bound with ~2.5 % useful lanes (profiles/r01_wave_v2_*),
 // because the packet's candidate union is ~40x one query's own box content.  This kernel turns
 // the work around: a wave is FOUR TEAMS OF 16 LANES; a team handles one query at a time and its
-// lanes are the 16 CANDIDATES of one leaf block (LBVH_BLOCK consecutive Morton-sorted points,
+// lanes are the 16 CANDIDATES of one leaf block (LBVH_BLOCK consecutive curve-sorted points,
 // one coalesced 256-byte read) of that query's OWN block list.
 //
-// Per packet of 64 Morton-consecutive queries and per radius level (hostCode.cpp:285-340 rounds):
+// Per packet of 64 curve-consecutive queries and per radius level (hostCode.cpp:285-340 rounds):
 //   1. lanes = queries: LDS query records and conservative query boxes for the gather.
 //   2. lanes = child boxes: the wave walks the 64-ary block pyramid (LbvhWideView) depth-first
 //      with an LDS stack, one wide node per step, against the union box of the packet.
@@ -307,11 +307,11 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     // the own tree's last block: its points fail every test, so the loop needs no "am I still in
     // my list" check
     const int32_t nan_block = a.wide[0].count[0];
-    // SELECT visits blocks outward from the query's own block, alternating sides of its Morton-ordered
+    // SELECT visits blocks outward from the query's own block, alternating sides of its curve-ordered
     // list: near blocks first tightens the k-th-distance gate early (about 30 % fewer inserts than
     // list order on uniform data) and changes nothing else -- the result does not depend on order.
     // COUNT takes the list as it is.
-    // A list that serves the level AFTER the step it was gathered for (see team_kernel) is "the step's blocks in Morton
+    // A list that serves the level AFTER the step it was gathered for (see team_kernel) is "the step's blocks in curve
     // order, then the rest": outward order inside the first part (bits 16..23 of the record; 0: the whole list), the
     // rest as listed -- farther than every block of the first part anyway.
     const int own_pos = (packed >> 8) & 0xff;
@@ -640,7 +640,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
   } while (0)
 #endif
 
-  // Packets are Morton-consecutive, so neighbouring packets read the same leaf blocks.  Each XCD has
+  // Packets are curve-consecutive, so neighbouring packets read the same leaf blocks.  Each XCD has
   // its own L2: packets are dealt to the XCDs in chunks of up to 1024 consecutive packets, a wave
   // pulls from the chunks of the XCD it runs on (HW_REG_XCC_ID) and steals from the others when
   // those are used up.  Placement changes speed only.  (Measured at C2: 15.0 ms with one global
@@ -759,7 +759,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
           reach_step = ext ? r_out + 2.0f * ((qabs + 2.0f * r_out) * 4.76837158203125e-07f) : reach_walk;
         }
       }
-      // The pyramid is culled against FOUR boxes, one per 16 Morton-consecutive queries (= one leaf
+      // The pyramid is culled against FOUR boxes, one per 16 curve-consecutive queries (= one leaf
       // block of queries), not against the packet's one union box: where the Z-curve jumps, or
       // among the outliers of a clustered set, the union covers space none of the queries needs.
       float s_lo_x[4], s_lo_y[4], s_lo_z[4], s_hi_x[4], s_hi_y[4], s_hi_z[4];
@@ -834,7 +834,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         if (tree_n <= 0 || wv.levels <= 0) continue;
         // Depth-first over the inner levels of the pyramid.  Wide nodes whose children are leaf blocks
         // are not expanded one by one but collected (the list grows down from the top of the stack
-        // array) and drained together: in ascending Morton order, the next node's child boxes in
+        // array) and drained together: in ascending curve order, the next node's child boxes in
         // flight while this node's blocks are tested against the 64 queries.
         int sp = 0, nleaf = 0;
         if (lane == 0) stack[wv.levels > 1 ? 0 : kTeamStack - 1] = (wv.levels << 26) | 0;  // virtual root above the top level
@@ -865,7 +865,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
               // children of `c` are leaf blocks.  Keep a survivor only if some single QUERY box reaches
               // it (lanes = queries, the survivor's box by v_readlane): a dozen instructions that save
               // its 64 blocks from being tested one by one where only the group box, not a query,
-              // overlapped.  Nodes are popped in descending Morton order and taken here from the
+              // overlapped.  Nodes are popped in descending curve order and taken here from the
               // highest lane down, so filling the list downwards keeps it ascending in memory.
               unsigned long long rest = om;
               if (rest) stash_boxes(bx);

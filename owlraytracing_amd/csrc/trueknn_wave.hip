@@ -1,6 +1,6 @@
 // trueknn_wave.hip -- the persistent wave-packet TrueKNN kernel (TKNN_KERNEL_WAVE).
 //
-// One wave owns a packet of 64 Morton-consecutive queries (one per lane) and resolves ALL radius
+// One wave owns a packet of 64 curve-consecutive queries (one per lane) and resolves ALL radius
 // levels for it inside one launch; waves are persistent and pull packets from an atomic counter.
 // Per level:
 //   * every lane turns "is candidate c in my box of radius r" (deviceCode.cu:38-56 + the RT-core
@@ -10,7 +10,7 @@
 //   * the wave walks the LBVH cooperatively: an LDS stack of node references, up to 64 nodes popped
 //     and box-tested per step (one per lane) against the union of the packet's thresholds,
 //     survivors' children pushed with ballot + prefix-count compaction;
-//   * subtrees of <= leaf_max points are "leaf ranges": contiguous runs of the Morton-sorted point
+//   * subtrees of <= leaf_max points are "leaf ranges": contiguous runs of the curve-sorted point
 //     array.  A range is refined against the 64 individual query boxes (ballot), loaded with one
 //     coalesced 16 B/lane access (lane l holds its l-th point) and broadcast point by point with
 //     v_readlane, each lane testing the candidate against its own thresholds -- the candidate
