@@ -10,13 +10,14 @@
 //   1. query_code_kernel + a radix sort: the queries along the tree's own curve (curve_key.h) over the tree's own quantisation, so that
 //      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
 //   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
-//      shape of team_walk_kernel (trueknn_team.hip) without anything that is per slot;
+//      walk of team_walk_kernel (trueknn_team.hip; both on team_walk.h) without anything that is per slot;
 //   3. query_lane_kernel: one query per lane, rope traversal, keys that carry the level -- for the few queries
 //      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
 //   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).
 #include "curve_key.h"
 #include "knn_thresholds.h"  // knn_gate_from_worst
 #include "team_lanes.h"
+#include "team_walk.h"
 #include "trueknn_engine.h"
 
 #include <hipcub/hipcub.hpp>
@@ -32,9 +33,7 @@ namespace owlmi {
 namespace {
 
 constexpr int kQueryBlock = 64;       // one wave per workgroup, four teams
-constexpr int kQueryStack = 384;      // stack entries per team, as kWalkStack: up to 63 siblings wait on each of <= 6 levels
 constexpr int kQueryBlocksPerCu = 16;  // 7.3 KB of LDS each: far inside what a CU holds
-constexpr int kQueryMergeAt = 12;     // buffered candidates of some team that trigger a merge (TKNN_MERGE_AT)
 constexpr int kLaneBlock = 256;
 constexpr int kCountedSubtree = 32;   // smallest subtree the lane kernel tries to count instead of walking
 constexpr int kCodeBits = 30;         // ten bits per axis order 10 M queries well enough, and sort in half the passes
@@ -62,12 +61,6 @@ struct QueryKernelArgs {
   unsigned long long *stats;  // the engine's statistics stripes (kStatBase)
 };
 
-struct WideLevel {  // per pyramid level, in LDS: lanes of different teams are at different levels
-  const LbvhBox *boxes;
-  int32_t count;
-  int32_t pad_;
-};
-
 // ---- 1. the order ------------------------------------------------------------------------------------------
 // The tree's quantisation (cubic cells over the scene box, one scale for all axes: lbvh.hip) at ten bits per
 // axis, along the curve the tree was sorted by (the key is hierarchical: ten levels order the queries as the first ten
@@ -84,22 +77,18 @@ __global__ void __launch_bounds__(kLaneBlock) query_code_kernel(const float *__r
 }
 
 // ---- 2. the walk -------------------------------------------------------------------------------------------
-// A team walks the 64-ary pyramid for one query: its 16 lanes test 16 child boxes at a time and push the
-// survivors on the team's LDS stack; a leaf block is 16 points = 16 lanes.  A child box inside the part of the
+// A team walks the 64-ary pyramid for one query (walk_tree, team_walk.h): a child box inside the part of the
 // query's box where the candidate test is certain, and beyond the list's gate, is counted instead of walked.
 // Candidates wait in the team's LDS buffer and are merged into the sorted register list sixteen at a time
 // (t_merge_rows).  Teams of a wave loop in lock step, so there is no __syncthreads, only t_wave_sync.
 template <int NREG>
 __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_eu(4))) query_walk_kernel(QueryKernelArgs a) {
-  __shared__ int32_t stack_mem[4 * kQueryStack];
-  __shared__ WideLevel levels[LBVH_WIDE_LEVELS];
+  __shared__ int32_t stack_mem[4 * kWalkStack];
+  __shared__ WalkLevel levels[LBVH_WIDE_LEVELS];
   __shared__ unsigned long long cand_mem[4 * kCandCapacity];
   const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kQueryStack;
-  if (lane < LBVH_WIDE_LEVELS) {
-    levels[lane].boxes = a.wide.level[lane];
-    levels[lane].count = a.wide.count[lane];
-  }
+  int32_t *stack = stack_mem + team * kWalkStack;
+  walk_fill_levels<1>(levels, &a.wide, lane);
   t_wave_sync();
   const LbvhWideView &wv = a.wide;
   const int32_t clean_end = a.bvh.n - (a.bvh.nan_count ? *a.bvh.nan_count : 0);  // NaN points sort last
@@ -128,11 +117,7 @@ __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_e
       r = dk * 1.000001f + 0x1p-74f;
     }
     while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
-      const float mg = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + 2.0f * r) * 4.76837158203125e-07f;  // 2^-21
-      const float in_below = r - mg, in_upto = r + mg;
-      // boxes that can hold a candidate meet [q - r - 2M, q + r + 2M]; every point of a box inside
-      // [q - r + 2M, q + r - 2M] certainly is one
-      const float rl = r + 2.0f * mg, rs = r - 2.0f * mg;
+      const WalkBox qb(q, r);
       uint32_t part = 0;  // my lane's share of the candidate count of this level
       uint32_t bd[NREG], bi[NREG];  // register j of lane t holds list entry 16 j + t
 #pragma unroll
@@ -141,96 +126,28 @@ __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_e
         bi[j] = 0u;
       }
       float tau2 = INFINITY;
-      bool overflow = false;
       const bool full = a.k == 16 * NREG;  // no spare list entry to see a tie with the row's last in
       uint32_t left_out = 0xffffffffu;
-      auto kth_dist = [&]() -> float {
-        uint32_t reg = bd[0];
-#pragma unroll
-        for (int j = 1; j < NREG; j++) reg = ((a.k - 1) >> 4) == j ? bd[j] : reg;
-        return __uint_as_float(t_lane_read(reg, (team << 4) + ((a.k - 1) & 15)));
-      };
       unsigned long long *my_cand = cand_mem + team * kCandCapacity;
       uint32_t fill_n = 0;
-      auto merge_buffer = [&]() {
+      auto merge_buffer = [&]() __attribute__((always_inline)) {
         t_wave_sync();
         t_merge_rows<NREG>(bd, bi, left_out, full, my_cand, fill_n, tl);
         t_wave_sync();
         fill_n = 0;
-        tau2 = knn_gate_from_worst(kth_dist());
+        tau2 = knn_gate_from_worst(t_kth_dist<NREG>(bd, a.k, team));
       };
-      int sp = 0;
-      if (active && wv.levels > 0) {
-        if (tl == 0) stack[0] = (wv.levels << 26) | 0;  // virtual root above the top level
-        sp = 1;
-      }
-      t_wave_sync();
-      while (__ballot(sp > 0) != 0ull) {
-        const bool work = sp > 0;
-        const int32_t e = work ? stack[sp - 1] : (1 << 26);
-        if (work) sp--;
-        const int lvl = (e >> 26) - 1;  // level of the children
-        const int32_t first_child = (e & 0x3ffffff) * 64;
-        const WideLevel wl = levels[lvl];
-        // the virtual root has the top level's few boxes as its children
-        const int32_t nchild = lvl == wv.levels - 1 ? (first_child == 0 ? wl.count : 0) : wl.count;
-        LbvhBox bx4[4];  // the node's 64 child boxes, all four loads in flight at once
-#pragma unroll
-        for (int chunk = 0; chunk < 4; chunk++) {
-          const int32_t c = first_child + 16 * chunk + tl;
-          bx4[chunk] = LbvhBox{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-          if (work && c < nchild) bx4[chunk] = wl.boxes[c];
-        }
-#pragma unroll
-        for (int chunk = 0; chunk < 4; chunk++) {
-          const int32_t c = first_child + 16 * chunk + tl;
-          const bool valid = work && c < nchild;
-          const LbvhBox bx = bx4[chunk];
-          const bool ov = valid & (bx.lo[0] <= q.x + rl) & (bx.hi[0] >= q.x - rl) & (bx.lo[1] <= q.y + rl) &
-                          (bx.hi[1] >= q.y - rl) & (bx.lo[2] <= q.z + rl) & (bx.hi[2] >= q.z - rl);
-          node_tests += valid ? 1u : 0u;
-          bool counted = false;
-          if (ov) {
-            const bool inside = (bx.lo[0] >= q.x - rs) & (bx.hi[0] <= q.x + rs) & (bx.lo[1] >= q.y - rs) &
-                                (bx.hi[1] <= q.y + rs) & (bx.lo[2] >= q.z - rs) & (bx.hi[2] <= q.z + rs);
-            if (inside) {
-              const float gx = fmaxf(fmaxf(bx.lo[0] - q.x, q.x - bx.hi[0]), 0.f), gy = fmaxf(fmaxf(bx.lo[1] - q.y, q.y - bx.hi[1]), 0.f),
-                          gz = fmaxf(fmaxf(bx.lo[2] - q.z, q.z - bx.hi[2]), 0.f);
-              const float m2 = (gx * gx + gy * gy) + gz * gz;  // <= every point's squared distance, up to rounding
-              const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
-              const int64_t first = (int64_t)c * span;
-              if (m2 * 0.999995f > tau2 && first + span <= (int64_t)clean_end) {
-                part += (uint32_t)span;
-                counted = true;
-              }
-            }
-          }
-          const bool keep = ov && !counted;
-          const uint32_t keep_mine = (uint32_t)(__ballot(keep) >> (team * 16)) & 0xffffu;
-          if (lvl > 0) {
-            if (sp + __popc(keep_mine) > kQueryStack) {
-              overflow = true;
-            } else {
-              if (keep) stack[sp + __popc(keep_mine & ((1u << tl) - 1u))] = (lvl << 26) | c;
-              sp += __popc(keep_mine);
-            }
-          } else {
-            // children are leaf blocks: lanes become the 16 points of one block at a time
-            uint32_t todo = keep_mine;
-            while (__ballot(todo != 0u) != 0ull) {
-              const bool has_b = todo != 0u;
-              const int32_t b = first_child + 16 * chunk + (has_b ? __ffs((int)todo) - 1 : 0);
-              todo &= todo - 1u;
-              LbvhPoint p = {__uint_as_float(0x7fc00000u), 0.f, 0.f, -1};
-              if (has_b) p = a.bvh.points[(int64_t)b * LBVH_BLOCK + tl];  // (padded with NaN sentinels to whole blocks: lbvh.hip)
+      bool overflow = false;
+      if (wv.levels > 0)
+        walk_tree<false>(
+            levels, wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
+            [&](const LbvhBox &bx, int32_t c, int lvl) { return !walk_count_box(bx, q, qb, tau2, c, lvl, clean_end, part); },
+            [&](int32_t b, bool has_b) {
+              LbvhPoint p;
+              float d2;
+              const unsigned long long in_m = walk_block_test(a.bvh.points, b, has_b, tl, q, qb, p, d2);
               point_tests += has_b ? 1u : 0u;
-              const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-              const float t = has_b ? fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz)) : __uint_as_float(0x7fc00000u);
-              unsigned long long in_m = __ballot(t <= in_below);
-              const unsigned long long maybe_m = __ballot(t <= in_upto) & ~in_m;
-              if (maybe_m) in_m |= maybe_m & __ballot(knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z));
               part = t_count(part, in_m);
-              const float d2 = t_dist2(dx, dy, dz);
               const unsigned long long pm = in_m & __ballot(d2 <= tau2);
               if (pm) {
                 const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
@@ -238,43 +155,20 @@ __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_e
                 fill_n += __popc(mine16);
                 if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
               }
-            }
-            // a tighter gate for what comes next as soon as a handful of candidates wait
-            if (__ballot(fill_n >= (uint32_t)kQueryMergeAt) != 0ull) merge_buffer();
-          }
-        }
-        t_wave_sync();
-      }
+            },
+            [&]() {  // a tighter gate for what comes next as soon as a handful of candidates wait
+              if (__ballot(fill_n >= (uint32_t)TKNN_MERGE_AT) != 0ull) merge_buffer();
+            }, overflow);
       if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
-      if (full) {
-        // the smallest key left out by any merge, where the tie test below looks for it: lane 15
-        uint32_t v = left_out;
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128 /*row_ror:8*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124 /*row_ror:4*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x122 /*row_ror:2*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x121 /*row_ror:1*/, 0xf, 0xf, false));
-        left_out = v;
-      }
+      if (full) left_out = t_team_min_u32(left_out);  // where the tie test below looks for it: lane 15
       // ---- the level's outcome, per team ----
       const uint32_t cnt = t_team_sum(part);  // no self: every candidate is a neighbour
       const bool fin = active && !overflow && (a.exact || cnt >= (uint32_t)a.k);
-      // Does the row depend on how bit-identical distances are ordered?  The list holds (dist, index) order; the
-      // reference's is (dist, first level, index).  At level 0 they are the same; later, only where two tied
-      // candidates can have become candidates at different levels (tie_may_straddle).
-      bool tie = false;
-      if (!a.exact && level > 0) {
-        const float qmax = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z));
-#pragma unroll
-        for (int reg = 0; reg < NREG; reg++) {
-          uint32_t before = t_team_shr1(bd[reg]);
-          if (reg > 0) before |= t_dpp<0x121>(bd[reg - 1]) & (tl == 0 ? 0xffffffffu : 0u);
-          bool t = ((reg > 0) | (tl >= 1)) & (16 * reg + tl <= a.k) & (bd[reg] == before);
-          t |= reg == NREG - 1 && full && tl == 15 && left_out == bd[reg];
-          t = t && fin && tie_may_straddle(__uint_as_float(bd[reg]), a.start_radius, r, qmax, 1.73206f);
-          tie |= t;
-        }
-      }
-      const bool tied = ((uint32_t)(__ballot(tie) >> (team * 16)) & 0xffffu) != 0u;
+      // Does the row depend on how bit-identical distances are ordered (t_row_ties)?  At level 0 the list's order and
+      // the reference's are the same.
+      bool tie = false, edge = false;
+      if (!a.exact && level > 0) t_row_ties<NREG>(bd, left_out, full, a.k, tl, q, a.start_radius, r, 1.73206f, fin, tie, edge);
+      const bool tied = t_team_any(tie, team);
       if (active && (overflow || a.force_redo || (fin && tied))) {
         // left to the lane kernel, which starts the query from level 0: nothing of it is written or counted here
         if (tl == 0) {
@@ -319,23 +213,13 @@ __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_e
       }
     }
   }
-  const unsigned long long isum = t_wave_sum(isect_sum), lsum = t_wave_sum(levels_sum), nt = t_wave_sum(node_tests),
-                           pt = t_wave_sum(point_tests), usum = t_wave_sum((unsigned long long)unfinished),
-                           fsum = t_wave_sum((unsigned long long)failed), tsum = t_wave_sum((unsigned long long)tied_rows);
-  const int ml = (int)t_wave_max((float)max_level);
+  const unsigned long long fsum = t_wave_sum((unsigned long long)failed), tsum = t_wave_sum((unsigned long long)tied_rows);
   if (lane == 0) {
     if (fsum) atomicAdd(&a.ws[kWsFailed], fsum);
     if (tsum) atomicAdd(&a.ws[kWsTies], tsum);
-    if (!a.exact) {
-      unsigned long long *st = a.stats + (blockIdx.x & (kStatStripes - 1)) * kStatStride;
-      atomicMax(&st[1], (unsigned long long)ml);
-      atomicAdd(&st[2], nt);
-      atomicAdd(&st[3], pt);
-      atomicAdd(&st[4], isum);
-      atomicAdd(&st[6], lsum);
-      if (usum) atomicAdd(&st[7], usum);
-    }
   }
+  if (!a.exact)
+    t_add_stats(a.stats + (blockIdx.x & (kStatStripes - 1)) * kStatStride, lane, max_level, node_tests, point_tests, isect_sum, levels_sum, unfinished);
 }
 
 // ---- 3. one query per lane -----------------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 // by (dist, index).
 #include "knn_thresholds.h"  // knn_gate_from_worst
 #include "team_lanes.h"
+#include "team_walk.h"
 #include "trueknn_engine.h"
 
 #include <hipcub/hipcub.hpp>
@@ -102,9 +103,6 @@ inline int grab_for(int64_t count, int blocks, int turns, int cap) {
 #define TKNN_NREG3 1
 #endif
 inline int nreg_for(int k) { return k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 48 && TKNN_NREG3 ? 3 : 4)); }
-#ifndef TKNN_MERGE_AT
-#define TKNN_MERGE_AT 12  // buffered candidates of some team at the end of a group of four blocks that trigger a merge
-#endif
 #ifndef TKNN_SORT_FIRST
 #define TKNN_SORT_FIRST 1  // k <= 16: 1 = sort the query's own block on the spot instead of buffering its candidates
 #endif
@@ -1157,16 +1155,10 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
 // candidate test is certain, and beyond the list's gate, is COUNTED (its points are consecutive
 // sorted slots: the count is arithmetic) instead of walked -- a box over a cluster of 100 000 points
 // costs a few hundred steps.  Levels loop inside the kernel (hostCode.cpp:285-340 per query).
-constexpr int kWalkStack = 384;  // stack entries per team: up to 63 siblings wait on each of <= 6 levels
+// The walk itself, its box and block tests and the counting rule are team_walk.h's.
 
 struct NotDone {
   __host__ __device__ bool operator()(uint8_t d) const { return d == 0; }
-};
-
-struct WalkLevel {  // per tree and pyramid level, in LDS: lanes of different teams are at different levels
-  const LbvhBox *boxes;
-  int32_t count;
-  int32_t pad_;
 };
 
 template <bool HALO, int NREG>
@@ -1176,26 +1168,14 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(Te
   __shared__ unsigned long long cand_mem[4 * kCandCapacity];  // per team: candidates waiting to be merged into its list (t_merge_rows)
   const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
   int32_t *stack = stack_mem + team * kWalkStack;
-  if (lane < 2 * LBVH_WIDE_LEVELS) {
-    const int t = lane / LBVH_WIDE_LEVELS, l = lane % LBVH_WIDE_LEVELS;
-    levels[t][l].boxes = a.wide[t].level[l];
-    levels[t][l].count = a.wide[t].count[l];
-  }
+  walk_fill_levels<2>(levels[0], a.wide, lane);
   t_wave_sync();
   unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
   unsigned int unfinished = 0, failed = 0;
   int max_level = 0;
-  int turn_next = 0, turn_left = 0;  // wave-uniform: the slots of my turn at the cursor that are still to do
+  int turn_next = 0, turn_left = 0;  // (t_next_slots)
   for (;;) {
-    if (turn_left == 0) {
-      int got = 0;
-      if (lane == 0) got = (int)atomicAdd(&a.counters[0], 4ull * (unsigned long long)max(a.grab, 1));
-      turn_next = __builtin_amdgcn_readfirstlane(got);
-      turn_left = max(a.grab, 1);
-    }
-    const int base = turn_next;
-    turn_next += 4;
-    turn_left--;
+    const int base = t_next_slots(&a.counters[0], a.grab, lane, turn_next, turn_left);
     if (base >= nslots) break;
     const bool has_q = base + team < nslots;
     const int32_t slot = has_q ? (slots ? slots[base + team] : base + team) : 0;
@@ -1208,11 +1188,7 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(Te
     for (int i = 0; i < level; i++) r = r * 2.0f;
     bool active = has_q;
     while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
-      const float mg = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + 2.0f * r) * 4.76837158203125e-07f;  // 2^-21
-      const float in_below = r - mg, in_upto = r + mg;
-      // boxes that can hold a candidate meet [q - r - 2M, q + r + 2M]; every point of a box inside
-      // [q - r + 2M, q + r - 2M] certainly is one
-      const float rl = r + 2.0f * mg, rs = r - 2.0f * mg;
+      const WalkBox qb(q, r);
       uint32_t part = 0;  // my lane's share of the candidate count of this level
       uint32_t bd[NREG], bi[NREG];  // register j of lane t holds list entry 16 j + t (indices are compile-time: stays in VGPRs)
 #pragma unroll
@@ -1224,127 +1200,46 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(Te
       bool overflow = false;
       const bool full = a.k == 16 * NREG;  // see team_pass
       uint32_t left_out = 0xffffffffu;
-      auto kth_dist = [&]() -> float {
-        uint32_t reg = bd[0];
-#pragma unroll
-        for (int j = 1; j < NREG; j++) reg = ((a.k - 1) >> 4) == j ? bd[j] : reg;
-        return __uint_as_float(t_lane_read(reg, (team << 4) + ((a.k - 1) & 15)));
-      };
       // candidates wait in the team's buffer and are merged sixteen at a time, as in the passes (one insert per lock-step
       // round was most of this kernel's time at k = 64: some 200 inserts per query)
       unsigned long long *my_cand = cand_mem + team * kCandCapacity;
       uint32_t fill_n = 0;
-      auto merge_buffer = [&]() {
+      auto merge_buffer = [&]() __attribute__((always_inline)) {
         t_wave_sync();
         t_merge_rows<NREG>(bd, bi, left_out, full, my_cand, fill_n, tl);
         t_wave_sync();
         fill_n = 0;
-        tau2 = knn_gate_from_worst(kth_dist());
+        tau2 = knn_gate_from_worst(t_kth_dist<NREG>(bd, a.k, team));
       };
       for (int tree = 0; tree < (HALO ? 2 : 1); tree++) {
         const LbvhWideView &wv = a.wide[tree];
         const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
         if (tv.n <= 0 || wv.levels <= 0) continue;
         const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-        int sp = 0;
-        if (active) {
-          if (tl == 0) stack[0] = (wv.levels << 26) | 0;  // virtual root above the top level
-          sp = 1;
-        }
-        t_wave_sync();
-        while (__ballot(sp > 0) != 0ull) {
-          const bool work = sp > 0;
-          const int32_t e = work ? stack[sp - 1] : (1 << 26);
-          if (work) sp--;
-          const int lvl = (e >> 26) - 1;  // level of the children
-          const int32_t first_child = (e & 0x3ffffff) * 64;
-          const WalkLevel wl = levels[tree][lvl];
-          // the virtual root has the top level's few boxes as its children
-          const int32_t nchild = lvl == wv.levels - 1 ? (first_child == 0 ? wl.count : 0) : wl.count;
-          LbvhBox bx4[4];  // the node's 64 child boxes, all four loads in flight at once
-#pragma unroll
-          for (int chunk = 0; chunk < 4; chunk++) {
-            const int32_t c = first_child + 16 * chunk + tl;
-            bx4[chunk] = LbvhBox{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            if (work && c < nchild) bx4[chunk] = wl.boxes[c];
-          }
-#pragma unroll
-          for (int chunk = 0; chunk < 4; chunk++) {
-            const int32_t c = first_child + 16 * chunk + tl;
-            const bool valid = work && c < nchild;
-            const LbvhBox bx = bx4[chunk];
-            const bool ov = valid & (bx.lo[0] <= q.x + rl) & (bx.hi[0] >= q.x - rl) & (bx.lo[1] <= q.y + rl) &
-                            (bx.hi[1] >= q.y - rl) & (bx.lo[2] <= q.z + rl) & (bx.hi[2] >= q.z - rl);
-            node_tests += valid ? 1u : 0u;
-            // inside the certain part of my box and beyond the gate: count, do not walk
-            bool counted = false;
-            if (ov) {
-              const bool inside = (bx.lo[0] >= q.x - rs) & (bx.hi[0] <= q.x + rs) & (bx.lo[1] >= q.y - rs) &
-                                  (bx.hi[1] <= q.y + rs) & (bx.lo[2] >= q.z - rs) & (bx.hi[2] <= q.z + rs);
-              if (inside) {
-                const float gx = fmaxf(fmaxf(bx.lo[0] - q.x, q.x - bx.hi[0]), 0.f), gy = fmaxf(fmaxf(bx.lo[1] - q.y, q.y - bx.hi[1]), 0.f),
-                            gz = fmaxf(fmaxf(bx.lo[2] - q.z, q.z - bx.hi[2]), 0.f);
-                const float m2 = (gx * gx + gy * gy) + gz * gz;
-                const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
-                const int64_t first = (int64_t)c * span;
-                if (m2 * 0.999995f > tau2 && first + span <= (int64_t)clean_end) {
-                  part += (uint32_t)span;
-                  counted = true;
-                }
+        walk_tree<false>(
+            levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
+            [&](const LbvhBox &bx, int32_t c, int lvl) { return !walk_count_box(bx, q, qb, tau2, c, lvl, clean_end, part); },
+            [&](int32_t b, bool has_b) {
+              LbvhPoint p;
+              float d2;
+              const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
+              point_tests += has_b ? 1u : 0u;
+              part = t_count(part, in_m);
+              unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
+              if (TKNN_DIAG_BUILD && (a.diag & 1)) pm = 0;
+              if (pm) {
+                const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
+                if ((mine16 >> tl) & 1u) my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)p.id;
+                fill_n += __popc(mine16);
+                if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
               }
-            }
-            const bool keep = ov && !counted;
-            const uint32_t keep_mine = (uint32_t)(__ballot(keep) >> (team * 16)) & 0xffffu;
-            if (lvl > 0) {
-              if (sp + __popc(keep_mine) > kWalkStack) {
-                overflow = true;
-              } else {
-                if (keep) stack[sp + __popc(keep_mine & ((1u << tl) - 1u))] = (lvl << 26) | c;
-                sp += __popc(keep_mine);
-              }
-            } else {
-              // children are leaf blocks: lanes become the 16 points of one block at a time
-              uint32_t todo = keep_mine;
-              while (__ballot(todo != 0u) != 0ull) {
-                const bool has_b = todo != 0u;
-                const int32_t b = first_child + 16 * chunk + (has_b ? __ffs((int)todo) - 1 : 0);
-                todo &= todo - 1u;
-                LbvhPoint p = {__uint_as_float(0x7fc00000u), 0.f, 0.f, -1};
-                if (has_b) p = tv.points[(int64_t)b * LBVH_BLOCK + tl];
-                point_tests += has_b ? 1u : 0u;
-                const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-                const float t = has_b ? fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz)) : __uint_as_float(0x7fc00000u);
-                unsigned long long in_m = __ballot(t <= in_below);
-                const unsigned long long maybe_m = __ballot(t <= in_upto) & ~in_m;
-                if (maybe_m) in_m |= maybe_m & __ballot(knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z));
-                part = t_count(part, in_m);
-                const float d2 = t_dist2(dx, dy, dz);
-                unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
-                if (TKNN_DIAG_BUILD && (a.diag & 1)) pm = 0;
-                if (pm) {
-                  const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
-                  if ((mine16 >> tl) & 1u) my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)p.id;
-                  fill_n += __popc(mine16);
-                  if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
-                }
-              }
-              // a tighter gate for what comes next as soon as a handful of candidates wait
+            },
+            [&]() {  // a tighter gate for what comes next as soon as a handful of candidates wait
               if (__ballot(fill_n >= (uint32_t)TKNN_MERGE_AT) != 0ull) merge_buffer();
-            }
-          }
-          t_wave_sync();
-        }
+            }, overflow);
       }
       if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
-      if (full) {
-        // the smallest key left out by any merge, where the tie test below looks for it: lane 15
-        uint32_t v = left_out;
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128 /*row_ror:8*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124 /*row_ror:4*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x122 /*row_ror:2*/, 0xf, 0xf, false));
-        v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x121 /*row_ror:1*/, 0xf, 0xf, false));
-        left_out = v;
-      }
+      if (full) left_out = t_team_min_u32(left_out);  // the smallest key left out by any merge, where the tie test below looks for it: lane 15
       // ---- the level's outcome, per team ----
       const uint32_t cnt = t_team_sum(part);
       const uint32_t others = cnt ? cnt - 1u : 0u;  // a query lies in its own box
@@ -1360,36 +1255,12 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(Te
           for (int reg = 0; reg < NREG; reg++) {
             const int j = tl + 16 * reg;
             if (j >= a.k) continue;
-            const int64_t o = (int64_t)row * a.k + j;
-            const int32_t prim = knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]);
-            const float d = __uint_as_float(bd[reg]);
-            if (a.out_idx) a.out_idx[o] = prim;
-            if (a.out_dist) a.out_dist[o] = d;
-            if (a.out_fb) {
-              tknnNeigh ev;
-              ev.ind = prim;
-              ev.dist = d;
-              ev.numNeighbors = j == 0 ? 0 : a.k;
-              ev.pad_ = 0;
-              ev.intersections = j == 0 ? isect : 0;
-              a.out_fb[o] = ev;
-            }
+            t_write_entry(a.out_idx, a.out_dist, a.out_fb, (int64_t)row * a.k + j, knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]),
+                          __uint_as_float(bd[reg]), j, a.k, isect);
           }
-          bool tie = false, edge = false;
-          const float qmax = fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z));
-#pragma unroll
-          for (int reg = 0; reg < NREG; reg++) {
-            uint32_t before = t_team_shr1(bd[reg]);
-            if (reg > 0) before |= t_dpp<0x121>(bd[reg - 1]) & (tl == 0 ? 0xffffffffu : 0u);
-            bool t = ((reg > 0) | (tl >= 1)) & (16 * reg + tl <= a.k) & (bd[reg] == before);
-            const bool out_t = reg == NREG - 1 && full && tl == 15 && left_out == bd[reg];
-            t |= out_t;
-            t = t && tie_may_straddle(__uint_as_float(bd[reg]), q_r0, r, qmax, a.tie_span);
-            tie |= t;
-            edge |= t && (16 * reg + tl == a.k || out_t);  // (a tie with a candidate that is not written: knn_flag_tie)
-          }
-          const bool tied = ((uint32_t)(__ballot(tie) >> (team * 16)) & 0xffffu) != 0u;
-          const bool tied_edge = ((uint32_t)(__ballot(edge) >> (team * 16)) & 0xffffu) != 0u;
+          bool tie, edge;
+          t_row_ties<NREG>(bd, left_out, full, a.k, tl, q, q_r0, r, a.tie_span, true, tie, edge);
+          const bool tied = t_team_any(tie, team), tied_edge = t_team_any(edge, team);
           if (tl == 0) {
             if (a.out_isect) a.out_isect[row] = isect;
             if (a.out_level) a.out_level[row] = level;
@@ -1416,20 +1287,10 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(Te
       }
     }
   }
-  const unsigned long long isum = t_wave_sum(isect_sum), lsum = t_wave_sum(levels_sum), nt = t_wave_sum(node_tests),
-                           pt = t_wave_sum(point_tests) * LBVH_BLOCK / 16, usum = t_wave_sum((unsigned long long)unfinished),
-                           fsum = t_wave_sum((unsigned long long)failed);
-  const int ml = (int)t_wave_max((float)max_level);
-  if (lane == 0) {
-    unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
-    atomicMax(&st[1], (unsigned long long)ml);
-    atomicAdd(&st[2], nt);
-    atomicAdd(&st[3], pt);
-    atomicAdd(&st[4], isum);
-    atomicAdd(&st[6], lsum);
-    if (usum) atomicAdd(&st[7], usum);
-    if (fsum) atomicAdd(&st[8], fsum);
-  }
+  unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
+  t_add_stats(st, lane, max_level, node_tests, point_tests, isect_sum, levels_sum, unfinished);
+  const unsigned long long fsum = t_wave_sum((unsigned long long)failed);
+  if (lane == 0 && fsum) atomicAdd(&st[8], fsum);
 }
 
 
@@ -1466,8 +1327,7 @@ __global__ void __launch_bounds__(256) team_prep_kernel(uint8_t *done, uint8_t *
 // it passes (the test is monotone in r).  Only neighbours within the row's k-th distance can be
 // part of the answer, and that distance is already known (it does not depend on the order of ties):
 // the walk prunes with it from the start, so a row costs a few wide nodes and leaf blocks.
-constexpr int kFixStack = 384;  // as the walk: 6 KB of LDS per wave leaves room for 16 waves per CU; the ball pruning keeps stacks far below
-
+// (The stack is the walk's: 6 KB of LDS per wave leaves room for 16 waves per CU; the ball pruning keeps stacks far below.)
 struct HasTie {
   __host__ __device__ bool operator()(uint8_t t) const { return (t & 0x7f) != 0; }  // (bit 7 alone: team_pass's note, no flag)
 };
@@ -1484,28 +1344,16 @@ __global__ void __launch_bounds__(kTeamBlock) tie_fix_kernel(TeamArgs a, const i
   else if (nslots < 0)
     nslots = (int32_t)min(a.counters[kTieCounter], (unsigned long long)kTieListCap);
   if (nslots <= 0) return;
-  __shared__ int32_t stack_mem[4 * kFixStack];
+  __shared__ int32_t stack_mem[4 * kWalkStack];
   __shared__ WalkLevel levels[2][LBVH_WIDE_LEVELS];
   const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kFixStack;
-  if (lane < 2 * LBVH_WIDE_LEVELS) {
-    const int t = lane / LBVH_WIDE_LEVELS, l = lane % LBVH_WIDE_LEVELS;
-    levels[t][l].boxes = a.wide[t].level[l];
-    levels[t][l].count = a.wide[t].count[l];
-  }
+  int32_t *stack = stack_mem + team * kWalkStack;
+  walk_fill_levels<2>(levels[0], a.wide, lane);
   t_wave_sync();
   unsigned int failed = 0, stood = 0;
-  int turn_next = 0, turn_left = 0;  // (as in team_walk_kernel)
+  int turn_next = 0, turn_left = 0;  // (t_next_slots)
   for (;;) {
-    if (turn_left == 0) {
-      int got = 0;
-      if (lane == 0) got = (int)atomicAdd(&a.counters[kTieCounter + 1], 4ull * (unsigned long long)max(a.grab, 1));
-      turn_next = __builtin_amdgcn_readfirstlane(got);
-      turn_left = max(a.grab, 1);
-    }
-    const int base = turn_next;
-    turn_next += 4;
-    turn_left--;
+    const int base = t_next_slots(&a.counters[kTieCounter + 1], a.grab, lane, turn_next, turn_left);
     if (base >= nslots) break;
     bool active = base + team < nslots;
     const int32_t slot = active ? slots[base + team] : 0;
@@ -1517,18 +1365,7 @@ __global__ void __launch_bounds__(kTeamBlock) tie_fix_kernel(TeamArgs a, const i
     const float q_r0 = a.start_radii ? a.start_radii[row] : a.start_radius;
     float r = q_r0;
     for (int i = 0; i < level; i++) r = r * 2.0f;
-    const float mg = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + 2.0f * r) * 4.76837158203125e-07f;  // 2^-21, as in team_walk_kernel
-    const float in_below = r - mg, in_upto = r + mg;
-    const float rl = r + 2.0f * mg;
-    // key word between distance and index: the level at which the candidate was first one
-    auto first_level = [&](const LbvhPoint &p) -> uint32_t {
-      float rr = q_r0;
-      for (int l = 0; l < level; l++) {
-        if (knn_in_box(p.x, p.y, p.z, rr, q.x, q.y, q.z)) return (uint32_t)l;
-        rr = rr * 2.0f;
-      }
-      return (uint32_t)level;
-    };
+    const WalkBox qb(q, r);
     uint32_t bd[NREG], bl[NREG], bi[NREG];
 #pragma unroll
     for (int j = 0; j < NREG; j++) {
@@ -1536,12 +1373,6 @@ __global__ void __launch_bounds__(kTeamBlock) tie_fix_kernel(TeamArgs a, const i
       bl[j] = 0u;
       bi[j] = 0u;
     }
-    auto kth_dist = [&]() -> float {
-      uint32_t reg = bd[0];
-#pragma unroll
-      for (int j = 1; j < NREG; j++) reg = ((a.k - 1) >> 4) == j ? bd[j] : reg;
-      return __uint_as_float(t_lane_read(reg, (team << 4) + ((a.k - 1) & 15)));
-    };
     // the row's k-th distance, if the caller asked for distances (else the gate closes as the list fills)
     float tau2 = INFINITY;
     if (active) {
@@ -1592,122 +1423,71 @@ __global__ void __launch_bounds__(kTeamBlock) tie_fix_kernel(TeamArgs a, const i
             differs = true;
           } else {
             const LbvhPoint pa = a.bvh.points[a.row_slot[ri[reg]]], pb = a.bvh.points[a.row_slot[pi]];
-            differs |= first_level(pa) != first_level(pb);
+            differs |= first_level(pa, q, q_r0, level) != first_level(pb, q, q_r0, level);
           }
         }
       }
-      const bool team_differs = ((uint32_t)(__ballot(differs) >> (team * 16)) & 0xffffu) != 0u;
-      if (look && !team_differs) {  // the row stands
+      if (look && !t_team_any(differs, team)) {  // the row stands
         active = false;
         stood += tl == 0 ? 1u : 0u;
       }
     }
     bool overflow = false;
+    unsigned long long node_tests = 0;  // (this pass reports no statistics)
     for (int tree = 0; tree < (HALO ? 2 : 1); tree++) {
       const LbvhWideView &wv = a.wide[tree];
       const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
       if (tv.n <= 0 || wv.levels <= 0) continue;
-      int sp = 0;
-      if (active) {
-        if (tl == 0) stack[0] = (wv.levels << 26) | 0;  // virtual root above the top level
-        sp = 1;
-      }
-      t_wave_sync();
-      while (__ballot(sp > 0) != 0ull) {
-        const bool work = sp > 0;
-        const int32_t e = work ? stack[sp - 1] : (1 << 26);
-        if (work) sp--;
-        const int lvl = (e >> 26) - 1;  // level of the children
-        const int32_t first_child = (e & 0x3ffffff) * 64;
-        const WalkLevel wl = levels[tree][lvl];
-        const int32_t nchild = lvl == wv.levels - 1 ? (first_child == 0 ? wl.count : 0) : wl.count;
-        LbvhBox bx4[4];  // the node's 64 child boxes, all four loads in flight at once
+      walk_tree<false>(
+          levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
+          // every box beyond the gate goes: nothing is counted here
+          [&](const LbvhBox &bx, int32_t, int) { return !beyond_gate(box_min_dist2(bx, q), tau2); },
+          [&](int32_t b, bool has_b) {
+            LbvhPoint p;
+            float d2;
+            const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
+            unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
+            if (pm) {
+              const uint32_t key_d = __float_as_uint(knn_sqrt(d2));
+              const uint32_t key_l = ((pm >> lane) & 1ull) ? first_level(p, q, q_r0, level) : 0u;
+              const uint32_t key_i = (uint32_t)p.id;
+              do {
+                const uint32_t pending_mine = (uint32_t)(pm >> (team * 16)) & 0xffffu;
+                const bool has = pending_mine != 0u;
+                const int src = (team << 4) + (has ? __ffs((int)pending_mine) - 1 : 0);
+                const uint32_t cd = t_lane_read(key_d, src), cl = t_lane_read(key_l, src), ci = t_lane_read(key_i, src);
+                const uint64_t chi = ((uint64_t)cd << 32) | cl;
+                const uint32_t lane0 = tl == 0 ? 0xffffffffu : 0u;
+                uint32_t nd_[NREG], nl_[NREG], ni_[NREG];
 #pragma unroll
-        for (int chunk = 0; chunk < 4; chunk++) {
-          const int32_t c = first_child + 16 * chunk + tl;
-          bx4[chunk] = LbvhBox{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-          if (work && c < nchild) bx4[chunk] = wl.boxes[c];
-        }
-#pragma unroll
-        for (int chunk = 0; chunk < 4; chunk++) {
-          const int32_t c = first_child + 16 * chunk + tl;
-          const bool valid = work && c < nchild;
-          const LbvhBox bx = bx4[chunk];
-          const bool ov = valid & (bx.lo[0] <= q.x + rl) & (bx.hi[0] >= q.x - rl) & (bx.lo[1] <= q.y + rl) &
-                          (bx.hi[1] >= q.y - rl) & (bx.lo[2] <= q.z + rl) & (bx.hi[2] >= q.z - rl);
-          // beyond the gate: nothing in the box can be listed (0.999995: roundings of m2 and of the
-          // points' distance arithmetic, as in team_walk_kernel)
-          const float gx = fmaxf(fmaxf(bx.lo[0] - q.x, q.x - bx.hi[0]), 0.f), gy = fmaxf(fmaxf(bx.lo[1] - q.y, q.y - bx.hi[1]), 0.f),
-                      gz = fmaxf(fmaxf(bx.lo[2] - q.z, q.z - bx.hi[2]), 0.f);
-          const float m2 = (gx * gx + gy * gy) + gz * gz;
-          const bool keep = ov && !(m2 * 0.999995f > tau2);
-          const uint32_t keep_mine = (uint32_t)(__ballot(keep) >> (team * 16)) & 0xffffu;
-          if (lvl > 0) {
-            if (sp + __popc(keep_mine) > kFixStack) {
-              overflow = true;
-            } else {
-              if (keep) stack[sp + __popc(keep_mine & ((1u << tl) - 1u))] = (lvl << 26) | c;
-              sp += __popc(keep_mine);
-            }
-          } else {
-            uint32_t todo = keep_mine;
-            while (__ballot(todo != 0u) != 0ull) {
-              const bool has_b = todo != 0u;
-              const int32_t b = first_child + 16 * chunk + (has_b ? __ffs((int)todo) - 1 : 0);
-              todo &= todo - 1u;
-              LbvhPoint p = {__uint_as_float(0x7fc00000u), 0.f, 0.f, -1};
-              if (has_b) p = tv.points[(int64_t)b * LBVH_BLOCK + tl];
-              const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-              const float t = has_b ? fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz)) : __uint_as_float(0x7fc00000u);
-              unsigned long long in_m = __ballot(t <= in_below);
-              const unsigned long long maybe_m = __ballot(t <= in_upto) & ~in_m;
-              if (maybe_m) in_m |= maybe_m & __ballot(knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z));
-              const float d2 = t_dist2(dx, dy, dz);
-              unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
-              if (pm) {
-                const uint32_t key_d = __float_as_uint(knn_sqrt(d2));
-                const uint32_t key_l = ((pm >> lane) & 1ull) ? first_level(p) : 0u;
-                const uint32_t key_i = (uint32_t)p.id;
-                do {
-                  const uint32_t pending_mine = (uint32_t)(pm >> (team * 16)) & 0xffffu;
-                  const bool has = pending_mine != 0u;
-                  const int src = (team << 4) + (has ? __ffs((int)pending_mine) - 1 : 0);
-                  const uint32_t cd = t_lane_read(key_d, src), cl = t_lane_read(key_l, src), ci = t_lane_read(key_i, src);
-                  const uint64_t chi = ((uint64_t)cd << 32) | cl;
-                  const uint32_t lane0 = tl == 0 ? 0xffffffffu : 0u;
-                  uint32_t nd_[NREG], nl_[NREG], ni_[NREG];
-#pragma unroll
-                  for (int j = 0; j < NREG; j++) {
-                    uint32_t pd = t_team_shr1(bd[j]), pl = t_team_shr1(bl[j]), pi = t_team_shr1(bi[j]);
-                    if (j > 0) {
-                      pd |= t_dpp<0x121>(bd[j - 1]) & lane0;
-                      pl |= t_dpp<0x121>(bl[j - 1]) & lane0;
-                      pi |= t_dpp<0x121>(bi[j - 1]) & lane0;
-                    }
-                    const uint64_t cur_hi = ((uint64_t)bd[j] << 32) | bl[j], prev_hi = ((uint64_t)pd << 32) | pl;
-                    const bool below_cur = (chi < cur_hi) | ((chi == cur_hi) & (ci < bi[j]));
-                    const bool below_prev = (chi < prev_hi) | ((chi == prev_hi) & (ci < pi));
-                    const bool take_prev = has & ((j > 0) | (tl != 0)) & below_prev;  // entry 0 has no entry before it
-                    const bool take_c = has & below_cur;
-                    nd_[j] = take_prev ? pd : (take_c ? cd : bd[j]);
-                    nl_[j] = take_prev ? pl : (take_c ? cl : bl[j]);
-                    ni_[j] = take_prev ? pi : (take_c ? ci : bi[j]);
+                for (int j = 0; j < NREG; j++) {
+                  uint32_t pd = t_team_shr1(bd[j]), pl = t_team_shr1(bl[j]), pi = t_team_shr1(bi[j]);
+                  if (j > 0) {
+                    pd |= t_dpp<0x121>(bd[j - 1]) & lane0;
+                    pl |= t_dpp<0x121>(bl[j - 1]) & lane0;
+                    pi |= t_dpp<0x121>(bi[j - 1]) & lane0;
                   }
+                  const uint64_t cur_hi = ((uint64_t)bd[j] << 32) | bl[j], prev_hi = ((uint64_t)pd << 32) | pl;
+                  const bool below_cur = (chi < cur_hi) | ((chi == cur_hi) & (ci < bi[j]));
+                  const bool below_prev = (chi < prev_hi) | ((chi == prev_hi) & (ci < pi));
+                  const bool take_prev = has & ((j > 0) | (tl != 0)) & below_prev;  // entry 0 has no entry before it
+                  const bool take_c = has & below_cur;
+                  nd_[j] = take_prev ? pd : (take_c ? cd : bd[j]);
+                  nl_[j] = take_prev ? pl : (take_c ? cl : bl[j]);
+                  ni_[j] = take_prev ? pi : (take_c ? ci : bi[j]);
+                }
 #pragma unroll
-                  for (int j = 0; j < NREG; j++) {
-                    bd[j] = nd_[j];
-                    bl[j] = nl_[j];
-                    bi[j] = ni_[j];
-                  }
-                  pm &= ~__ballot(lane == src);
-                } while (pm);
-                tau2 = fminf(tau2, knn_gate_from_worst(kth_dist()));
-              }
+                for (int j = 0; j < NREG; j++) {
+                  bd[j] = nd_[j];
+                  bl[j] = nl_[j];
+                  bi[j] = ni_[j];
+                }
+                pm &= ~__ballot(lane == src);
+              } while (pm);
+              tau2 = fminf(tau2, knn_gate_from_worst(t_kth_dist<NREG>(bd, a.k, team)));
             }
-          }
-        }
-        t_wave_sync();
-      }
+          },
+          [] {}, overflow);
     }
     if (active && overflow) {
       failed += tl == 0 ? 1u : 0u;  // the row keeps its (dist, index) order; reported in tknnSolveInfo.tie_rows_left
@@ -1798,28 +1578,16 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
   BigKey *my_cand = cand_mem + team * kCandCapacity;
   uint32_t *my_cmax = cmax_mem + team * kBigMaxChunks;
   BigKey *my_list = lists + ((size_t)blockIdx.x * 4 + (size_t)team) * (size_t)chunks * 16;
-  if (lane < 2 * LBVH_WIDE_LEVELS) {
-    const int t = lane / LBVH_WIDE_LEVELS, l = lane % LBVH_WIDE_LEVELS;
-    levels[t][l].boxes = a.wide[t].level[l];
-    levels[t][l].count = a.wide[t].count[l];
-  }
+  walk_fill_levels<2>(levels[0], a.wide, lane);
   t_wave_sync();
   const int32_t n = a.bvh.n;
   const int kc = (a.k - 1) >> 4;  // the chunk of the k-th entry
   unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
   unsigned int unfinished = 0, failed = 0;
   int max_level = 0;
-  int turn_next = 0, turn_left = 0;  // (as in team_walk_kernel)
+  int turn_next = 0, turn_left = 0;  // (t_next_slots)
   for (;;) {
-    if (turn_left == 0) {
-      int got = 0;
-      if (lane == 0) got = (int)atomicAdd(&a.counters[0], 4ull * (unsigned long long)max(a.grab, 1));
-      turn_next = __builtin_amdgcn_readfirstlane(got);
-      turn_left = max(a.grab, 1);
-    }
-    const int base = turn_next;
-    turn_next += 4;
-    turn_left--;
+    const int base = t_next_slots(&a.counters[0], a.grab, lane, turn_next, turn_left);
     if (base >= n) break;
     const int32_t slot = min(base + team, n - 1);
     bool has_q = base + team < n;
@@ -1840,9 +1608,7 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
     while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
       const bool select_on = again || level >= a.first_step || prev_others * 5u >= (uint32_t)a.k;
       const unsigned long long select_m = __ballot(select_on);
-      const float mg = (fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fabsf(q.z)) + 2.0f * r) * 4.76837158203125e-07f;  // 2^-21
-      const float in_below = r - mg, in_upto = r + mg;
-      const float rl = r + 2.0f * mg, rs = r - 2.0f * mg;
+      const WalkBox qb(q, r);
       uint32_t part = 0;       // my lane's share of the candidate count of this level
       uint32_t n_list = 0;     // keys in my team's list (the same in its lanes)
       uint32_t kth_bits = 0x7f7fffffu;  // distance of the list's k-th entry (FLT_MAX: not that many yet)
@@ -1851,15 +1617,6 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
       float tau2 = 3.402823466e+38f;
       bool overflow = false;
       uint32_t fill_n = 0;
-      // key word between distance and index: the level at which the candidate was first one (the box test is monotone in r)
-      auto first_level = [&](const LbvhPoint &p) -> uint32_t {
-        float rr = q_r0;
-        for (int l = 0; l < level; l++) {
-          if (knn_in_box(p.x, p.y, p.z, rr, q.x, q.y, q.z)) return (uint32_t)l;
-          rr = rr * 2.0f;
-        }
-        return (uint32_t)level;
-      };
       auto merge_buffer = [&]() {
         t_wave_sync();
 #pragma unroll 1
@@ -1915,92 +1672,26 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
         const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
         if (tv.n <= 0 || wv.levels <= 0) continue;
         const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-        int sp = 0;
-        if (active) {
-          if (tl == 0) stack[0] = (wv.levels << 26) | 0;  // virtual root above the top level
-          sp = 1;
-        }
-        t_wave_sync();
-        while (__ballot(sp > 0) != 0ull) {
-          const bool work = sp > 0;
-          const int32_t e = work ? stack[sp - 1] : (1 << 26);
-          if (work) sp--;
-          const int lvl = (e >> 26) - 1;  // level of the children
-          const int32_t first_child = (e & 0x3ffffff) * 64;
-          const WalkLevel wl = levels[tree][lvl];
-          const int32_t nchild = lvl == wv.levels - 1 ? (first_child == 0 ? wl.count : 0) : wl.count;
-          LbvhBox bx4[4];
-#pragma unroll
-          for (int chunk = 0; chunk < 4; chunk++) {
-            const int32_t c = first_child + 16 * chunk + tl;
-            bx4[chunk] = LbvhBox{{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-            if (work && c < nchild) bx4[chunk] = wl.boxes[c];
-          }
-#pragma unroll 1
-          for (int chunk = 0; chunk < 4; chunk++) {  // (not unrolled: the merge below is large; the box by selects, not by an index)
-            const int32_t c = first_child + 16 * chunk + tl;
-            const bool valid = work && c < nchild;
-            LbvhBox bx = bx4[0];
-#pragma unroll
-            for (int u = 1; u < 4; u++)
-              if (chunk == u) bx = bx4[u];
-            const bool ov = valid & (bx.lo[0] <= q.x + rl) & (bx.hi[0] >= q.x - rl) & (bx.lo[1] <= q.y + rl) &
-                            (bx.hi[1] >= q.y - rl) & (bx.lo[2] <= q.z + rl) & (bx.hi[2] >= q.z - rl);
-            node_tests += valid ? 1u : 0u;
-            bool counted = false;  // inside the certain part of my box and beyond the gate: count, do not walk (team_walk_kernel)
-            if (ov) {
-              const bool inside = (bx.lo[0] >= q.x - rs) & (bx.hi[0] <= q.x + rs) & (bx.lo[1] >= q.y - rs) &
-                                  (bx.hi[1] <= q.y + rs) & (bx.lo[2] >= q.z - rs) & (bx.hi[2] <= q.z + rs);
-              if (inside) {
-                const float gx = fmaxf(fmaxf(bx.lo[0] - q.x, q.x - bx.hi[0]), 0.f), gy = fmaxf(fmaxf(bx.lo[1] - q.y, q.y - bx.hi[1]), 0.f),
-                            gz = fmaxf(fmaxf(bx.lo[2] - q.z, q.z - bx.hi[2]), 0.f);
-                const float m2 = (gx * gx + gy * gy) + gz * gz;
-                const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
-                const int64_t first = (int64_t)c * span;
-                if (m2 * 0.999995f > tau2 && first + span <= (int64_t)clean_end) {
-                  part += (uint32_t)span;
-                  counted = true;
-                }
+        // (the chunk loop of a node is not unrolled: the merge is large)
+        walk_tree<true>(
+            levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
+            [&](const LbvhBox &bx, int32_t c, int lvl) { return !walk_count_box(bx, q, qb, tau2, c, lvl, clean_end, part); },
+            [&](int32_t b, bool has_b) {
+              LbvhPoint p;
+              float d2;
+              const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
+              point_tests += has_b ? 1u : 0u;
+              part = t_count(part, in_m);
+              const unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2) & select_m;
+              if (pm) {
+                const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
+                if ((mine16 >> tl) & 1u)
+                  my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = BigKey{__float_as_uint(d2), first_level(p, q, q_r0, level), (uint32_t)p.id, 0u};
+                fill_n += __popc(mine16);
+                if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
               }
-            }
-            const bool keep = ov && !counted;
-            const uint32_t keep_mine = (uint32_t)(__ballot(keep) >> (team * 16)) & 0xffffu;
-            if (lvl > 0) {
-              if (sp + __popc(keep_mine) > kWalkStack) {
-                overflow = true;
-              } else {
-                if (keep) stack[sp + __popc(keep_mine & ((1u << tl) - 1u))] = (lvl << 26) | c;
-                sp += __popc(keep_mine);
-              }
-            } else {
-              uint32_t todo = keep_mine;
-              while (__ballot(todo != 0u) != 0ull) {
-                const bool has_b = todo != 0u;
-                const int32_t b = first_child + 16 * chunk + (has_b ? __ffs((int)todo) - 1 : 0);
-                todo &= todo - 1u;
-                LbvhPoint p = {__uint_as_float(0x7fc00000u), 0.f, 0.f, -1};
-                if (has_b) p = tv.points[(int64_t)b * LBVH_BLOCK + tl];
-                point_tests += has_b ? 1u : 0u;
-                const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-                const float t = has_b ? fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz)) : __uint_as_float(0x7fc00000u);
-                unsigned long long in_m = __ballot(t <= in_below);
-                const unsigned long long maybe_m = __ballot(t <= in_upto) & ~in_m;
-                if (maybe_m) in_m |= maybe_m & __ballot(knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z));
-                part = t_count(part, in_m);
-                const float d2 = t_dist2(dx, dy, dz);
-                const unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2) & select_m;
-                if (pm) {
-                  const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
-                  if ((mine16 >> tl) & 1u)
-                    my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = BigKey{__float_as_uint(d2), first_level(p), (uint32_t)p.id, 0u};
-                  fill_n += __popc(mine16);
-                  if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
-                }
-              }
-            }
-          }
-          t_wave_sync();
-        }
+            },
+            [] {}, overflow);
       }
       if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
       // ---- the level's outcome, per team ----
@@ -2022,20 +1713,8 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
             const int en = 16 * j + tl;
             if (en >= a.k) continue;
             const BigKey ky = my_list[(size_t)j * 16 + tl];
-            const int64_t o = (int64_t)row * a.k + en;
             const int32_t prim = (ky.d == 0x7f7fffffu && ky.i == 0u) ? -1 : (int32_t)ky.i;
-            const float d = __uint_as_float(ky.d);
-            if (a.out_idx) a.out_idx[o] = prim;
-            if (a.out_dist) a.out_dist[o] = d;
-            if (a.out_fb) {
-              tknnNeigh ev;
-              ev.ind = prim;
-              ev.dist = d;
-              ev.numNeighbors = en == 0 ? 0 : a.k;
-              ev.pad_ = 0;
-              ev.intersections = en == 0 ? isect : 0;
-              a.out_fb[o] = ev;
-            }
+            t_write_entry(a.out_idx, a.out_dist, a.out_fb, (int64_t)row * a.k + en, prim, __uint_as_float(ky.d), en, a.k, isect);
           }
           if (tl == 0) {
             if (a.out_isect) a.out_isect[row] = isect;
@@ -2061,20 +1740,10 @@ __global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(Te
       }
     }
   }
-  const unsigned long long isum = t_wave_sum(isect_sum), lsum = t_wave_sum(levels_sum), nt = t_wave_sum(node_tests),
-                           pt = t_wave_sum(point_tests) * LBVH_BLOCK / 16, usum = t_wave_sum((unsigned long long)unfinished),
-                           fsum = t_wave_sum((unsigned long long)failed);
-  const int ml = (int)t_wave_max((float)max_level);
-  if (lane == 0) {
-    unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
-    atomicMax(&st[1], (unsigned long long)ml);
-    atomicAdd(&st[2], nt);
-    atomicAdd(&st[3], pt);
-    atomicAdd(&st[4], isum);
-    atomicAdd(&st[6], lsum);
-    if (usum) atomicAdd(&st[7], usum);
-    if (fsum) atomicAdd(&st[8], fsum);
-  }
+  unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
+  t_add_stats(st, lane, max_level, node_tests, point_tests, isect_sum, levels_sum, unfinished);
+  const unsigned long long fsum = t_wave_sum((unsigned long long)failed);
+  if (lane == 0 && fsum) atomicAdd(&st[8], fsum);
 }
 
 }  // namespace

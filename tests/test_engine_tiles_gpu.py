@@ -5,6 +5,11 @@ tknnSolveEx -- on point sets with exact fp32 distance ties, where the tie pass d
 Expected values: rows from oracle.trueknn on the global set G (ids = positions in G: the replay's tie order by index is the
 order by id), per-query levels from oracle.trueknn_numpy, per-query start radii from oracle.trueknn_per_query.  The sets and
 layouts are tests/tile_sets.py's; tests/test_tile_expectations.py checks these expectations on the CPU."""
+import os
+import re
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -13,7 +18,7 @@ import tile_sets
 from oracle.trueknn_numpy import trueknn_numpy
 from owlraytracing_amd import _lib
 
-from conftest import assert_rows_equal
+from conftest import ROOT, assert_rows_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +148,10 @@ def test_large_ids(engines, k, kernel, offset):
 def test_tile_with_halo(engines, k, kernel):
     """(c) the tile on one side of a plane in shuffled order (ids = positions in G, not monotone), the complement as the
     halo tree, phase 0: every row is the global replay's."""
+    _tile_with_halo(engines, k, kernel)
+
+
+def _tile_with_halo(engines, k, kernel):
     for name in _sets(k):
         xyz, r0, ref = _replay(name, k)
         eng = engines(name, "split")
@@ -155,6 +164,73 @@ def test_tile_with_halo(engines, k, kernel):
         what = "%s k=%d %s halo" % (name, k, kernel)
         _check_rows(r, ref, own, what)
         _check_ties(r, ref, k, what)
+
+
+@pytest.mark.parametrize("k", [48, 64])
+def test_tile_with_halo_through_the_team_walk_alone(engines, monkeypatch, k):
+    """(c) once more with TKNN_TEAM_WALK_ALL=1: no packet kernel, every query of the tile walks both trees from level 0
+    (the engine picks the walk's halo instantiation from the halo tree being set), four list registers per lane -- k = 64
+    fills the list, k = 48 does not."""
+    monkeypatch.setenv("TKNN_TEAM_WALK_ALL", "1")
+    _tile_with_halo(engines, k, "team")
+
+
+_TAIL_KS = (5, 17)
+_TAIL_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import tile_sets
+from owlraytracing_amd import _lib
+from owlraytracing_amd.trueknn import TrueKNN
+xyz, r0 = tile_sets.clustered()
+own, rest = tile_sets.split(xyz)
+eng = TrueKNN()
+eng.build(xyz[own], own)
+eng.set_halo(xyz[rest], rest)
+out = {}
+for k in %r:
+    print("solve k=%%d" %% k, file=sys.stderr, flush=True)
+    r = eng.solve(k, r0, kernel=_lib.KERNEL_TEAM)
+    for name in ("idx", "dist", "intersections"):
+        out["%%s_%%d" %% (name, k)] = r[name].cpu().numpy()
+    out["ties_%%d" %% k] = np.int64([r["info"]["tie_rows"], r["info"]["tie_rows_left"]])
+eng.close()
+np.savez(sys.argv[1], **out)
+"""
+
+
+@pytest.fixture(scope="module")
+def walk_tail(tmp_path_factory):
+    """The clustered set split by a plane, tile plus halo, solved in ONE child process with TKNN_TEAM_TAIL=walk and
+    TKNN_VERBOSE=1 for every k of _TAIL_KS: (the child's stderr per k, its rows)."""
+    path = str(tmp_path_factory.mktemp("walk_tail") / "rows.npz")
+    env = dict(os.environ, TKNN_TEAM_TAIL="walk", TKNN_VERBOSE="1")
+    p = subprocess.run([sys.executable, "-c", _TAIL_CHILD % (ROOT, os.path.join(ROOT, "tests"), _TAIL_KS), path], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    said = {int(part.split(None, 1)[0]): part for part in p.stderr.split("solve k=")[1:]}
+    return said, np.load(path)
+
+
+@pytest.mark.parametrize("k", _TAIL_KS)
+def test_tile_with_halo_handed_over_to_the_team_walk(walk_tail, k):
+    """(c) with a tail: the clustered set at a start radius far too large for its cores, so that the packet kernel hands
+    its queries over, and the team walk (TKNN_TEAM_TAIL=walk; one and two list registers per lane) finishes them over both
+    trees.  The engine says so (TKNN_VERBOSE), else the case would pass without the walk."""
+    said, rows = walk_tail
+    m = re.search(r"\[team\] (\d+) of \d+ queries handed over .* team walk ", said[k])
+    assert m and int(m.group(1)) > 0, said[k]
+    xyz, r0 = tile_sets.clustered()
+    own, rest = tile_sets.split(xyz)
+    assert len(own) > 0 and len(rest) > 0
+    ref = oracle.trueknn(xyz, k, r0)
+    assert ref["rounds"] >= 3
+    r = {name: rows["%s_%d" % (name, k)] for name in ("idx", "dist", "intersections")}
+    r["info"] = {"tie_rows": int(rows["ties_%d" % k][0]), "tie_rows_left": int(rows["ties_%d" % k][1])}
+    what = "clustered k=%d team walk tail, halo" % k
+    _check_rows(r, ref, own, what)
+    _check_ties(r, ref, k, what)
 
 
 def _sentinel(dev, n, k):

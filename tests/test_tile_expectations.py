@@ -108,3 +108,17 @@ def test_halo_boxes_contain_every_candidate_up_to_the_cap():
         assert reach.any()
         assert np.isin(rest[reach.any(axis=0)], lay["near"]).all()
         assert lay["boundary"][reach.any(axis=1)].all()
+
+
+@pytest.mark.parametrize("k", [5, 17, 50, 64])
+def test_clustered_set_needs_levels_and_carries_ties(k):
+    """The clustered set the GPU tests hand over to the team walk: several levels, exact-distance ties in the rows of
+    both sides of the split, neither side empty."""
+    xyz, r0 = tile_sets.clustered()
+    own, rest = tile_sets.split(xyz)
+    assert len(own) > 0 and len(rest) > 0 and len(own) + len(rest) == len(xyz)
+    ref = oracle.trueknn(xyz, k, r0)
+    assert ref["rounds"] >= 3
+    for side in (own, rest):
+        d = ref["dist"][side]
+        assert (d[:, 1:] == d[:, :-1]).any()

@@ -6,7 +6,7 @@ import oracle
 from owlraytracing_amd import _lib, datasets
 
 from conftest import assert_rows_equal, assert_rows_match
-from tile_sets import lattice as _lattice
+from tile_sets import clustered as _clustered, lattice as _lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -168,6 +168,25 @@ def test_team_kernel_tails_agree_when_everything_is_handed_over(monkeypatch, tai
     eng = _engine()
     eng.build(xyz)
     r = eng.solve(k, 0.002, kernel=_lib.KERNEL_TEAM)
+    assert r["info"]["rounds"] == ref["rounds"] and ref["rounds"] >= 3  # the sparse fringe needs more levels
+    assert np.array_equal(r["intersections"].cpu().numpy(), ref["intersections"])
+    assert np.array_equal(r["idx"].cpu().numpy(), ref["idx"])
+    assert np.array_equal(r["dist"].cpu().numpy().view(np.int32), ref["dist"].view(np.int32))
+    assert r["info"]["total_intersections"] == int(ref["intersections"].sum())
+    eng.close()
+
+
+@pytest.mark.parametrize("k", [50, 64])
+def test_team_walk_alone_with_four_list_registers(monkeypatch, k):
+    """TKNN_TEAM_WALK_ALL=1: no packet kernel, every query goes through the team walk from level 0 with four list registers
+    per lane -- k = 64 fills the list, k = 50 does not.  The clustered set of the test above at 8 000 points."""
+    monkeypatch.setenv("TKNN_TEAM_WALK_ALL", "1")
+    xyz, r0 = _clustered(8_000)
+    ref = oracle.trueknn(xyz, k, r0)
+    assert (ref["dist"][:, 1:] == ref["dist"][:, :-1]).any()
+    eng = _engine()
+    eng.build(xyz)
+    r = eng.solve(k, r0, kernel=_lib.KERNEL_TEAM)
     assert r["info"]["rounds"] == ref["rounds"] and ref["rounds"] >= 3  # the sparse fringe needs more levels
     assert np.array_equal(r["intersections"].cpu().numpy(), ref["intersections"])
     assert np.array_equal(r["idx"].cpu().numpy(), ref["idx"])

@@ -52,6 +52,15 @@ def tie_set(name):
     raise KeyError(name)
 
 
+def clustered(n=8000):
+    """(G, r0): three tight Gaussian clusters, every seventh point a copy of its neighbour, and a start radius far too large
+    for the density of the cluster cores -- the packet kernel's lists overflow and its queries are handed over to a tail;
+    the sparse fringe needs several levels."""
+    xyz = datasets.gaussian_mixture3d(n, components=3, sigma=0.004, seed=13)
+    xyz[::7] = xyz[1::7][: len(xyz[::7])]  # duplicates
+    return xyz, 0.002
+
+
 def relabel(n, seed=0):
     """perm: local row i of the relabelled layout holds G[perm[i]] with id perm[i]."""
     return np.random.default_rng(500 + seed).permutation(n).astype(np.int32)
