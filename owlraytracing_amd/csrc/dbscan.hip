@@ -24,14 +24,15 @@
 // neighbour counts use the same node tests (a node inside the sphere is counted, not walked).
 // Union-find reads/writes go through agent-scope atomics: a workgroup's L1 (and another XCD's L2)
 // would otherwise keep serving a stale parent and a failed CAS could retry forever.
+#include "db_workspace.h"
 #include "trueknn_engine.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <vector>
-
+#include <climits>
 #include <cstring>
+#include <vector>
 
 #ifndef TKNN_DIAG_BUILD
 #define TKNN_DIAG_BUILD 0  // make DIAG=1 -> libowl_mi355x_diag.so: TKNN_DB_DIAG switches parts of the union pass off (times only)
@@ -39,8 +40,6 @@
 
 namespace owlmi {
 namespace {
-
-constexpr int kDbBlock = 256;
 
 struct DbArgs {
   LbvhView bvh;
@@ -58,8 +57,8 @@ struct DbArgs {
   int32_t *labels;       // per caller index
   const int32_t *next_core;  // per sorted slot (+1 sentinel): first core slot at or after it, n if none
   float eps_in2, eps_out2;   // eps^2 (1 -+ 1e-5): below / above these, fp32 distance arithmetic cannot disagree
-  // work counters, per traversal kernel k (0 core flags, 1 unions, 2 labels / assign): [2k] tree nodes
-  // tested, [2k + 1] points whose distance to a query was computed (12 algorithmic bytes each)
+  // work counters, per traversal kernel (kDbStatCore, kDbStatUnion, kDbStatLabel: knn_device.h): tree nodes
+  // tested, then points whose distance to a query was computed (12 algorithmic bytes each)
   unsigned long long *stats;
   int32_t *group_of;  // per sorted slot, written by the core-flag kernel (see db_group_kernel); null: not wanted
   int32_t *near_node;  // per sorted slot, or null: the node a few levels above the point's group (written by the core-flag kernel for the noise probe)
@@ -79,14 +78,10 @@ struct DbArgs {
 };
 
 // a workgroup's counts into the kernel's two counters: wave sums, one LDS atomic per wave, one global
-// atomic per workgroup (every thread of the workgroup must call it).  `stats` = a.stats + 2 * (which kernel): the counters
-// are kept in 32 stripes of 8 words, a workgroup adds to the stripe of its index, the host sums them.
-constexpr int kDbStripes = 32;
-// the group-union kernel's per-XCD packet cursors: a cache line each (side by side their atomics -- one per packet, its answer
-// awaited, and up to eight per wave that finds the lists used up -- queue at one place: trueknn_team.hip, kXcdCounter)
-constexpr int kDbCursorStride = 32;
+// atomic per workgroup (every thread of the workgroup must call it).  `stats` = a.stats + the kernel's kDbStat.. word: the
+// counters are kept in kDbStripes stripes, a workgroup adds to the stripe of its index, the host sums them (knn_device.h).
 __device__ __forceinline__ void db_add_stats(unsigned long long *stats, unsigned long long *blk, uint32_t nodes, uint32_t points) {
-  stats += (blockIdx.x & (kDbStripes - 1)) * 8;
+  stats += (blockIdx.x & (kDbStripes - 1)) * kDbStripeWords;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     nodes += __shfl_xor(nodes, off);
@@ -105,7 +100,7 @@ __device__ __forceinline__ void db_add_stats(unsigned long long *stats, unsigned
 
 // the same for a kernel whose waves are independent and whose LDS is counted in waves per CU: one global atomic per wave
 __device__ __forceinline__ void db_add_stats_wave(unsigned long long *stats, uint32_t nodes, uint32_t points) {
-  stats += ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (kDbStripes - 1)) * 8;
+  stats += ((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (kDbStripes - 1)) * kDbStripeWords;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     nodes += __shfl_xor(nodes, off);
@@ -381,7 +376,7 @@ __global__ void __launch_bounds__(kDbBlock) db_core_kernel(DbArgs a, int32_t *bl
     const unsigned long long m = __ballot(t < a.bvh.n && a.core_sorted[t] != 0);
     if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(m);
   }
-  db_add_stats(a.stats + 0, blk_stats, node_tests, point_tests);  // (a barrier inside)
+  db_add_stats(a.stats + kDbStatCore, blk_stats, node_tests, point_tests);  // (a barrier inside)
   if (block_count && threadIdx.x == 0) {
     int32_t total = 0;
     for (int w = 0; w < kDbBlock / 64; w++) total += wave_count[w];
@@ -389,34 +384,13 @@ __global__ void __launch_bounds__(kDbBlock) db_core_kernel(DbArgs a, int32_t *bl
   }
 }
 
-// next_core[s] = first core slot >= s (n if none): with rank[s] = number of core slots before s (an
-// exclusive sum of the flags) and pos[r] = slot of the r-th core point, next_core[s] = pos[rank[s]]
-// (the flags are summed as they are read: one byte per slot in, one word out)
-struct DbFlagOf {
-  __host__ __device__ int32_t operator()(uint8_t c) const { return c; }
-};
-typedef hipcub::TransformInputIterator<int32_t, DbFlagOf, const uint8_t *> DbFlagIter;
+// next_core[s] = first core slot >= s (n if none): with rank[s] = number of core slots before s and pos[r] = slot of the
+// r-th core point, next_core[s] = pos[rank[s]].  No rank per slot is kept (a library sum over the n flags took 0.05 ms and a
+// 40 MB array was written once and read twice): a count of the core flags per workgroup of 256 slots (db_core_kernel, or
+// db_flag_count_kernel), a sum over those n / 256 counts, and the two kernels below find a slot's rank as its workgroup's place
+// + the core slots before it in the workgroup.
 // (and, if asked: the slots that are NOT core, listed in slot order for the label pass -- slot t is the (t - rank[t])-th of
 // them, no atomics -- with their number)
-__global__ void __launch_bounds__(kDbBlock) db_core_pos_kernel(DbArgs a, const int32_t *rank, int32_t *pos, int32_t *others,
-                                                               unsigned long long *n_others) {
-  const int32_t t = blockIdx.x * kDbBlock + threadIdx.x;
-  if (t >= a.bvh.n) return;
-  const int32_t r = rank[t];
-  const bool is_core = a.core_sorted[t] != 0;
-  if (is_core)
-    pos[r] = t;
-  else if (others)
-    others[t - r] = t;
-  if (t == a.bvh.n - 1) {
-    const int32_t n_core = r + (is_core ? 1 : 0);
-    pos[n_core] = 0x7f7f7f7f;  // "none" (clamped by db_next_core_kernel): the one place a slot behind the last core point looks at
-    if (others) *n_others = (unsigned long long)(a.bvh.n - n_core);
-  }
-}
-// The same three steps without a rank per slot (tknnDbscan; a library sum over the n flags took 0.05 ms and a 40 MB array
-// written once and read twice): a count of the core flags per workgroup of 256 slots, a sum over those n / 256 counts, and
-// the two kernels below find a slot's rank as its workgroup's place + the core slots before it in the workgroup.
 __device__ __forceinline__ int32_t db_rank_in_block(bool flag, int32_t block_place, int32_t *wave_count, int32_t &block_total) {
   const unsigned long long m = __ballot(flag);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -465,18 +439,6 @@ __global__ void __launch_bounds__(kDbBlock) db_next_core_blocks_kernel(DbArgs a,
   const int32_t v = pos[r];  // a slot after the last core point has rank = number of core points: pos[] holds "none" there
   next_core[t] = v < a.bvh.n ? v : a.bvh.n;
   if (t == a.bvh.n - 1) next_core[a.bvh.n] = a.bvh.n;
-}
-__global__ void __launch_bounds__(kDbBlock) db_next_core_kernel(DbArgs a, const int32_t *rank, const int32_t *pos,
-                                                                int32_t *next_core) {
-  const int32_t t = blockIdx.x * kDbBlock + threadIdx.x;
-  if (t > a.bvh.n) return;
-  if (t == a.bvh.n) {
-    next_core[t] = a.bvh.n;
-    return;
-  }
-  // a slot after the last core point has rank = number of core points: pos[] holds n there
-  const int32_t v = pos[rank[t]];
-  next_core[t] = v < a.bvh.n ? v : a.bvh.n;
 }
 
 __device__ __forceinline__ void db_union_body(const DbArgs &a, int32_t t, unsigned long long *seen, int kPairs, uint32_t &node_tests,
@@ -548,7 +510,7 @@ __global__ void __launch_bounds__(kDbBlock) db_union_kernel(DbArgs a) {
   uint32_t node_tests = 0, point_tests = 0;
   const int32_t t = blockIdx.x * kDbBlock + threadIdx.x;
   if (t < a.bvh.n && a.core_sorted[t]) db_union_body(a, t, seen, kPairs, node_tests, point_tests);
-  db_add_stats(a.stats + 2, blk_stats, node_tests, point_tests);
+  db_add_stats(a.stats + kDbStatUnion, blk_stats, node_tests, point_tests);
 }
 
 // ---- unions by GROUP: one walk per maximal tight node ------------------------------------------------------------------
@@ -1159,13 +1121,13 @@ __global__ void __launch_bounds__(kDbUnionBlock) __attribute__((amdgpu_waves_per
     atomicAdd(&a.diag_out[13], el), atomicMax(&a.diag_out[14], el), atomicAdd(&a.diag_out[15], 1ull);
   }
 #undef DB_LAP
-  if (a.diag & 8) {  // [6] most walk steps of a wave, [7] their sum
+  if (a.diag & 8) {  // most walk steps of a wave, their sum
     if (lane == 0) {
-      atomicMax(&a.stats[6], (unsigned long long)node_tests);
-      atomicAdd(&a.stats[7], (unsigned long long)node_tests);
+      atomicMax(&a.stats[kDbStatLongestWalk], (unsigned long long)node_tests);
+      atomicAdd(&a.stats[kDbStatWalkSum], (unsigned long long)node_tests);
     }
   }
-  db_add_stats_wave(a.stats + 2, node_tests, point_tests);  // (no LDS words: 16 384 bytes per workgroup are ten workgroups per CU, 16 400 are nine)
+  db_add_stats_wave(a.stats + kDbStatUnion, node_tests, point_tests);  // (no LDS words: 16 384 bytes per workgroup are ten workgroups per CU, 16 400 are nine)
 }
 
 // min_row[root] = min(min_row[root], row).  The value only falls, so a read that finds it at or below `row` settles the matter
@@ -1256,7 +1218,7 @@ __global__ void __launch_bounds__(kDbBlock) db_root_kernel(DbArgs a, int32_t *is
 }
 
 // The points that are not core (few -- BASELINE config 3: 0.13 % --, scattered over the waves, listed in slot order since the
-// core flags were known: db_core_pos_kernel) take the lowest-numbered cluster among their core neighbours.  Finding those
+// core flags were known: db_core_pos_blocks_kernel) take the lowest-numbered cluster among their core neighbours.  Finding those
 // neighbours needs the core flags only, not the clusters: the walks -- chains of dependent loads by a few hundred waves, 0.25 ms
 // on config 3 -- run BESIDE the group unions on a stream of their own and leave, per listed point, the core neighbours they met
 // (one per tight node, db for_each_core_group; a point that is not core has fewer than minPts - 1 of them: `per` - 1 places, and
@@ -1284,7 +1246,7 @@ __global__ void __launch_bounds__(kDbBlock) db_border_walk_kernel(DbArgs a, cons
       mine[0] = cnt <= per - 1 ? cnt : -1;
     }
   }
-  db_add_stats(a.stats + 4, blk_stats, node_tests, point_tests);
+  db_add_stats(a.stats + kDbStatLabel, blk_stats, node_tests, point_tests);
 }
 
 // Labels: core points take their cluster's number (and every point's core flag goes to its row); the listed points take the
@@ -1368,7 +1330,7 @@ __global__ void __launch_bounds__(kDbBlock) db_label_kernel(DbArgs a, const int3
         a.labels[a.bvh.prim_id[t]] = label;
     }
   }
-  db_add_stats(a.stats + 4, blk_stats, node_tests, point_tests);
+  db_add_stats(a.stats + kDbStatLabel, blk_stats, node_tests, point_tests);
 }
 // rows <- slots: four consecutive ROWS per thread; their slots come from the tree's inverse permutation (one 16-byte load), the
 // slots' words are four scattered 4-byte reads of an array the launch before has just written (40 MB at 10 M points: it sits
@@ -1423,7 +1385,7 @@ __global__ void __launch_bounds__(kDbBlock) db_assign_kernel(DbArgs a, const int
     }
     a.labels[row] = best;
   }
-  db_add_stats(a.stats + 4, blk_stats, node_tests, point_tests);
+  db_add_stats(a.stats + kDbStatLabel, blk_stats, node_tests, point_tests);
 }
 
 // ---- "eps auto-grown" (tknnDbscanAuto; spec: oracle/dbscan_oracle.c, dbref_dbscan_auto) ----------------------------
@@ -1485,7 +1447,7 @@ __device__ __forceinline__ bool db_has_core_neighbour(const DbArgs &a, const Lbv
 }
 
 // noise[slot] (per sorted slot): in, unless first_round: 1 = was noise in the round before; out: 1 = is noise now.
-// stats[0..1] += node / point tests, stats[6] += points still noise.
+// stats: kDbStatCore += node / point tests, kDbStatNoise += points still noise.
 __global__ void __launch_bounds__(kDbBlock) db_noise_probe_kernel(DbArgs a, uint8_t *noise, int first_round) {
   __shared__ unsigned long long blk_stats[2], blk_noise[2];
   if (threadIdx.x < 2) blk_stats[threadIdx.x] = blk_noise[threadIdx.x] = 0ull;
@@ -1500,8 +1462,8 @@ __global__ void __launch_bounds__(kDbBlock) db_noise_probe_kernel(DbArgs a, uint
       noise[t] = (uint8_t)still;
     }
   }
-  db_add_stats(a.stats + 0, blk_stats, node_tests, point_tests);
-  db_add_stats(a.stats + 6, blk_noise, still, 0u);
+  db_add_stats(a.stats + kDbStatCore, blk_stats, node_tests, point_tests);
+  db_add_stats(a.stats + kDbStatNoise, blk_noise, still, 0u);
 }
 
 // per-slot flags to the caller's rows
@@ -1553,432 +1515,433 @@ void db_segment_min(const int32_t *d_seg, const int64_t *d_val, int64_t n, int64
   OWLMI_HIP(hipGetLastError());
 }
 
-// the work counters of the launches so far: the stripes to the host (synchronises the stream), summed into h_counters_[0..7]
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+// RT-DBSCAN's environment knobs -- this is the list.  Read at the top of every call (DbCall): tests and measurement scripts
+// switch them between calls.  Not here: TKNN_DB_PER_CU (union workgroups per CU, at most what fits; read once per engine
+// with Engine::db_union_resident_) and the build macros (TKNN_DB_STACK, TKNN_DB_BUF, TKNN_DB_BOXES, TKNN_DB_UNION_BLOCK).
+namespace {
+struct DbKnobs {
+  static int num(const char *name, int otherwise) { return getenv(name) ? atoi(getenv(name)) : otherwise; }
+  static bool is(const char *name, const char *value) { return getenv(name) && std::strcmp(getenv(name), value) == 0; }
+  bool paths = num("TKNN_DB_PATHS", 1) != 0;               // 0: a point's walk down to its group starts at the root (measurements)
+  bool side = num("TKNN_DB_SIDE", 1) != 0;                 // 0: no side stream, the label kernel walks for the points that are not core (measurements)
+  bool uniform = num("TKNN_DB_UNIFORM", 1) != 0;           // 0: the second union pass without the one-set shortcut (measurements)
+  bool per_point = is("TKNN_DBSCAN_UNION", "point");       // the per-point union walk (A/B measurements, tests)
+  bool scatter = is("TKNN_DB_LABEL", "scatter");           // labels straight to the rows instead of by slot and a gather (A/B)
+  int chunk = std::max(1, num("TKNN_DB_CHUNK", 64));       // packets per chunk dealt to an XCD
+  int short_way = num("TKNN_DB_SHORT", 1);                 // 0: the group-union kernel's settle the long way only (measurements)
+  int scan_budget = std::max(0, num("TKNN_DB_SCAN", 12));  // steps a probe's quick scan may take
+  int grid = num("TKNN_DB_GRID", INT_MAX);                 // at most this many workgroups of the group-union kernel (at least 1; measurements)
+  float split = getenv("TKNN_DB_SPLIT") ? (float)atof(getenv("TKNN_DB_SPLIT")) : 0.25f;  // the first union pass takes faces up to this fraction of eps apart; >= 1: one pass
+  int diag = TKNN_DIAG_BUILD ? num("TKNN_DB_DIAG", 0) : 0;  // the diagnostic library only (DbArgs::diag)
+  const char *dump = getenv("TKNN_DB_DUMP");               // <file>: the timed pass's packet records (TKNN_DB_DIAG & 512; scripts/db_packet_stats.py)
+  bool verbose = getenv("TKNN_DB_VERBOSE") != nullptr;     // the traversals' work counters on stderr
+};
+}  // namespace
+
+// the work counters of the launches so far: the stripes to the host (synchronises the stream), summed into h_counters_'s first words
 void Engine::db_read_stats(hipStream_t s) {
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + 16, counters_ + kCounters, kDbStripes * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  OWLMI_HIP(hipMemcpyAsync(h_counters_ + kHostStripes, counters_ + kDbStats, kDbStripes * kDbStripeWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));
-  for (int i = 0; i < 8; i++) {
+  for (int i = 0; i < kDbStripeWords; i++) {
     unsigned long long sum = 0;
-    for (int st = 0; st < kDbStripes; st++) sum += h_counters_[16 + st * 8 + i];
+    for (int st = 0; st < kDbStripes; st++) sum += h_counters_[kHostStripes + st * kDbStripeWords + i];
     h_counters_[i] = sum;
   }
 }
 
-// tknnDbscanNoise: one growth round of the auto-eps loop without the loop -- core flags, then the noise probe of every
-// point that is not core.  Returns the number of noise points; d_noise is indexed by row.
-int64_t Engine::dbscan_noise(float eps, int min_pts, uint8_t *d_noise, hipStream_t s) {
-  const int64_t n = bvh_.size();
-  size_t scan_bytes = 0;
-  OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)n, s));
-  {
-    size_t flag_scan_bytes = 0;
-    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, flag_scan_bytes, DbFlagIter(nullptr, DbFlagOf()), (int32_t *)nullptr, (int)n, s));
-    scan_bytes = std::max(scan_bytes, flag_scan_bytes);
-  }
-  const size_t need = (((size_t)n * (4 + 4 + 4 + 4 + 1 + 1)) + 32 + 255) / 256 * 256;  // as dbscan_auto
-  char *ws = (char *)workspace(need + scan_bytes);
-  DbArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.bvh = bvh_.view();
-  a.block_paths = (getenv("TKNN_DB_PATHS") && atoi(getenv("TKNN_DB_PATHS")) == 0) ? nullptr : bvh_.block_paths_device();  // (0: measurements)
-  a.min_pts = min_pts;
-  a.eps = eps;
-  a.eps_wide = eps * 1.000001f;
-  a.eps_in2 = eps * eps * (1.0f - 1e-5f);
-  a.eps_out2 = eps * eps * (1.0f + 1e-5f);
-  a.parent = nullptr;            // no unions here: the slots' place holds ...
-  a.near_node = (int32_t *)ws;   // ... where each point's noise probe starts (db_has_core_neighbour)
-  int32_t *core_rank = (int32_t *)(ws + (size_t)n * 4);
-  a.rank = (int32_t *)(ws + (size_t)n * 8);                   // n + 1 entries: flags, then positions
-  int32_t *next_core = (int32_t *)(ws + (size_t)n * 12 + 4);  // n + 1 entries
-  a.core_sorted = (uint8_t *)(ws + (size_t)n * 16 + 8);
-  uint8_t *noise = a.core_sorted + n;
-  a.next_core = next_core;
-  a.stats = counters_ + kCounters;  // striped (db_add_stats)
-  void *scan_tmp = ws + need;
-  const unsigned blocks = (unsigned)((n + kDbBlock - 1) / kDbBlock), blocks1 = (unsigned)((n + 1 + kDbBlock - 1) / kDbBlock);
-  OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounterWords * sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(db_core_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, (int32_t *)nullptr);
-  {
-    int32_t *pos = a.rank;
-    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, DbFlagIter(a.core_sorted, DbFlagOf()), core_rank, (int)n, s));
-    hipLaunchKernelGGL(db_core_pos_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_rank, pos, (int32_t *)nullptr, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(db_next_core_kernel, dim3(blocks1), dim3(kDbBlock), 0, s, a, core_rank, pos, next_core);
-  }
-  hipLaunchKernelGGL(db_noise_probe_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, noise, 1);
-  hipLaunchKernelGGL(db_rows_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, noise, d_noise);
-  OWLMI_HIP(hipGetLastError());
-  db_read_stats(s);
-  return (int64_t)h_counters_[6];
-}
-
-void Engine::dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
-                    tknnDbscanInfo *info, hipStream_t s, const int32_t *core_label) {
-  const int64_t n = bvh_.size();
-  // scratch: core flags per slot, parent, root flags, ranks, next_core (+ two sentinels), smallest rows
-  const size_t min_row_at = ((size_t)n * 17 + 8 + 15) / 16 * 16;
-  const size_t block_places_bytes = (((size_t)n / kDbBlock + 2) * 8 + 15) / 16 * 16;
-  const size_t max_packets = (size_t)n / 64 + 1;  // of db_group_union_kernel (their diagnostic records: the diagnostic library only)
-  const size_t need = (min_row_at + (size_t)n * 16 + block_places_bytes + (TKNN_DIAG_BUILD ? max_packets * 16 : 0) + 255) / 256 * 256;  // ... the list of the slots that are not core, their core neighbours
-  size_t scan_bytes = 0;
-  OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)n, s));
-  {
-    size_t flag_scan_bytes = 0;
-    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, flag_scan_bytes, DbFlagIter(nullptr, DbFlagOf()), (int32_t *)nullptr, (int)n, s));
-    scan_bytes = std::max(scan_bytes, flag_scan_bytes);
-  }
-  char *ws = (char *)workspace(need + scan_bytes);
-  DbArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.bvh = bvh_.view();
-  a.block_paths = (getenv("TKNN_DB_PATHS") && atoi(getenv("TKNN_DB_PATHS")) == 0) ? nullptr : bvh_.block_paths_device();  // (0: measurements)
-  a.eps = eps;
-  a.eps_wide = eps * 1.000001f;
-  a.min_pts = min_pts;
-  a.want_counts = d_counts != nullptr;
-  a.keep_core = 0;
-  a.diag = (TKNN_DIAG_BUILD && getenv("TKNN_DB_DIAG")) ? atoi(getenv("TKNN_DB_DIAG")) : 0;  // the diagnostic library only
-  a.parent = (int32_t *)ws;
-  int32_t *is_root = (int32_t *)(ws + (size_t)n * 4);
-  a.rank = (int32_t *)(ws + (size_t)n * 8);  // n + 1 entries
-  int32_t *next_core = (int32_t *)(ws + (size_t)n * 12 + 4);  // n + 1 entries
-  a.core_sorted = (uint8_t *)(ws + (size_t)n * 16 + 8);
-  a.min_row = (int32_t *)(ws + min_row_at);
-  int32_t *not_core = a.min_row + n;  // in slot order; its length in counters_[19]
-  int32_t *uni = not_core + 2 * (size_t)n;  // db_uniform_kernel's per-node sets (behind border_lists)
-  int32_t *block_places = uni + n;          // per workgroup of 256 slots: its listed groups; behind them, their places in the list
-  int32_t *border_lists = not_core + n;  // `border_per` words per listed point, if they fit n words: a count and the core neighbours
-  const int border_per = std::max(2, min_pts);
-  const bool side = !core_label && !(getenv("TKNN_DB_SIDE") && atoi(getenv("TKNN_DB_SIDE")) == 0);  // (0: measurements without the side stream)
-  if (side && !db_side_) {
-    OWLMI_HIP(hipStreamCreateWithFlags(&db_side_, hipStreamNonBlocking));
-    OWLMI_HIP(hipEventCreateWithFlags(&ev_side_a_, hipEventDisableTiming));
-    OWLMI_HIP(hipEventCreateWithFlags(&ev_side_b_, hipEventDisableTiming));
-  }
-  a.next_core = next_core;
-  a.eps_in2 = eps * eps * (1.0f - 1e-5f);
-  a.eps_out2 = eps * eps * (1.0f + 1e-5f);
-  void *scan_tmp = ws + need;
-  a.core = d_core;
-  a.counts = d_counts;
-  a.labels = d_labels;
-  const char *union_env = getenv("TKNN_DBSCAN_UNION");  // "point": the per-point union walk (A/B measurements, tests); read per call
-  const bool per_point = db_force_point_ || (union_env && std::strcmp(union_env, "point") == 0);
-  // every point's group, for the union pass; kept in the caller's label array, which is written last
-  a.group_of = core_label || per_point ? nullptr : d_labels;
-  const unsigned blocks = (unsigned)((n + kDbBlock - 1) / kDbBlock);
-  a.diag_out = counters_ + 20;
-  a.stats = counters_ + kCounters;  // striped (db_add_stats); [0..5]: node / point tests of the three traversal kernels
-  if (db_side_pending_) {
-    // a call that threw between its side launch and its rejoin has left db_border_walk_kernel running on the workspace
-    // and the counters this call is about to reset: nothing of this call before that kernel has ended
-    OWLMI_HIP(hipStreamWaitEvent(s, ev_side_b_, 0));
-    db_side_pending_ = false;
-  }
-  OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounterWords * sizeof(unsigned long long), s));  // ... [19]: length of the label pass's list
+struct Engine::DbCall {
+  Engine &e;
+  const hipStream_t s;
+  const DbKnobs knobs;  // (reads the environment)
+  const int64_t n = e.bvh_.size();
+  const unsigned blocks = (unsigned)((n + kDbBlock - 1) / kDbBlock);  // of a launch over the slots
+  const unsigned blocks_per = (unsigned)(((n + kDbPer - 1) / kDbPer + kDbBlock - 1) / kDbBlock);  // ... kDbPer slots per thread
   const unsigned walk_grid = blocks < 2048u ? blocks : 2048u;  // grid-stride over lists whose lengths only the device knows
-  hipEvent_t e0 = ev_a_, e1 = ev_b_;
-  OWLMI_HIP(hipEventRecord(e0, s));
-  if (core_label) {
-    hipLaunchKernelGGL(db_core_from_labels_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_label);
-  } else {
+  size_t scan_bytes = 0;  // the library's exclusive sum over up to n words: its temporary storage, behind the layout
+  void *ws = nullptr, *scan_tmp = nullptr;
+  DbArgs a, common;  // common: what every call sets, as the constructor leaves it
+
+  // what every call sets
+  DbCall(Engine &engine, int min_pts, hipStream_t stream) : e(engine), s(stream) {
+    std::memset(&a, 0, sizeof a);
+    a.bvh = e.bvh_.view();
+    a.block_paths = knobs.paths ? e.bvh_.block_paths_device() : nullptr;
+    a.stats = e.counters_ + kDbStats;  // striped (db_add_stats)
+    a.min_pts = min_pts;
+    common = a;
+    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)n, s));
+  }
+  void reserve(size_t layout_bytes) {
+    const size_t scan_at = db_round_up(layout_bytes, kDbScanAlign);
+    ws = e.workspace(scan_at + scan_bytes);
+    scan_tmp = db_at<void>(ws, scan_at);
+  }
+  void set_eps(float eps) {
+    a.eps = eps, a.eps_wide = eps * 1.000001f;
+    a.eps_in2 = eps * eps * (1.0f - 1e-5f), a.eps_out2 = eps * eps * (1.0f + 1e-5f);
+  }
+  void reset_counters() { OWLMI_HIP(hipMemsetAsync(e.counters_, 0, kCounterWords * sizeof(unsigned long long), s)); }
+
+  // next_core from a.core_sorted: the core slots of each workgroup (block_places, counted by db_core_kernel; `count`: by a
+  // launch of its own) -> their exclusive sum -> slot of the r-th core point (pos: where a.rank goes later) -> first core
+  // slot at or after each slot; and, if asked, the list of the slots that are not core with its length in counters_[kDbNotCore]
+  int32_t *block_places = nullptr, *next_core = nullptr;  // (a.next_core, to write through)
+  void build_next_core(bool count, int32_t *not_core) {
+    int32_t *pos = a.rank;
+    if (count) hipLaunchKernelGGL(db_flag_count_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places);
+    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, block_places, block_places + blocks, (int)blocks, s));
+    hipLaunchKernelGGL(db_core_pos_blocks_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places + blocks, pos, not_core, e.counters_ + kDbNotCore);
+    hipLaunchKernelGGL(db_next_core_blocks_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places + blocks, pos, next_core);
+  }
+
+  // ---- a growth round: core flags (with a.keep_core, those of the rounds before stand), next_core, the noise probe of
+  // every point that is not core (later rounds: of those that still were noise), the statistics read back.  Returns the
+  // number of noise points; `noise` is per slot.
+  uint8_t *noise = nullptr;
+  void probe_setup() {
+    const DbProbeWs w = DbProbeWs::of((size_t)n);
+    reserve(w.end);
+    // (a.parent stays null: no unions here; near_node: where each point's noise probe starts, db_has_core_neighbour)
+    a.near_node = db_at<int32_t>(ws, w.near_node), a.rank = db_at<int32_t>(ws, w.pos), a.next_core = next_core = db_at<int32_t>(ws, w.next_core);
+    a.core_sorted = db_at<uint8_t>(ws, w.core_sorted), noise = db_at<uint8_t>(ws, w.noise), block_places = db_at<int32_t>(ws, w.block_places);
+  }
+  int64_t probe_round(float eps, bool first_round) {
+    set_eps(eps);
+    reset_counters();
+    hipLaunchKernelGGL(db_core_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places);
+    build_next_core(false, nullptr);
+    hipLaunchKernelGGL(db_noise_probe_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, noise, first_round ? 1 : 0);
+    OWLMI_HIP(hipGetLastError());
+    e.db_read_stats(s);
+    return (int64_t)e.h_counters_[kDbStatNoise];
+  }
+
+  // ---- the full clustering, and the assign step (which shares its first steps)
+  int32_t *roots = nullptr, *not_core = nullptr, *border_lists = nullptr, *uni = nullptr;
+  int border_per = 0;
+  bool side = false, per_point = false, between_passes = false;
+  int union_launches = 1;
+  int32_t last[2] = {0, 0};  // rank and root flag of the last row: their sum is the number of clusters
+
+  // scratch, arguments, the side stream, a clean start of the stream: everything before the first launch
+  void cluster_setup(float eps, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, bool with_side, bool by_point, bool groups_wanted) {
+    const DbClusterWs w = DbClusterWs::of((size_t)n, TKNN_DIAG_BUILD != 0);
+    reserve(w.end);
+    a = common, union_launches = 1, between_passes = false;
+    set_eps(eps);
+    a.want_counts = d_counts != nullptr, a.diag = knobs.diag;
+    a.parent = db_at<int32_t>(ws, w.parent), roots = db_at<int32_t>(ws, w.roots), a.rank = db_at<int32_t>(ws, w.ranks);
+    a.next_core = next_core = db_at<int32_t>(ws, w.next_core), a.core_sorted = db_at<uint8_t>(ws, w.core_sorted);
+    a.min_row = db_at<int32_t>(ws, w.min_row), not_core = db_at<int32_t>(ws, w.not_core), border_lists = db_at<int32_t>(ws, w.border_lists);
+    uni = db_at<int32_t>(ws, w.uni), block_places = db_at<int32_t>(ws, w.block_places);
+    if (TKNN_DIAG_BUILD && (a.diag & 512) && groups_wanted) a.pk_diag = db_at<int32_t>(ws, w.pk_diag);
+    border_per = std::max(2, a.min_pts), side = with_side, per_point = by_point;
+    if (side && !e.db_side_) {
+      OWLMI_HIP(hipStreamCreateWithFlags(&e.db_side_, hipStreamNonBlocking));
+      OWLMI_HIP(hipEventCreateWithFlags(&e.ev_side_a_, hipEventDisableTiming));
+      OWLMI_HIP(hipEventCreateWithFlags(&e.ev_side_b_, hipEventDisableTiming));
+    }
+    a.core = d_core, a.counts = d_counts, a.labels = d_labels;
+    // every point's group, for the union pass; kept in the caller's label array, which is written last
+    a.group_of = groups_wanted ? d_labels : nullptr;
+    a.diag_out = e.counters_ + kDbDiag;
+    if (e.db_side_pending_) {
+      // a call that threw between its side launch and its rejoin has left db_border_walk_kernel running on the workspace
+      // and the counters this call is about to reset: nothing of this call before that kernel has ended
+      OWLMI_HIP(hipStreamWaitEvent(s, e.ev_side_b_, 0));
+      e.db_side_pending_ = false;
+    }
+    reset_counters();
+    OWLMI_HIP(hipEventRecord(e.ev_a_, s));
+  }
+  void core_flags() {
     // the flags BY ROW are written by the label kernel, which scatters to the rows anyway: a one-byte store at the
     // caller's row from this kernel cost a partial sector per point (rocprofv3: 426 MB written for 10 M points)
     DbArgs c = a;
     c.core = nullptr;
     hipLaunchKernelGGL(db_core_kernel, dim3(blocks), dim3(kDbBlock), 0, s, c, block_places);
+    OWLMI_HIP(hipEventRecord(e.ev_c_, s));  // end of the core-flag traversal
   }
-  OWLMI_HIP(hipEventRecord(ev_c_, s));  // end of the core-flag traversal
-  {
-    // next_core: flags -> exclusive sum (rank of a slot among the core slots) -> slot of the r-th core
-    // point -> first core slot at or after each slot.  is_root / rank are free until the unions are done.
-    int32_t *pos = a.rank;
-    if (core_label) hipLaunchKernelGGL(db_flag_count_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places);  // (else: db_core_kernel has counted)
-    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, block_places, block_places + blocks, (int)blocks, s));
-    hipLaunchKernelGGL(db_core_pos_blocks_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places + blocks, pos, core_label ? (int32_t *)nullptr : not_core, counters_ + 19);
-    hipLaunchKernelGGL(db_next_core_blocks_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, block_places + blocks, pos, next_core);
+  // the walks of the points that are not core, on the side stream beside everything up to the label kernel
+  void border_walk() {
+    if (!side) return;
+    OWLMI_HIP(hipEventRecord(e.ev_side_a_, s));
+    OWLMI_HIP(hipStreamWaitEvent(e.db_side_, e.ev_side_a_, 0));
+    hipLaunchKernelGGL(db_border_walk_kernel, dim3(walk_grid), dim3(kDbBlock), 0, e.db_side_, a, not_core, e.counters_ + kDbNotCore, border_lists, border_per, (long long)n);
+    OWLMI_HIP(hipEventRecord(e.ev_side_b_, e.db_side_));
+    e.db_side_pending_ = true;  // (until some stream waits for it: labels(), or the top of the next call if this one throws in between)
   }
-  if (side) {  // the walks of the points that are not core, beside everything up to the label kernel
-    OWLMI_HIP(hipEventRecord(ev_side_a_, s));
-    OWLMI_HIP(hipStreamWaitEvent(db_side_, ev_side_a_, 0));
-    hipLaunchKernelGGL(db_border_walk_kernel, dim3(walk_grid), dim3(kDbBlock), 0, db_side_, a, not_core, counters_ + 19, border_lists, border_per, (long long)n);
-    OWLMI_HIP(hipEventRecord(ev_side_b_, db_side_));
-    db_side_pending_ = true;  // (until some stream waits for it: below, or at the top of the next call if this one throws in between)
-  }
-  if (core_label) {
-    hipLaunchKernelGGL(db_assign_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_label);
-    OWLMI_HIP(hipGetLastError());
-    OWLMI_HIP(hipEventRecord(e1, s));
-    OWLMI_HIP(hipStreamSynchronize(s));
-    db_read_stats(s);
-    if (info) {
-      float ms = 0;
-      OWLMI_HIP(hipEventElapsedTime(&ms, e0, e1));
-      std::memset(info, 0, sizeof *info);
-      info->clusters = -1;
-      info->solve_ms = ms;
-      info->label_ms = ms;
-      info->node_tests = (int64_t)h_counters_[4];
-      info->point_tests = (int64_t)h_counters_[5];
-      info->label_point_tests = (int64_t)h_counters_[5];
-    }
-    return;
-  }
-  int union_launches = 1;
-  bool between_passes = false;  // ev_g_ .. ev_h_: the cursors' reset and db_uniform_kernel, not part of union_ms
-  if (per_point) {
-    OWLMI_HIP(hipEventRecord(ev_d_, s));
+  void unions() {
+    OWLMI_HIP(hipEventRecord(e.ev_d_, s));
     hipLaunchKernelGGL(db_union_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a);
-  } else {
+    OWLMI_HIP(hipEventRecord(e.ev_e_, s));
+    OWLMI_HIP(hipMemsetAsync(a.min_row, 0x7f, (size_t)n * sizeof(int32_t), s));  // 0x7f7f7f7f: above every row (group_unions: db_group_kernel)
+  }
+  void group_unions() {
     // per-slot group references where the ranks go afterwards, the list itself (slot order = curve order: neighbours in
-    // the list are neighbours in space) where the root flags go; its length in counters_[8], the XCDs' cursors behind the statistics' stripes
-    int32_t *group_at = a.rank, *groups = is_root;
-    unsigned long long *n_groups = counters_ + 8;
-    unsigned long long *cursors = counters_ + kCounters + kDbStripes * 8;  // (behind the statistics' stripes, kDbCursorStride apart)
-    // (... and the count of stack overflows in [17]; all zero since the call's first memset)
-    a.chunk = getenv("TKNN_DB_CHUNK") ? std::max(1, atoi(getenv("TKNN_DB_CHUNK"))) : 64;
-    a.short_way = getenv("TKNN_DB_SHORT") ? atoi(getenv("TKNN_DB_SHORT")) : 1;
-    a.scan_budget = getenv("TKNN_DB_SCAN") ? std::max(0, atoi(getenv("TKNN_DB_SCAN"))) : 12;
+    // the list are neighbours in space) where the root flags go (db_workspace.h); its length, the stack overflows and the
+    // XCDs' cursors in the counter array, all zero since the call's first memset
+    int32_t *group_at = a.rank, *groups = roots;
+    unsigned long long *n_groups = e.counters_ + kDbGroups, *overflows = e.counters_ + kDbOverflows, *cursors = e.counters_ + kDbCursors;
+    a.chunk = knobs.chunk, a.short_way = knobs.short_way, a.scan_budget = knobs.scan_budget;
     hipLaunchKernelGGL(db_group_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, group_at, uni, a.min_row, block_places);
     OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, block_places, block_places + blocks, (int)blocks, s));
     hipLaunchKernelGGL(db_group_list_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, group_at, block_places + blocks, groups, n_groups);
     // persistent lanes: as many workgroups as the device holds at once (the list's length is known on the device only)
     // (per engine: the CU count and the occupancy are those of THIS engine's device)
-    if (db_union_resident_ == 0) {
+    if (e.db_union_resident_ == 0) {
       int per_cu = 0;
       hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, device_) != hipSuccess) {
-        db_union_resident_ = 256 * 4;
+      if (hipGetDeviceProperties(&prop, e.device_) != hipSuccess) {
+        e.db_union_resident_ = 256 * 4;
       } else {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)db_group_union_kernel, kDbUnionBlock, 0) != hipSuccess) per_cu = 4;
         // nine workgroups = 18 waves per CU are what fits (16 KB of LDS per workgroup = 13 granules of 1 280 bytes: the occupancy
         // query says ten).  BASELINE config 3, both passes, since the packet cursors have cache lines of their own (round 4):
         // 1.46 / 1.34 / 1.25 ms with seven / eight / nine; ten (a build with seven buffered unions per lane: 12 granules) 1.27
         // (TKNN_DB_PER_CU: measurements)
-        db_union_resident_ = prop.multiProcessorCount * std::max(1, std::min(per_cu, getenv("TKNN_DB_PER_CU") ? atoi(getenv("TKNN_DB_PER_CU")) : 9));
+        e.db_union_resident_ = prop.multiProcessorCount * std::max(1, std::min(per_cu, getenv("TKNN_DB_PER_CU") ? atoi(getenv("TKNN_DB_PER_CU")) : 9));
       }
     }
-    const int resident = db_union_resident_;
-    unsigned grid = blocks < (unsigned)resident ? blocks : (unsigned)resident;
-    if (getenv("TKNN_DB_GRID")) grid = std::max(1, std::min((int)grid, atoi(getenv("TKNN_DB_GRID"))));  // measurements
+    const unsigned resident = (unsigned)e.db_union_resident_;
+    const unsigned grid = (unsigned)std::max(1, std::min((int)(blocks < resident ? blocks : resident), knobs.grid));
     // Two passes: first the pairs of groups that (nearly) touch -- in a dense region their probes hit at once, and when the
     // pass is over a cluster's groups are one set --, then the pairs further apart, nearly all of which then are in one
     // set already and cost a parent read instead of a probe that would have to look at many point pairs to find one close
     // enough (or none).  One pass settles everything as soon as it is met: 4 times the point tests, 14 ms instead of 4.
-    const float split = getenv("TKNN_DB_SPLIT") ? (float)atof(getenv("TKNN_DB_SPLIT")) : 0.25f;
+    const float split = knobs.split;
     // ONE number bounds both passes: pass 1 takes near2 <= near_hi2, pass 2 near2 > that same value, and the per-axis
     // reach of a pass's box prefilter is derived from its near_hi2 (>= its square root, DbArgs), so that no pair whose
     // faces are between split * eps_wide and sqrt(near_hi2) apart along one axis falls between the passes
     // (reach = split * eps (1 + 1e-6) against near2 <= split^2 eps^2 (1 + 1e-5) left a 34-ulp window).
-    if (TKNN_DIAG_BUILD && (a.diag & 512)) {
-      a.pk_diag = (int32_t *)((char *)block_places + block_places_bytes);
-      OWLMI_HIP(hipMemsetAsync(a.pk_diag, 0, max_packets * 16, s));
-    }
+    if (a.pk_diag) OWLMI_HIP(hipMemsetAsync(a.pk_diag, 0, DbClusterWs::max_packets((size_t)n) * 16, s));
     a.near_lo2 = -1.f;
     a.near_hi2 = split * split * a.eps_out2;
     a.reach = db_reach_of(a.near_hi2);
-    OWLMI_HIP(hipEventRecord(ev_d_, s));
+    OWLMI_HIP(hipEventRecord(e.ev_d_, s));
     if (split < 1.f) {
       union_launches = 2;
-      hipLaunchKernelGGL(db_group_union_kernel, dim3(grid), dim3(kDbUnionBlock), 0, s, a, groups, n_groups, cursors, n_groups + 9);
+      hipLaunchKernelGGL(db_group_union_kernel, dim3(grid), dim3(kDbUnionBlock), 0, s, a, groups, n_groups, cursors, overflows);
       OWLMI_HIP(hipMemsetAsync(cursors, 0, 8 * kDbCursorStride * sizeof(unsigned long long), s));
       a.near_lo2 = a.near_hi2;
-      OWLMI_HIP(hipEventRecord(ev_g_, s));
-      between_passes = true;
-      if (n > 1 && !(getenv("TKNN_DB_UNIFORM") && atoi(getenv("TKNN_DB_UNIFORM")) == 0)) {  // (0: measurements without it)
-        // which nodes hold one set only, now that the groups that touch are united (min_row's place is free until the unions are done)
+      OWLMI_HIP(hipEventRecord(e.ev_g_, s));
+      between_passes = true;  // ev_g_ .. ev_h_: the cursors' reset and db_uniform_kernel, not part of union_ms
+      if (n > 1 && knobs.uniform) {
+        // which nodes hold one set only, now that the groups that touch are united
         a.uni = uni;          // (filled by db_group_kernel)
-        a.uni_leaf = a.rank;  // (the select has used the per-slot group references up)
-        a.split_owner = bvh_.split_owner_device();
+        a.uni_leaf = a.rank;  // (the list kernel has used the per-slot group references up)
+        a.split_owner = e.bvh_.split_owner_device();
         hipLaunchKernelGGL(db_uniform_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, groups, n_groups);
       }
-      OWLMI_HIP(hipEventRecord(ev_h_, s));
+      OWLMI_HIP(hipEventRecord(e.ev_h_, s));
     }
     a.near_hi2 = a.eps_out2;
     a.reach = db_reach_of(a.near_hi2);
-    hipLaunchKernelGGL(db_group_union_kernel, dim3(grid), dim3(kDbUnionBlock), 0, s, a, groups, n_groups, cursors, n_groups + 9);
+    hipLaunchKernelGGL(db_group_union_kernel, dim3(grid), dim3(kDbUnionBlock), 0, s, a, groups, n_groups, cursors, overflows);
+    OWLMI_HIP(hipEventRecord(e.ev_e_, s));
   }
-  OWLMI_HIP(hipEventRecord(ev_e_, s));
-  if (per_point) OWLMI_HIP(hipMemsetAsync(a.min_row, 0x7f, (size_t)n * sizeof(int32_t), s));  // 0x7f7f7f7f: above every row (else: db_group_kernel)
-  const unsigned blocks_per = (unsigned)(((n + kDbPer - 1) / kDbPer + kDbBlock - 1) / kDbBlock);  // kDbPer slots per thread
-  hipLaunchKernelGGL(db_flatten_kernel, dim3(blocks_per), dim3(kDbBlock), 0, s, a, is_root);
-  hipLaunchKernelGGL(db_root_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, is_root);
-  OWLMI_HIP(hipGetLastError());
-  OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, is_root, a.rank, (int)n, s));
-  // number of clusters = rank[n-1] + is_root[n-1]
-  int32_t last[2] = {0, 0};
-  OWLMI_HIP(hipMemcpyAsync(&last[0], a.rank + (n - 1), 4, hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipMemcpyAsync(&last[1], is_root + (n - 1), 4, hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipEventRecord(ev_f_, s));
-  if (side) {
-    OWLMI_HIP(hipStreamWaitEvent(s, ev_side_b_, 0));
-    db_side_pending_ = false;
+  // every core slot to its root, the roots' smallest rows, the clusters numbered by them
+  void number_clusters() {
+    int32_t *is_root = roots;
+    hipLaunchKernelGGL(db_flatten_kernel, dim3(blocks_per), dim3(kDbBlock), 0, s, a, is_root);
+    hipLaunchKernelGGL(db_root_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, is_root);
+    OWLMI_HIP(hipGetLastError());
+    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, is_root, a.rank, (int)n, s));
+    // number of clusters = rank[n-1] + is_root[n-1]
+    OWLMI_HIP(hipMemcpyAsync(&last[0], a.rank + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    OWLMI_HIP(hipMemcpyAsync(&last[1], is_root + (n - 1), 4, hipMemcpyDeviceToHost, s));
+    OWLMI_HIP(hipEventRecord(e.ev_f_, s));
   }
   // labels by slot first and a gather to the rows (default), or scattered straight to the rows (TKNN_DB_LABEL=scatter: A/B).
   // The caller's arrays must allow 16-byte stores for the gather (hipMalloc'd ones do).
-  const char *label_env = getenv("TKNN_DB_LABEL");
-  const int32_t *row_slot = bvh_.row_slot_device();
-  const bool gather = row_slot && !(label_env && std::strcmp(label_env, "scatter") == 0) && ((uintptr_t)d_labels % 16 == 0) && (!d_core || (uintptr_t)d_core % 4 == 0);
-  int32_t *by_slot = gather ? is_root : nullptr;  // (the root flags have been summed: their place is free)
-  hipLaunchKernelGGL(db_label_kernel, dim3(walk_grid + blocks_per), dim3(kDbBlock), 0, s, a, not_core, counters_ + 19, (int)walk_grid,
-                     side ? border_lists : (const int32_t *)nullptr, border_per, (long long)n, by_slot);
-  if (gather) hipLaunchKernelGGL(db_rows_from_slots_kernel, dim3(blocks_per), dim3(kDbBlock), 0, s, a, row_slot, by_slot);
-  OWLMI_HIP(hipGetLastError());
-  OWLMI_HIP(hipEventRecord(e1, s));
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + 8, counters_ + 8, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // groups
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + 9, counters_ + 17, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));  // stack overflows
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + 10, counters_ + 19, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));  // slots that are not core
-  db_read_stats(s);
-  OWLMI_HIP(hipStreamSynchronize(s));
-  if (!per_point && h_counters_[9] != 0 && !db_force_point_) {
-    // a packet's walk ran out of stack (a tree some 250 levels deep): the whole call again with the per-point unions
-    db_force_point_ = true;
-    try {
-      dbscan(eps, min_pts, d_labels, d_core, d_counts, info, s, core_label);
-    } catch (...) {
-      db_force_point_ = false;
-      throw;
+  void labels() {
+    if (side) {  // the border walk's lists
+      OWLMI_HIP(hipStreamWaitEvent(s, e.ev_side_b_, 0));
+      e.db_side_pending_ = false;
     }
-    db_force_point_ = false;
-    return;
+    const int32_t *row_slot = e.bvh_.row_slot_device();
+    const bool gather = row_slot && !knobs.scatter && ((uintptr_t)a.labels % 16 == 0) && (!a.core || (uintptr_t)a.core % 4 == 0);
+    int32_t *by_slot = gather ? roots : nullptr;  // (the root flags have been summed: their place is free)
+    hipLaunchKernelGGL(db_label_kernel, dim3(walk_grid + blocks_per), dim3(kDbBlock), 0, s, a, not_core, e.counters_ + kDbNotCore, (int)walk_grid,
+                       side ? border_lists : (const int32_t *)nullptr, border_per, (long long)n, by_slot);
+    if (gather) hipLaunchKernelGGL(db_rows_from_slots_kernel, dim3(blocks_per), dim3(kDbBlock), 0, s, a, row_slot, by_slot);
+    OWLMI_HIP(hipGetLastError());
+    OWLMI_HIP(hipEventRecord(e.ev_b_, s));
   }
-  if (info) {
+  // the counters to the host; returns when the stream has run dry
+  void read_back() {
+    OWLMI_HIP(hipMemcpyAsync(e.h_counters_ + kHostDbGroups, e.counters_ + kDbGroups, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    OWLMI_HIP(hipMemcpyAsync(e.h_counters_ + kHostDbOverflows, e.counters_ + kDbOverflows, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    OWLMI_HIP(hipMemcpyAsync(e.h_counters_ + kHostDbNotCore, e.counters_ + kDbNotCore, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    e.db_read_stats(s);
+    OWLMI_HIP(hipStreamSynchronize(s));
+  }
+  // one clustering from the first launch to the last
+  void cluster(float eps, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, bool by_point) {
+    cluster_setup(eps, d_labels, d_core, d_counts, knobs.side, by_point, !by_point);
+    core_flags();
+    build_next_core(false, not_core);
+    border_walk();
+    per_point ? unions() : group_unions();
+    number_clusters();
+    labels();
+    read_back();
+  }
+  // tknnDbscanAssign: the caller's labels decide the core flags; a core point keeps its label, any other point takes the
+  // smallest among its core neighbours
+  void assign(float eps, int32_t *d_labels, const int32_t *core_label, tknnDbscanInfo *info) {
+    cluster_setup(eps, d_labels, nullptr, nullptr, false, false, false);
+    hipLaunchKernelGGL(db_core_from_labels_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_label);
+    OWLMI_HIP(hipEventRecord(e.ev_c_, s));
+    build_next_core(true, nullptr);
+    hipLaunchKernelGGL(db_assign_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_label);
+    OWLMI_HIP(hipGetLastError());
+    OWLMI_HIP(hipEventRecord(e.ev_b_, s));
+    OWLMI_HIP(hipStreamSynchronize(s));
+    e.db_read_stats(s);
+    if (!info) return;
     float ms = 0;
+    OWLMI_HIP(hipEventElapsedTime(&ms, e.ev_a_, e.ev_b_));
     std::memset(info, 0, sizeof *info);
-    OWLMI_HIP(hipEventElapsedTime(&ms, e0, e1));
-    info->clusters = last[0] + last[1];
-    info->solve_ms = ms;
-    OWLMI_HIP(hipEventElapsedTime(&info->core_ms, e0, ev_c_));
-    OWLMI_HIP(hipEventElapsedTime(&info->union_ms, ev_d_, ev_e_));
-    if (between_passes) {  // union_ms: the two launches of the union kernel
-      float between = 0;
-      OWLMI_HIP(hipEventElapsedTime(&between, ev_g_, ev_h_));
-      info->union_ms -= between;
-    }
-    OWLMI_HIP(hipEventElapsedTime(&info->label_ms, ev_f_, e1));
-    info->node_tests = (int64_t)(h_counters_[0] + h_counters_[2] + h_counters_[4]);
-    info->point_tests = (int64_t)(h_counters_[1] + h_counters_[3] + h_counters_[5]);
-    info->core_point_tests = (int64_t)h_counters_[1];
-    info->union_point_tests = (int64_t)h_counters_[3];
-    info->label_point_tests = (int64_t)h_counters_[5];
-    info->union_launches = union_launches;
-    info->union_node_tests = (int64_t)h_counters_[2];
-    info->groups = per_point ? 0 : (int64_t)h_counters_[8];
-    if ((a.diag & 512) && a.pk_diag) {
-      // what the packets of the timed pass took, and when the launch would end if the waves took them longest first
-      // (TKNN_DB_DUMP=<file>: four int32 per packet -- ticks, extent in 1e-6, rounds, settles -- for scripts/db_packet_stats.py)
-      const size_t np = ((size_t)h_counters_[8] + 63) / 64;
-      std::vector<int32_t> d(np * 4);
-      OWLMI_HIP(hipMemcpy(d.data(), a.pk_diag, np * 16, hipMemcpyDeviceToHost));
-      if (const char *dump = getenv("TKNN_DB_DUMP")) {
-        if (FILE *f = std::fopen(dump, "wb")) {
-          std::fwrite(d.data(), 16, np, f);
-          std::fclose(f);
-        }
-      }
-      std::vector<size_t> order(np);
-      for (size_t i = 0; i < np; i++) order[i] = i;
-      std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return d[x * 4] > d[y * 4]; });
-      double sum = 0;
-      for (size_t i = 0; i < np; i++) sum += d[i * 4];
-      const int machines = (int)db_union_resident_ * (kDbUnionBlock / 64);
-      std::vector<double> load(machines, 0.0);
-      for (size_t i = 0; i < np; i++) load[std::min_element(load.begin(), load.end()) - load.begin()] += d[order[i] * 4];
-      std::fprintf(stderr, "[dbscan] %zu packets, %d waves: sum %.3g ticks, mean per wave %.0f, longest packet %d; longest-first would end at %.0f ticks\n", np, machines, sum,
-                   sum / machines, np ? d[order[0] * 4] : 0, *std::max_element(load.begin(), load.end()));
-      for (int i = 0; i < 6 && (size_t)i < np; i++)
-        std::fprintf(stderr, "[dbscan]   packet %zu: %d ticks, extent %.4f, %d rounds, %d settles\n", order[i], d[order[i] * 4], d[order[i] * 4 + 1] * 1e-6, d[order[i] * 4 + 2], d[order[i] * 4 + 3]);
-    }
-    if (a.diag & 512) {
-      unsigned long long t[20];
-      OWLMI_HIP(hipMemcpy(t, counters_ + 20, sizeof t, hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[dbscan] union kernel: %llu waves, mean time in the kernel %.0f ticks, longest %llu ticks (%.0f %% of it filled on average), in packets %.0f ticks\n", t[15],
-                   (double)t[13] / (double)t[15], t[14], 100.0 * (double)t[13] / (double)t[15] / (double)t[14], (double)(t[0] + t[1] + t[2] + t[3] + t[4]) / (double)t[15]);
-      if (!(a.diag & 1024)) std::fprintf(stderr, "[dbscan] union kernel: longest packet %llu ticks; %llu packets above 2^20 ticks, %llu above 2^21\n", t[12], t[10], t[11]);
-      if (!(a.diag & 1024) && t[11]) std::fprintf(stderr, "[dbscan] union kernel: the packets above 2^21 ticks, each on average: %.1f rounds, %.1f settles (%.0f ticks in them), %.1f entries the long way, %.1f point tests\n",
-                   (double)t[16] / t[11], (double)t[17] / t[11], (double)t[9] / t[11], (double)t[18] / t[11], (double)t[19] / t[11]);
-      const double tot = (double)(t[0] + t[1] + t[2] + t[3] + t[4]);
-      std::fprintf(stderr, "[dbscan] union kernel wave time: loads %.1f%%  tests %.1f%%  settles %.1f%%  pushes %.1f%%  packet set-up %.1f%%;  %.1f rounds and %.1f settles per packet, %llu packet walks, %.1f us per packet walk (s_memtime at 100 MHz)\n",
-                   100 * t[0] / tot, 100 * t[1] / tot, 100 * t[2] / tot, 100 * t[3] / tot, 100 * t[4] / tot, (double)t[5] / (double)t[7], (double)t[6] / (double)t[7], t[7], tot / 100.0 / (double)t[7]);
-    }
-    if (getenv("TKNN_DB_VERBOSE"))
-      std::fprintf(stderr, "[dbscan] node / point tests: core flags %llu / %llu, unions %llu / %llu, labels %llu / %llu; %llu slots not core\n", h_counters_[0],
-                   h_counters_[1], h_counters_[2], h_counters_[3], h_counters_[4], h_counters_[5], h_counters_[10]);
-    if (a.diag & 1024) {
-      unsigned long long t[5];
-      OWLMI_HIP(hipMemcpy(t, counters_ + 28, sizeof t, hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[dbscan] second union pass: %llu packets of one set, %llu mixed; %llu nodes popped, %llu of them dropped as the packet's own set, %llu known to be of one set\n", t[0], t[1], t[3], t[2], t[4]);
-    }
-    if (a.diag & 8)
-      std::fprintf(stderr, "[dbscan] groups %llu  union-phase node tests %llu  longest walk %llu  mean of the waves' longest %.0f\n", h_counters_[8],
-                   h_counters_[2], h_counters_[6], (double)h_counters_[7] / ((double)((h_counters_[8] + 63) / 64) + 1e-9));
+    info->clusters = -1, info->solve_ms = ms, info->label_ms = ms;
+    info->node_tests = (int64_t)e.h_counters_[kDbStatLabel];
+    info->point_tests = info->label_point_tests = (int64_t)e.h_counters_[kDbStatLabel + 1];
   }
+  void cluster_info(tknnDbscanInfo *info) const;
+  void print_diagnostics() const;
+};
+
+void Engine::DbCall::cluster_info(tknnDbscanInfo *info) const {
+  const unsigned long long *h = e.h_counters_;
+  float ms = 0;
+  std::memset(info, 0, sizeof *info);
+  OWLMI_HIP(hipEventElapsedTime(&ms, e.ev_a_, e.ev_b_));
+  info->clusters = last[0] + last[1];
+  info->solve_ms = ms;
+  OWLMI_HIP(hipEventElapsedTime(&info->core_ms, e.ev_a_, e.ev_c_));
+  OWLMI_HIP(hipEventElapsedTime(&info->union_ms, e.ev_d_, e.ev_e_));
+  if (between_passes) {  // union_ms: the two launches of the union kernel
+    float between = 0;
+    OWLMI_HIP(hipEventElapsedTime(&between, e.ev_g_, e.ev_h_));
+    info->union_ms -= between;
+  }
+  OWLMI_HIP(hipEventElapsedTime(&info->label_ms, e.ev_f_, e.ev_b_));
+  info->node_tests = (int64_t)(h[kDbStatCore] + h[kDbStatUnion] + h[kDbStatLabel]);
+  info->point_tests = (int64_t)(h[kDbStatCore + 1] + h[kDbStatUnion + 1] + h[kDbStatLabel + 1]);
+  info->core_point_tests = (int64_t)h[kDbStatCore + 1];
+  info->union_point_tests = (int64_t)h[kDbStatUnion + 1];
+  info->label_point_tests = (int64_t)h[kDbStatLabel + 1];
+  info->union_launches = union_launches;
+  info->union_node_tests = (int64_t)h[kDbStatUnion];
+  info->groups = per_point ? 0 : (int64_t)h[kHostDbGroups];
 }
 
+// what TKNN_DB_DIAG (diagnostic library) and TKNN_DB_VERBOSE ask for, on stderr (scripts/db_probe.py, db_packet_stats.py,
+// diag_sweep.sh and db_fallback_check.py read it)
+void Engine::DbCall::print_diagnostics() const {
+  const unsigned long long *h = e.h_counters_;
+  if ((a.diag & 512) && a.pk_diag) {
+    // what the packets of the timed pass took, and when the launch would end if the waves took them longest first
+    // (TKNN_DB_DUMP=<file>: four int32 per packet -- ticks, extent in 1e-6, rounds, settles -- for scripts/db_packet_stats.py)
+    const size_t np = ((size_t)h[kHostDbGroups] + 63) / 64;
+    std::vector<int32_t> d(np * 4);
+    OWLMI_HIP(hipMemcpy(d.data(), a.pk_diag, np * 16, hipMemcpyDeviceToHost));
+    if (knobs.dump) {
+      if (FILE *f = std::fopen(knobs.dump, "wb")) {
+        std::fwrite(d.data(), 16, np, f);
+        std::fclose(f);
+      }
+    }
+    std::vector<size_t> order(np);
+    for (size_t i = 0; i < np; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return d[x * 4] > d[y * 4]; });
+    double sum = 0;
+    for (size_t i = 0; i < np; i++) sum += d[i * 4];
+    const int machines = (int)e.db_union_resident_ * (kDbUnionBlock / 64);
+    std::vector<double> load(machines, 0.0);
+    for (size_t i = 0; i < np; i++) load[std::min_element(load.begin(), load.end()) - load.begin()] += d[order[i] * 4];
+    std::fprintf(stderr, "[dbscan] %zu packets, %d waves: sum %.3g ticks, mean per wave %.0f, longest packet %d; longest-first would end at %.0f ticks\n", np, machines, sum,
+                 sum / machines, np ? d[order[0] * 4] : 0, *std::max_element(load.begin(), load.end()));
+    for (int i = 0; i < 6 && (size_t)i < np; i++)
+      std::fprintf(stderr, "[dbscan]   packet %zu: %d ticks, extent %.4f, %d rounds, %d settles\n", order[i], d[order[i] * 4], d[order[i] * 4 + 1] * 1e-6, d[order[i] * 4 + 2], d[order[i] * 4 + 3]);
+  }
+  if (a.diag & 512) {
+    unsigned long long t[kDbDiagWords];  // (the block's words: knn_device.h)
+    OWLMI_HIP(hipMemcpy(t, e.counters_ + kDbDiag, sizeof t, hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[dbscan] union kernel: %llu waves, mean time in the kernel %.0f ticks, longest %llu ticks (%.0f %% of it filled on average), in packets %.0f ticks\n", t[15],
+                 (double)t[13] / (double)t[15], t[14], 100.0 * (double)t[13] / (double)t[15] / (double)t[14], (double)(t[0] + t[1] + t[2] + t[3] + t[4]) / (double)t[15]);
+    if (!(a.diag & 1024)) std::fprintf(stderr, "[dbscan] union kernel: longest packet %llu ticks; %llu packets above 2^20 ticks, %llu above 2^21\n", t[12], t[10], t[11]);
+    if (!(a.diag & 1024) && t[11]) std::fprintf(stderr, "[dbscan] union kernel: the packets above 2^21 ticks, each on average: %.1f rounds, %.1f settles (%.0f ticks in them), %.1f entries the long way, %.1f point tests\n",
+                 (double)t[16] / t[11], (double)t[17] / t[11], (double)t[9] / t[11], (double)t[18] / t[11], (double)t[19] / t[11]);
+    const double tot = (double)(t[0] + t[1] + t[2] + t[3] + t[4]);
+    std::fprintf(stderr, "[dbscan] union kernel wave time: loads %.1f%%  tests %.1f%%  settles %.1f%%  pushes %.1f%%  packet set-up %.1f%%;  %.1f rounds and %.1f settles per packet, %llu packet walks, %.1f us per packet walk (s_memtime at 100 MHz)\n",
+                 100 * t[0] / tot, 100 * t[1] / tot, 100 * t[2] / tot, 100 * t[3] / tot, 100 * t[4] / tot, (double)t[5] / (double)t[7], (double)t[6] / (double)t[7], t[7], tot / 100.0 / (double)t[7]);
+  }
+  if (knobs.verbose)
+    std::fprintf(stderr, "[dbscan] node / point tests: core flags %llu / %llu, unions %llu / %llu, labels %llu / %llu; %llu slots not core\n", h[kDbStatCore],
+                 h[kDbStatCore + 1], h[kDbStatUnion], h[kDbStatUnion + 1], h[kDbStatLabel], h[kDbStatLabel + 1], h[kHostDbNotCore]);
+  if (a.diag & 1024) {
+    unsigned long long t[5];
+    OWLMI_HIP(hipMemcpy(t, e.counters_ + kDbDiag + kDbDiagSets, sizeof t, hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[dbscan] second union pass: %llu packets of one set, %llu mixed; %llu nodes popped, %llu of them dropped as the packet's own set, %llu known to be of one set\n", t[0], t[1], t[3], t[2], t[4]);
+  }
+  if (a.diag & 8)
+    std::fprintf(stderr, "[dbscan] groups %llu  union-phase node tests %llu  longest walk %llu  mean of the waves' longest %.0f\n", h[kHostDbGroups],
+                 h[kDbStatUnion], h[kDbStatLongestWalk], (double)h[kDbStatWalkSum] / ((double)((h[kHostDbGroups] + 63) / 64) + 1e-9));
+}
+
+// tknnDbscanNoise: one growth round of the auto-eps loop without the loop.  Returns the number of noise points; d_noise is
+// indexed by row.
+int64_t Engine::dbscan_noise(float eps, int min_pts, uint8_t *d_noise, hipStream_t s) {
+  DbCall c(*this, min_pts, s);
+  c.probe_setup();
+  const int64_t count = c.probe_round(eps, true);
+  hipLaunchKernelGGL(db_rows_kernel, dim3(c.blocks), dim3(kDbBlock), 0, s, c.a, c.noise, d_noise);
+  OWLMI_HIP(hipGetLastError());
+  OWLMI_HIP(hipStreamSynchronize(s));
+  return count;
+}
+
+void Engine::dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
+                    tknnDbscanInfo *info, hipStream_t s, const int32_t *core_label) {
+  DbCall c(*this, min_pts, s);
+  if (core_label) return c.assign(eps, d_labels, core_label, info);
+  c.cluster(eps, d_labels, d_core, d_counts, c.knobs.per_point);
+  // a packet's walk ran out of stack (a tree some 250 levels deep): the whole call again with the per-point unions
+  if (!c.per_point && h_counters_[kHostDbOverflows] != 0) c.cluster(eps, d_labels, d_core, d_counts, true);
+  if (info) {
+    c.cluster_info(info);
+    c.print_diagnostics();
+  }
+}
 
 // tknnDbscanAuto: the growth loop of the spec -- rounds of (core flags of the points not core yet, noise probe of the
 // points still noise) with eps doubling, then ONE full clustering at the eps that brought the noise under the bound.
 void Engine::dbscan_auto(float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                          tknnDbscanAutoInfo *info, hipStream_t s) {
-  const int64_t n = bvh_.size();
-  const int64_t bound = (int64_t)std::floor(max_noise * (double)n);
-  // scratch of the probe rounds: parent (unused but written by the core kernel), rank / flags, core ranks, next_core,
-  // core flags per slot, noise flags per slot
-  size_t scan_bytes = 0;
-  OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t *)nullptr, (int32_t *)nullptr, (int)n, s));
-  {
-    size_t flag_scan_bytes = 0;
-    OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, flag_scan_bytes, DbFlagIter(nullptr, DbFlagOf()), (int32_t *)nullptr, (int)n, s));
-    scan_bytes = std::max(scan_bytes, flag_scan_bytes);
-  }
-  const size_t need = (((size_t)n * (4 + 4 + 4 + 4 + 1 + 1)) + 32 + 255) / 256 * 256;
-  char *ws = (char *)workspace(need + scan_bytes);
-  DbArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.bvh = bvh_.view();
-  a.block_paths = (getenv("TKNN_DB_PATHS") && atoi(getenv("TKNN_DB_PATHS")) == 0) ? nullptr : bvh_.block_paths_device();  // (0: measurements)
-  a.min_pts = min_pts;
-  a.keep_core = 1;
-  a.parent = nullptr;           // no unions in the growth rounds: the slots' place holds ...
-  a.near_node = (int32_t *)ws;  // ... where each point's noise probe starts (db_has_core_neighbour)
-  int32_t *core_rank = (int32_t *)(ws + (size_t)n * 4);
-  a.rank = (int32_t *)(ws + (size_t)n * 8);                     // n + 1 entries: flags, then positions
-  int32_t *next_core = (int32_t *)(ws + (size_t)n * 12 + 4);  // n + 1 entries
-  a.core_sorted = (uint8_t *)(ws + (size_t)n * 16 + 8);
-  uint8_t *noise = a.core_sorted + n;
-  a.next_core = next_core;
-  a.stats = counters_ + kCounters;  // striped (db_add_stats)
-  void *scan_tmp = ws + need;
-  const unsigned blocks = (unsigned)((n + kDbBlock - 1) / kDbBlock), blocks1 = (unsigned)((n + 1 + kDbBlock - 1) / kDbBlock);
-  OWLMI_HIP(hipMemsetAsync(a.core_sorted, 0, (size_t)n, s));
-  OWLMI_HIP(hipEventRecord(ev_a_, s));
+  const int64_t bound = (int64_t)std::floor(max_noise * (double)bvh_.size());
   float eps = eps0;
   int rounds = 0;
-  int64_t noise_now = n;
+  int64_t noise_now = bvh_.size();
   bool reached = false;
-  for (int t = 0; t < max_rounds; t++) {
-    a.eps = eps;
-    a.eps_wide = eps * 1.000001f;
-    a.eps_in2 = eps * eps * (1.0f - 1e-5f);
-    a.eps_out2 = eps * eps * (1.0f + 1e-5f);
-    OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounterWords * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(db_core_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, (int32_t *)nullptr);
-    {
-      int32_t *pos = a.rank;
-        OWLMI_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, DbFlagIter(a.core_sorted, DbFlagOf()), core_rank, (int)n, s));
-      hipLaunchKernelGGL(db_core_pos_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_rank, pos, (int32_t *)nullptr, (unsigned long long *)nullptr);
-      hipLaunchKernelGGL(db_next_core_kernel, dim3(blocks1), dim3(kDbBlock), 0, s, a, core_rank, pos, next_core);
+  {
+    DbCall c(*this, min_pts, s);
+    c.probe_setup();
+    c.a.keep_core = 1;  // slots flagged core by a round with a smaller eps stay core (N(p) only grows)
+    OWLMI_HIP(hipMemsetAsync(c.a.core_sorted, 0, (size_t)c.n, s));
+    OWLMI_HIP(hipEventRecord(ev_a_, s));
+    for (int t = 0; t < max_rounds; t++) {
+      noise_now = c.probe_round(eps, t == 0);
+      rounds = t + 1;
+      if (noise_now <= bound) {
+        reached = true;
+        break;
+      }
+      if (t + 1 < max_rounds) eps = eps * 2.0f;  // hostCode.cpp:321
     }
-    hipLaunchKernelGGL(db_noise_probe_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, noise, t == 0 ? 1 : 0);
-    OWLMI_HIP(hipGetLastError());
-    db_read_stats(s);
-    rounds = t + 1;
-    noise_now = (int64_t)h_counters_[6];
-    if (noise_now <= bound) {
-      reached = true;
-      break;
-    }
-    if (t + 1 < max_rounds) eps = eps * 2.0f;  // hostCode.cpp:321
   }
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   OWLMI_HIP(hipEventSynchronize(ev_b_));
@@ -1991,10 +1954,7 @@ void Engine::dbscan_auto(float eps0, int min_pts, double max_noise, int max_roun
   if (info) {
     std::memset(info, 0, sizeof *info);
     info->last = last;
-    info->rounds = rounds;
-    info->eps = eps;
-    info->noise = noise_now;
-    info->probe_ms = probe_ms;
+    info->rounds = rounds, info->eps = eps, info->noise = noise_now, info->probe_ms = probe_ms;
   }
   if (!reached) throw RoundsExceeded{};
 }

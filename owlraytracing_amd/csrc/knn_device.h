@@ -50,11 +50,35 @@ __device__ __forceinline__ int32_t knn_key_prim(uint64_t key) {
 constexpr int kTieCounter = 32;  // no kernel's own counter reset reaches this far
 constexpr int kCounters = 40;
 constexpr int kTieListCap = 4096;
-// End-of-wave / end-of-workgroup statistics of the TrueKNN kernels live in STRIPES behind RT-DBSCAN's words of the counter array
-// (Engine::kStatBase): kStatStripes stripes of kStatStride words, a cache line each, a workgroup adds to the stripe of its index
-// and the host folds them.  All on one line they were a third of the lane kernel's time (10 M points, k = 10: 44.9 ms with, 29.7
-// without its seven atomics per wave, 1.1 M a launch at ~12 ns each) and 1.5 % of the packet kernel's.
-constexpr int kStatStripes = 32, kStatStride = 16, kStatBase = kCounters + 32 * 8 + 8 * 32;
+// RT-DBSCAN's words of the counter array (dbscan.hip; a call zeroes the whole array first):
+constexpr int kDbGroups = 8;      // length of the group list
+constexpr int kDbOverflows = 17;  // packet walks of db_group_union_kernel that ran out of stack (the host then falls back)
+constexpr int kDbNotCore = 19;    // length of the list of the slots that are not core
+// the diagnostic library's block (DbArgs::diag_out; it runs over the tie words: no solve is under way).  TKNN_DB_DIAG & 512, ticks
+// of the group-union kernel's waves: [0] loads [1] tests [2] settles [3] pushes [4] packet set-up, [5] rounds [6] settles [7]
+// packets, [9] [16] .. [19] the packets above 2^21 ticks, [10] [11] packets above 2^20 / 2^21, [12] the longest, [13] [14] [15]
+// sum / maximum / number of the waves' times.  & 1024, from kDbDiagSets: packets of one set, mixed, nodes dropped, popped, of one set.
+constexpr int kDbDiag = 20, kDbDiagWords = 20, kDbDiagSets = 8;
+// ... behind the kCounters words its work counters in kDbStripes STRIPES of kDbStripeWords words: a workgroup adds to the stripe of
+// its index, the host sums them (a launch over 50 M points would otherwise queue 400 000 atomics on two addresses).  Within a
+// stripe and in the host's sums: (node tests, point tests) of the core-flag / noise-probe, union and label / border / assign
+// kernels; then a growth round's points still noise, or under TKNN_DB_DIAG & 8 the most walk steps of a wave and their sum.
+constexpr int kDbStats = kCounters, kDbStripes = 32, kDbStripeWords = 8;
+constexpr int kDbStatCore = 0, kDbStatUnion = 2, kDbStatLabel = 4, kDbStatNoise = 6, kDbStatLongestWalk = 6, kDbStatWalkSum = 7;
+// ... behind the stripes the group-union kernel's per-XCD packet cursors, a cache line each (side by side their atomics -- one per
+// packet, its answer awaited -- queue at one place).  The packet kernel's per-XCD counters (trueknn_team.hip, kXcdCounter) borrow
+// the stripes' words during a solve.
+constexpr int kDbCursors = kDbStats + kDbStripes * kDbStripeWords, kDbCursorStride = 32;
+// End-of-wave / end-of-workgroup statistics of the TrueKNN kernels live in STRIPES behind RT-DBSCAN's words of the counter array:
+// kStatStripes stripes of kStatStride words, a cache line each (within a stripe the words are the counter array's [1] .. [9]), a
+// workgroup adds to the stripe of its index and the host folds them.  All on one line they were a third of the lane kernel's time
+// (10 M points, k = 10: 44.9 ms with, 29.7 without its seven atomics per wave, 1.1 M a launch at ~12 ns each) and 1.5 % of the
+// packet kernel's.
+constexpr int kStatStripes = 32, kStatStride = 16, kStatBase = kDbCursors + 8 * kDbCursorStride;
+constexpr int kCounterWords = kStatBase + kStatStripes * kStatStride;
+// the host's copy (Engine::h_counters_): folded words first, the stripes as fetched from kHostStripes on; an RT-DBSCAN call
+// also keeps the group list's length, the stack overflows and the not-core list's length in the words named here
+constexpr int kHostStripes = 16, kHostDbGroups = 8, kHostDbOverflows = 9, kHostDbNotCore = 10;
 // edge: one of the tied candidates may be the best one LEFT OUT of the row (or the kernel cannot tell): only a walk finds it.
 // Without it every tie lies between two written entries, and tie_fix_kernel first looks whether the pairs' candidates became
 // candidates at the same level (coincident points -- duplicates of a data set -- always do): then the row stands as it is.

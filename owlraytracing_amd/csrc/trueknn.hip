@@ -323,7 +323,7 @@ Engine::Engine() {
   OWLMI_HIP(hipEventCreate(&ev_h_));
   OWLMI_HIP(hipMalloc((void **)&counters_, kCounterWords * sizeof(unsigned long long)));  // (the team kernel's per-XCD packet counters sit in the stripes' words, 32 words apart: trueknn_team.hip) [32]: tie rows
   OWLMI_HIP(hipMalloc((void **)&tie_list_, kTieListCap * sizeof(int32_t)));
-  OWLMI_HIP(hipHostMalloc((void **)&h_counters_, (16 + std::max(kDbStripes * 8, kStatStripes * kStatStride)) * sizeof(unsigned long long)));
+  OWLMI_HIP(hipHostMalloc((void **)&h_counters_, (kHostStripes + std::max(kDbStripes * kDbStripeWords, kStatStripes * kStatStride)) * sizeof(unsigned long long)));
   if (const char *e = getenv("TKNN_WAVE_FORCE_REDO")) wave_force_redo_ = atoi(e) != 0;
   if (const char *e = getenv("TKNN_LEAF_MAX")) {
     int v = atoi(e);
@@ -475,7 +475,6 @@ void Engine::lane_rounds(const SolveArgs &sa, int first_level, bool fresh, tknnS
     if (sa.d_levels) OWLMI_HIP(hipMemsetAsync(sa.d_levels, 0xff, (size_t)n * sizeof(int32_t), s));
   }
   OWLMI_HIP(hipMemsetAsync(counters_, 0, 16 * sizeof(unsigned long long), s));
-  static_assert(kStatBase == owlmi::kStatBase && kStatStripes == owlmi::kStatStripes && kStatStride == owlmi::kStatStride, "one layout (knn_device.h)");
   reset_stat_stripes(s);
   LaneRoundArgs a;
   a.bvh = bvh_.view();
@@ -523,7 +522,7 @@ void Engine::lane_rounds(const SolveArgs &sa, int first_level, bool fresh, tknnS
     OWLMI_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < 7; i++) {
       h_counters_[i] = 0;
-      for (int j = 0; j < kStatStripes; j++) h_counters_[i] += h_counters_[16 + j * kStatStride + i];
+      for (int j = 0; j < kStatStripes; j++) h_counters_[i] += h_counters_[kHostStripes + j * kStatStride + i];
     }
     float ms = 0;
     OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));

@@ -147,6 +147,7 @@ class Engine {
   const Lbvh &tree() const { return bvh_; }
 
  private:
+  struct DbCall;  // dbscan.hip: one RT-DBSCAN call -- its knobs, its kernels' argument block and its launches, in steps
   void solve_lane(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
   // lane rounds over the queries another kernel left with done_[slot] == 0, each from next_level_[slot]
   void continue_lane(const SolveArgs &sa, int first_level, tknnSolveInfo *info, hipStream_t s);
@@ -206,20 +207,11 @@ class Engine {
   int32_t *tie_list_ = nullptr;  // the first kTieListCap flagged slots, in the order the kernels met them
   uint8_t *tie_ = nullptr;  // per sorted slot: 0, or 1 + the level at which the query finished with exact-distance ties in reach of its row
   int64_t state_cap_ = 0;
-  // counters_: kCounters words (knn_device.h) + kDbStripes x 8 words of RT-DBSCAN's work counters, striped over the workgroups
-  // (dbscan.hip: a launch over 50 M points would otherwise queue 400 000 atomics on two addresses); h_counters_: 16 + the stripes
-  static constexpr int kDbStripes = 32;
-  // ... + the group-union kernel's per-XCD packet cursors, kDbCursorStride words apart (a cache line each: dbscan.hip)
-  static constexpr int kDbCursorStride = 32;
-  // ... + the packet kernel's end-of-wave statistics, striped over the workgroups: kStatStripes stripes of kStatStride words
-  // (a cache line each; within a stripe the words are counters_'s [1] .. [9]), folded on the host (trueknn_team.hip)
-  static constexpr int kStatStripes = 32, kStatStride = 16, kStatBase = kCounters + kDbStripes * 8 + 8 * kDbCursorStride;
-  static constexpr int kCounterWords = kStatBase + kStatStripes * kStatStride;
+  // counters_: kCounterWords words, h_counters_: the host's copy (the layouts of both: knn_device.h)
   unsigned long long *counters_ = nullptr, *h_counters_ = nullptr;
   void *wave_ws_ = nullptr;
   size_t wave_ws_bytes_ = 0;
   int db_union_resident_ = 0;     // workgroups of db_group_union_kernel this engine's device holds at once (0: not asked yet)
-  bool db_force_point_ = false;   // dbscan(): per-point unions (the fallback when a packet walk of the group unions ran out of stack)
   bool wave_force_redo_ = false;  // TKNN_WAVE_FORCE_REDO (tests): treat every wave-kernel solve as if its LDS stack had overflowed
   int wave_leaf_max_ = 16;  // subtrees of at most this many points are streamed as one range (TKNN_LEAF_MAX)
   int32_t *slot_list_ = nullptr;  // compact list of the sorted slots the team kernel handed over (+ its length)

@@ -132,10 +132,10 @@ constexpr int kWalkBlocksPerCu = 4 * (TKNN_WALK_WAVES > 4 ? TKNN_WALK_WAVES : 4)
 // the per-XCD packet counters: 256 bytes apart, behind the kCounters words (the words RT-DBSCAN stripes its statistics over: not in
 // use during a solve).  Side by side in one cache line (round 3: counters[16 + x]) their atomics -- one per packet, 156 000 per launch
 // of the benchmark -- queued at one place (see TeamArgs::grab for what a turn at one address costs)
-constexpr int kXcdCounter = kCounters, kXcdCounterStride = 32;
+constexpr int kXcdCounter = kDbStats, kXcdCounterStride = 32;
 // ... and the packet kernel's end-of-wave statistics: five atomics per wave on one cache line, 20 000 at the end of a launch of the
 // benchmark, cost it 0.10 of 6.6 ms (measured by leaving them out).  Striped over the workgroups, a cache line per stripe (the layout
-// is Engine::kStatBase .. in trueknn_engine.h: behind RT-DBSCAN's words), folded by the host (Engine::fold_stat_stripes)
+// is kStatBase .. in knn_device.h: behind RT-DBSCAN's words), folded by the host (Engine::fold_stat_stripes)
 // (kStatStripes, kStatStride, kStatBase: knn_device.h)
 constexpr int kTeamStack = 192;     // wide-pyramid stack entries per wave
 constexpr int kQrecStride = 6;      // floats per LDS query record (layout below)
@@ -1758,13 +1758,13 @@ void Engine::reset_stat_stripes(hipStream_t s) {
   OWLMI_HIP(hipMemsetAsync(counters_ + kStatBase, 0, kStatStripes * kStatStride * sizeof(unsigned long long), s));
 }
 void Engine::fetch_stat_stripes(hipStream_t s) {
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + 16, counters_ + kStatBase, kStatStripes * kStatStride * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  OWLMI_HIP(hipMemcpyAsync(h_counters_ + kHostStripes, counters_ + kStatBase, kStatStripes * kStatStride * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 }
 KernelStats Engine::fold_stat_stripes(bool with_min) const {
   KernelStats sum;
   if (with_min) sum.first_handover_level = ~0ull;
   for (int j = 0; j < kStatStripes; j++) {
-    const KernelStats st = KernelStats::from_words(h_counters_ + 16 + j * kStatStride);
+    const KernelStats st = KernelStats::from_words(h_counters_ + kHostStripes + j * kStatStride);
     sum.rounds = std::max(sum.rounds, st.rounds);
     sum.node_tests += st.node_tests;
     sum.point_tests += st.point_tests;
@@ -2024,7 +2024,7 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     return true;
   }
   int per_cu = 2;
-  static_assert(kDbStripes * 8 >= 8 * kXcdCounterStride, "the packet counters borrow the words of RT-DBSCAN's striped statistics");
+  static_assert(kDbStripes * kDbStripeWords >= 8 * kXcdCounterStride, "the packet counters borrow the words of RT-DBSCAN's striped statistics");
   const size_t lds = (size_t)kTeamBlock / 64 * (size_t)(nreg == 1 ? TeamLayout<1>::kTeamLds : (nreg == 2 ? TeamLayout<2>::kTeamLds
                                                          : (nreg == 3 ? TeamLayout<3>::kTeamLds : TeamLayout<4>::kTeamLds)));
   const bool full_list = sa.k == 16 * nreg;  // no spare list entry to see a tie with the row's last in
@@ -2059,7 +2059,6 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
   // before the host knows anything, so the usual handful costs no round trip of its own
   launch_tie_fix(sa, tie_list_, -1, std::min(cu_count_ * 4, kTieListCap / 4), s);
   OWLMI_HIP(hipEventRecord(ev_c_, s));
-  static_assert(kStatBase == Engine::kStatBase && kStatStripes == Engine::kStatStripes && kStatStride == Engine::kStatStride, "one layout");
   fetch_stat_stripes(s);
   OWLMI_HIP(hipMemcpyAsync(h_counters_ + 10, counters_ + kTieCounter, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   OWLMI_HIP(hipStreamSynchronize(s));

@@ -598,3 +598,81 @@ def test_core_count_never_counts_a_subtree_twice(min_pts, monkeypatch):
         assert np.array_equal(counted["counts"].cpu().numpy(), ref["counts"]), paths
     monkeypatch.delenv("TKNN_DB_PATHS", raising=False)
     eng.close()
+
+
+_EDGE_SIZES = [1, 2, 255, 256, 257, 512, 513]
+
+
+def _pick_eps_for_rounds(xyz, eps0, rounds=24):
+    """eps0 nudged until no pair distance is within rounding of eps0 * 2^t for any round a growth loop could take"""
+    for j in range(40):
+        e0 = np.float32(eps0 * (1 + 1e-3 * j))
+        e, ok = e0, True
+        for _ in range(rounds):
+            ok = ok and _boundary_free(xyz, float(e))
+            e = np.float32(e * np.float32(2))
+        if ok:
+            return float(e0)
+    return None
+
+
+def _edge_cases(n):
+    """(kind, xyz, eps, min_pts, max_noise or None) at a size where a probe round's last workgroup is full, nearly full or
+    one slot long: no core point at eps, every point core, and clumps with stragglers.  eps is also the growth loop's first
+    eps; max_noise None: the spec has no answer (minPts > n never brings the noise down), the growth loop is left out."""
+    rng = np.random.default_rng(1000 + n)
+    sparse = datasets.uniform3d(n, seed=40 + n)
+    clump = (np.float32(0.5) + np.float32(1e-4) * rng.standard_normal((n, 3))).astype(np.float32)
+    m = (n * 3) // 5
+    centres = rng.uniform(0.1, 0.9, (max(1, m // 20), 3))
+    mixed = np.concatenate([centres[rng.integers(0, len(centres), m)] + 0.002 * rng.standard_normal((m, 3)),
+                            rng.uniform(0, 1, (n - m, 3))]).astype(np.float32)[rng.permutation(n)]
+    few = min(4, n)
+    yield "no_core", sparse, _pick_eps_for_rounds(sparse, 1e-5), 2, (0.5 if n >= 2 else None)
+    yield "all_core", clump, _pick_eps_for_rounds(clump, 0.01), few, 0.0
+    yield "mixed", mixed, _pick_eps_for_rounds(mixed, 0.002), few, 0.1
+
+
+@pytest.mark.parametrize("n", _EDGE_SIZES)
+def test_probe_round_edge_cases_are_what_they_claim(n):
+    """The spec accepts every case of the GPU test below, and the three kinds are the three kinds."""
+    for kind, xyz, eps, min_pts, max_noise in _edge_cases(n):
+        assert eps is not None and len(xyz) == n, kind
+        ref = oracle.dbscan(xyz, eps, min_pts)
+        if kind == "no_core":
+            assert not ref["core"].any()
+        elif kind == "all_core":
+            assert ref["core"].all()
+        elif n >= 255:
+            assert ref["core"].any() and not ref["core"].all() and (ref["labels"] < 0).any()
+        if max_noise is not None:
+            auto = oracle.dbscan_auto(xyz, eps, min_pts, max_noise)
+            assert auto["rounds"] <= 24
+            if kind != "all_core" and n >= 255:
+                assert auto["rounds"] > 1  # later rounds: flags kept from the round before
+        else:
+            assert min_pts > n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", _EDGE_SIZES)
+def test_probe_round_at_block_edges(n):
+    """A growth round builds next_core from per-workgroup counts of 256 slots; the sentinel next_core[n] comes from the thread
+    of slot n - 1.  tknnDbscanNoise and tknnDbscanAuto against the spec at sizes around one and two workgroups."""
+    from owlraytracing_amd.trueknn import TrueKNN
+    eng = TrueKNN()
+    for kind, xyz, eps, min_pts, max_noise in _edge_cases(n):
+        ref = oracle.dbscan(xyz, eps, min_pts)
+        eng.build(xyz)
+        got = eng.dbscan_noise(eps, min_pts)
+        assert np.array_equal(got["noise"].cpu().numpy(), ref["labels"] < 0), kind
+        assert got["count"] == int((ref["labels"] < 0).sum()), kind
+        if max_noise is None:
+            continue
+        want = oracle.dbscan_auto(xyz, eps, min_pts, max_noise)
+        auto = eng.dbscan_auto(eps, min_pts, max_noise)
+        info = auto["info"]
+        assert (info["rounds"], info["eps"], info["noise"], info["clusters"]) == (want["rounds"], want["eps"], want["noise"], want["clusters"]), kind
+        assert np.array_equal(auto["labels"].cpu().numpy(), want["labels"]), kind
+        assert np.array_equal(auto["core"].cpu().numpy(), want["core"]), kind
+    eng.close()
