@@ -320,6 +320,55 @@ TKNN_API int tknnExportTree(tknnEngine e, void *nodes, int32_t *rope_node, int32
  *                (last word) and its four nearest ancestors, farthest first, the root where the path is shorter            */
 TKNN_API int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_paths, void *stream);
 
+/* Test / debug export of everything else the readers of a point tree rely on (tests/lbvh_spec.py restates each array from the
+ * headers; tests/test_lbvh_gpu.py compares them word for word).  which = 0: the tree of tknnBuild / tknnBuildIds; which = 1: the
+ * halo tree of tknnSetHalo.  n is the tree's point count; every pointer is a HOST buffer and may be NULL:
+ *   keys         n uint64: the sorted 63-bit curve keys (curve_point_key of owlraytracing_amd/csrc/curve_key.h with 21 levels over
+ *                the scene box below; bit 63 alone for a point with a NaN coordinate), ascending, equal keys in input order
+ *   points       ceil(n/16)*16 + 16 records {x, y, z, id} of 16 bytes: the points in that order (a point with a NaN coordinate
+ *                stored as all-NaN; id = d_ids[row], or the row without ids), then sentinels {NaN, NaN, NaN, -1} that fill the
+ *                last block of 16 and one whole block after it
+ *   row_slot     n: the sorted slot of each input row (the inverse of prim_id)
+ *   wide_boxes   the 64-ary box pyramid the team kernels descend (LbvhWideView, include/owl/lbvh_device.h): the wide_levels
+ *                live levels one after the other, level l with wide_count[l] boxes {lo[3], hi[3]}; level 0 = the boxes of the
+ *                blocks of 16 sorted points, level l = the boxes of 64 consecutive entries of level l-1, levels added while
+ *                the top one has more than 64 entries.  wide_capacity = the boxes the buffer holds (TKNN_E_HIP if too few;
+ *                ceil(n/16) * 33/32 + 6 always suffice)
+ *   nodes, rope_node, rope_leaf, prim_id, split_owner   as tknnExportTree / tknnExportTreeTables give them for the own tree
+ *   scene        lo xyz, hi xyz of the points (NaN coordinates ignored); nan_count: the points with a NaN coordinate, the last
+ *                of the order; curve: 0 Hilbert, 1 Morton (TKNN_CURVE at build time)
+ * TKNN_E_STATE when the tree asked for is not built: before tknnBuild, and for which = 1 while no halo is set. */
+typedef struct {
+  int32_t which;         /* in */
+  int32_t curve;         /* out, as everything down to scene */
+  int64_t n;
+  int32_t nan_count;
+  int32_t wide_levels;
+  int32_t wide_count[6];
+  float scene[6];
+  int64_t wide_capacity; /* in */
+  uint64_t *keys;
+  void *points;
+  int32_t *row_slot;
+  void *wide_boxes;
+  void *nodes;
+  int32_t *rope_node;
+  int32_t *rope_leaf;
+  int32_t *prim_id;
+  int32_t *split_owner;
+} tknnTreeExport;
+TKNN_API int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream);
+
+/* Test hook for the builder's box trees (what the owl* entry points build over a bounds program's output), without an engine.
+ * mode 0: a private tree is built from the n device boxes d_boxes ({lo[3], hi[3]}, 24 bytes each; sorted by the curve key of
+ * the centres 0.5f*lo + 0.5f*hi); if d_boxes_refit is not NULL, the tree is then refitted to those n boxes (same topology and
+ * order, new node boxes); then nodes (n-1), rope_node (n-1), rope_leaf (n), prim_id (n) and sorted_boxes (n x 6 floats: the
+ * boxes last given, in sorted order) are copied to the HOST buffers given (any may be NULL).
+ * mode 1: no tree is built, mode 2: a POINT tree is built (d_boxes read as 2 n points), and a refit is asked of it: the refit
+ * is refused with TKNN_E_STATE, nothing is launched for it and nothing is copied. */
+TKNN_API int tknnDebugBoxTree(const float *d_boxes, int64_t n, const float *d_boxes_refit, int mode, void *nodes,
+                              int32_t *rope_node, int32_t *rope_leaf, int32_t *prim_id, float *sorted_boxes, void *stream);
+
 /* Test hook for the wave kernel's candidate test.  For each pair (q[i], r[i]) writes lo[i], hi[i]
  * such that, for every fp32 c,   lo <= c <= hi   <=>   fl(c - r) <= q <= fl(c + r)
  * (the box the bounds program of deviceCode.cu:38-56 writes, tested against the query point). */

@@ -107,6 +107,15 @@ class BuildInfo(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TreeExport(ctypes.Structure):
+    _fields_ = [("which", ctypes.c_int32), ("curve", ctypes.c_int32), ("n", ctypes.c_int64), ("nan_count", ctypes.c_int32),
+                ("wide_levels", ctypes.c_int32), ("wide_count", ctypes.c_int32 * 6), ("scene", ctypes.c_float * 6),
+                ("wide_capacity", ctypes.c_int64), ("keys", ctypes.c_void_p), ("points", ctypes.c_void_p),
+                ("row_slot", ctypes.c_void_p), ("wide_boxes", ctypes.c_void_p), ("nodes", ctypes.c_void_p),
+                ("rope_node", ctypes.c_void_p), ("rope_leaf", ctypes.c_void_p), ("prim_id", ctypes.c_void_p),
+                ("split_owner", ctypes.c_void_p)]
+
+
 # every symbol include/owlknn.h declares, with its signature
 SIGNATURES = {
     "tknnLastError": (ctypes.c_char_p, []),
@@ -143,6 +152,9 @@ SIGNATURES = {
     "tknnExportTree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tknnExportTreeTables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "tknnExportTreeEx": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(TreeExport), ctypes.c_void_p]),
+    "tknnDebugBoxTree": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tknnDebugThresholds": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }

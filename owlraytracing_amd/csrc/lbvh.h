@@ -17,6 +17,8 @@ namespace owlmi {
 struct HipError {
   std::string what;
 };
+// a call the tree's state does not allow (refit_boxes on a point tree or on no tree); the C-ABI answers TKNN_E_STATE
+struct LbvhStateError : HipError {};
 
 #define OWLMI_HIP(call)                                                                        \
   do {                                                                                         \
@@ -75,6 +77,19 @@ class Lbvh {
                 hipStream_t stream) const;
   // split_owner: n - 1 entries; block_paths: ceil(n / LBVH_PATH_BLOCK) * LBVH_PATH_WORDS (point trees with n > 1)
   void download_tables(int32_t *split_owner, int32_t *block_paths, hipStream_t stream) const;
+  // what else a point tree's readers rely on (tknnExportTreeEx; tests/lbvh_spec.py states each array): the sorted keys (n), the
+  // sorted points with their NaN sentinels (sentinel_end() entries), row_slot (n), the live levels of the wide pyramid one
+  // after the other (level l: info->wide_count[l] boxes; wide_capacity: how many boxes the buffer holds).  Any pointer but
+  // info may be null.
+  struct DebugInfo {
+    int32_t curve, nan_count, wide_levels, wide_count[LBVH_WIDE_LEVELS];
+    float scene[6];
+  };
+  int64_t sentinel_end() const { return (n_ + LBVH_BLOCK - 1) / LBVH_BLOCK * LBVH_BLOCK + LBVH_BLOCK; }
+  void download_debug(DebugInfo *info, uint64_t *keys, LbvhPoint *points, int32_t *row_slot, LbvhBox *wide_boxes,
+                      int64_t wide_capacity, hipStream_t stream) const;
+  // box trees: the primitives' boxes in sorted order (n)
+  void download_boxes(LbvhBox *sorted_boxes, hipStream_t stream) const;
 
  private:
   void reserve(int64_t n);

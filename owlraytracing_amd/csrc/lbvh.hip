@@ -528,6 +528,7 @@ void Lbvh::build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, 
 
 void Lbvh::build_from_boxes(const LbvhBox *d_boxes, int64_t n, hipStream_t stream) {
   if (n <= 0 || n >= 0x7fffffffLL) throw HipError{"Lbvh: primitive count out of range"};
+  built_ = false;  // until the last launch below has been issued without an error
   reserve(n);
   n_ = n;
   point_mode_ = false;
@@ -549,7 +550,7 @@ void Lbvh::build_from_boxes(const LbvhBox *d_boxes, int64_t n, hipStream_t strea
 }
 
 void Lbvh::refit_boxes(const LbvhBox *d_boxes, hipStream_t stream) {
-  if (!built_ || point_mode_) throw HipError{"Lbvh::refit_boxes: no box tree to refit"};
+  if (!built_ || point_mode_) throw LbvhStateError{{"Lbvh::refit_boxes: no box tree to refit"}};
   hipLaunchKernelGGL(gather_kernel<false>, dim3(blocks_for(n_)), dim3(kBlock), 0, stream,
                      (const float *)nullptr, d_boxes, n_, order_alt_, (LbvhPoint *)nullptr, boxes_, prim_id_, (const int32_t *)nullptr, nan_count(), (int32_t *)nullptr);
   OWLMI_HIP(hipGetLastError());
@@ -589,6 +590,38 @@ void Lbvh::download_tables(int32_t *split_owner, int32_t *block_paths, hipStream
   if (block_paths && block_paths_device())
     OWLMI_HIP(hipMemcpyAsync(block_paths, block_paths_, (size_t)((n_ + LBVH_PATH_BLOCK - 1) / LBVH_PATH_BLOCK) * LBVH_PATH_WORDS * 4,
                              hipMemcpyDeviceToHost, stream));
+  OWLMI_HIP(hipStreamSynchronize(stream));
+}
+
+void Lbvh::download_debug(DebugInfo *info, uint64_t *keys, LbvhPoint *points, int32_t *row_slot, LbvhBox *wide_boxes,
+                          int64_t wide_capacity, hipStream_t stream) const {
+  if (!built_ || !point_mode_) throw HipError{"Lbvh::download_debug: no point tree"};
+  float scene[8];  // 6 floats and the NaN counter behind them
+  OWLMI_HIP(hipMemcpyAsync(scene, scene_, 7 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  if (keys) OWLMI_HIP(hipMemcpyAsync(keys, codes_alt_, (size_t)n_ * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+  if (points)
+    OWLMI_HIP(hipMemcpyAsync(points, points_, (size_t)sentinel_end() * sizeof(LbvhPoint), hipMemcpyDeviceToHost, stream));
+  if (row_slot) OWLMI_HIP(hipMemcpyAsync(row_slot, row_slot_device(), (size_t)n_ * 4, hipMemcpyDeviceToHost, stream));
+  const LbvhWideView w = wide_view();
+  if (wide_boxes) {
+    int64_t at = 0;
+    for (int l = 0; l < w.levels; l++) {
+      if (at + w.count[l] > wide_capacity) throw HipError{"Lbvh::download_debug: the buffer for the wide pyramid is too small"};
+      OWLMI_HIP(hipMemcpyAsync(wide_boxes + at, w.level[l], (size_t)w.count[l] * sizeof(LbvhBox), hipMemcpyDeviceToHost, stream));
+      at += w.count[l];
+    }
+  }
+  OWLMI_HIP(hipStreamSynchronize(stream));
+  info->curve = curve_;
+  std::memcpy(info->scene, scene, 6 * sizeof(float));
+  std::memcpy(&info->nan_count, scene + 6, sizeof(int32_t));
+  info->wide_levels = w.levels;
+  for (int l = 0; l < LBVH_WIDE_LEVELS; l++) info->wide_count[l] = w.count[l];
+}
+
+void Lbvh::download_boxes(LbvhBox *sorted_boxes, hipStream_t stream) const {
+  if (!built_ || point_mode_) throw HipError{"Lbvh::download_boxes: no box tree"};
+  OWLMI_HIP(hipMemcpyAsync(sorted_boxes, boxes_, (size_t)n_ * sizeof(LbvhBox), hipMemcpyDeviceToHost, stream));
   OWLMI_HIP(hipStreamSynchronize(stream));
 }
 

@@ -666,6 +666,9 @@ static int guarded(F &&f) {
   try {
     f();
     return TKNN_OK;
+  } catch (const owlmi::LbvhStateError &e) {
+    g_last_error = e.what;
+    return TKNN_E_STATE;
   } catch (const owlmi::HipError &e) {
     g_last_error = e.what;
     return TKNN_E_HIP;
@@ -979,6 +982,48 @@ int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_path
   return guarded_on(e, [&] {
     if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeTables: call tknnBuild first"};
     e->impl.tree().download_tables(split_owner, block_paths, (hipStream_t)stream);
+  });
+}
+
+int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream) {
+  if (!e || !x || (x->which != 0 && x->which != 1) || (x->wide_boxes && x->wide_capacity < 0)) {
+    g_last_error = "tknnExportTreeEx: need an engine, the export record and which = 0 (own tree) or 1 (halo tree)";
+    return TKNN_E_ARG;
+  }
+  return guarded_on(e, [&] {
+    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeEx: call tknnBuild first"};
+    if (x->which == 1 && !(e->impl.has_halo() && e->impl.halo_tree().built()))
+      throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeEx: no halo tree is set"};
+    const owlmi::Lbvh &t = x->which == 1 ? e->impl.halo_tree() : e->impl.tree();
+    static_assert(sizeof(x->wide_count) == sizeof(owlmi::Lbvh::DebugInfo::wide_count), "wide levels");
+    owlmi::Lbvh::DebugInfo d;
+    t.download_debug(&d, x->keys, (LbvhPoint *)x->points, x->row_slot, (LbvhBox *)x->wide_boxes, x->wide_capacity, (hipStream_t)stream);
+    t.download((LbvhNode *)x->nodes, x->rope_node, x->rope_leaf, x->prim_id, (hipStream_t)stream);
+    t.download_tables(x->split_owner, nullptr, (hipStream_t)stream);
+    x->n = t.size();
+    x->curve = d.curve;
+    x->nan_count = d.nan_count;
+    x->wide_levels = d.wide_levels;
+    for (int l = 0; l < LBVH_WIDE_LEVELS; l++) x->wide_count[l] = d.wide_count[l];
+    for (int a = 0; a < 6; a++) x->scene[a] = d.scene[a];
+  });
+}
+
+int tknnDebugBoxTree(const float *d_boxes, int64_t n, const float *d_boxes_refit, int mode, void *nodes, int32_t *rope_node,
+                     int32_t *rope_leaf, int32_t *prim_id, float *sorted_boxes, void *stream) {
+  if (!d_boxes || n <= 0 || n >= 0x7fffffffLL || mode < 0 || mode > 2) {
+    g_last_error = "tknnDebugBoxTree: need device boxes, 0 < n < 2^31-1 and mode 0, 1 or 2";
+    return TKNN_E_ARG;
+  }
+  return guarded([&] {
+    const hipStream_t s = (hipStream_t)stream;
+    owlmi::Lbvh tree;
+    if (mode == 0) tree.build_from_boxes((const LbvhBox *)d_boxes, n, s);
+    if (mode == 2) tree.build_from_points(d_boxes, 2 * n, s);
+    if (d_boxes_refit || mode != 0) tree.refit_boxes((const LbvhBox *)(d_boxes_refit ? d_boxes_refit : d_boxes), s);
+    tree.download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, s);
+    if (sorted_boxes) tree.download_boxes((LbvhBox *)sorted_boxes, s);
+    OWLMI_HIP(hipStreamSynchronize(s));
   });
 }
 

@@ -145,6 +145,7 @@ class Engine {
   int device() const { return device_; }
   int64_t size() const { return bvh_.size(); }
   const Lbvh &tree() const { return bvh_; }
+  const Lbvh &halo_tree() const { return halo_; }  // meaningful while has_halo()
 
  private:
   struct DbCall;  // dbscan.hip: one RT-DBSCAN call -- its knobs, its kernels' argument block and its launches, in steps

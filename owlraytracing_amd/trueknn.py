@@ -31,6 +31,7 @@ class TrueKNN:
         with torch.cuda.device(self.device):
             _lib.check(lib.tknnCreate(ctypes.byref(self._h)))
         self.n = 0
+        self.halo_n = 0
         self.build_info = None
         self.last_info = None
 
@@ -78,6 +79,7 @@ class TrueKNN:
                                               None if ids is None else ctypes.c_void_p(ids.data_ptr()),
                                               points.shape[0], ctypes.byref(info), self._stream()))
         self.n = int(points.shape[0])
+        self.halo_n = 0  # a build drops the halo tree
         self.build_info = info.as_dict()
         return self.build_info
 
@@ -87,6 +89,7 @@ class TrueKNN:
         with torch.cuda.device(self.device):
             if points is None or len(points) == 0:
                 _lib.check(self._lib.tknnSetHalo(self._h, None, None, 0, self._stream()))
+                self.halo_n = 0
                 return
             points = self._points(points)
             ids = self._ids(ids, points.shape[0])
@@ -95,6 +98,7 @@ class TrueKNN:
             _lib.check(self._lib.tknnSetHalo(self._h, ctypes.c_void_p(points.data_ptr()),
                                              ctypes.c_void_p(ids.data_ptr()), points.shape[0], self._stream()))
             torch.cuda.current_stream(self.device).synchronize()  # the engine copied what it needs
+            self.halo_n = int(points.shape[0])
 
     def halo_select(self, boxes, box_peer, npeers):
         """Send side of the halo exchange: my points inside any of ``boxes`` (m,6 float32 closed boxes,
@@ -372,6 +376,64 @@ class TrueKNN:
             _lib.check(self._lib.tknnExportTreeTables(self._h, split_owner.ctypes.data, paths.ctypes.data, self._stream()))
         return {"nodes": nodes[: max(n - 1, 0)], "rope_node": rope_node[: max(n - 1, 0)],
                 "rope_leaf": rope_leaf, "prim_id": prim, "split_owner": split_owner[: max(n - 1, 0)], "block_paths": paths}
+
+    def export_tree_ex(self, halo=False):
+        """Host copies of everything the readers of a point tree rely on (tknnExportTreeEx), for the own tree or, with
+        ``halo``, the halo tree: n, curve, nan_count, scene (6,) float32, keys (n,) uint64, points (ceil(n/16)*16 + 16, 4)
+        uint32 records x y z id with the sentinels, prim_id, row_slot, nodes (n-1, 8) uint32, rope_node, rope_leaf,
+        split_owner, wide_levels, wide_count (6,) int32 and wide_boxes (sum of the counts, 6) float32, level after level."""
+        torch = self._torch
+        n = self.halo_n if halo else self.n
+        blocks = (n + 15) // 16
+        arrays = {"keys": np.zeros(n, np.uint64), "points": np.zeros((blocks * 16 + 16, 4), np.uint32), "row_slot": np.zeros(n, np.int32),
+                  "wide_boxes": np.zeros((blocks + blocks // 32 + 6, 6), np.float32), "nodes": np.zeros((max(n - 1, 1), 8), np.uint32),
+                  "rope_node": np.zeros(max(n - 1, 1), np.int32), "rope_leaf": np.zeros(n, np.int32), "prim_id": np.zeros(n, np.int32),
+                  "split_owner": np.zeros(max(n - 1, 1), np.int32)}
+        x = _lib.TreeExport()
+        x.which = 1 if halo else 0
+        x.wide_capacity = len(arrays["wide_boxes"])
+        for name, a in arrays.items():
+            setattr(x, name, a.ctypes.data)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.tknnExportTreeEx(self._h, ctypes.byref(x), self._stream()))
+        if int(x.n) != n:
+            raise RuntimeError("export_tree_ex: the tree holds %d points, %d expected" % (x.n, n))
+        out = dict(arrays)
+        for name in ("nodes", "rope_node", "split_owner"):
+            out[name] = arrays[name][: n - 1]
+        out["wide_count"] = np.array(list(x.wide_count), np.int32)
+        out["wide_boxes"] = arrays["wide_boxes"][: int(out["wide_count"].sum())]
+        out.update(n=n, curve=int(x.curve), nan_count=int(x.nan_count), wide_levels=int(x.wide_levels),
+                   scene=np.array(list(x.scene), np.float32))
+        return out
+
+
+def debug_box_tree(boxes, refit=None, mode=0, device=None):
+    """The builder's box tree over (n, 6) float32 ``boxes`` {lo xyz, hi xyz} without an engine (tknnDebugBoxTree), refitted
+    to ``refit`` where given: dict(nodes (n-1, 8) uint32, rope_node, rope_leaf, prim_id, sorted_boxes (n, 6) float32).
+    ``mode`` 1 / 2 ask for a refit of no tree / of a point tree, which raises TknnError (TKNN_E_STATE)."""
+    import torch
+
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise RuntimeError("debug_box_tree needs an MI355X: no GPU is visible and there is no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    boxes = np.ascontiguousarray(boxes, np.float32)
+    n = len(boxes)
+    if boxes.shape != (n, 6) or (refit is not None and np.shape(refit) != (n, 6)):
+        raise ValueError("debug_box_tree: boxes (and refit) must be (n, 6)")
+    nodes = np.zeros((max(n - 1, 1), 8), np.uint32)
+    rope_node = np.zeros(max(n - 1, 1), np.int32)
+    rope_leaf, prim = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    sorted_boxes = np.zeros((n, 6), np.float32)
+    with torch.cuda.device(dev):
+        d_boxes = torch.from_numpy(boxes).to(dev)
+        d_refit = None if refit is None else torch.from_numpy(np.ascontiguousarray(refit, np.float32)).to(dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.tknnDebugBoxTree(ctypes.c_void_p(d_boxes.data_ptr()), n, None if d_refit is None else ctypes.c_void_p(d_refit.data_ptr()),
+                                        int(mode), nodes.ctypes.data, rope_node.ctypes.data, rope_leaf.ctypes.data, prim.ctypes.data,
+                                        sorted_boxes.ctypes.data, stream))
+    return {"nodes": nodes[: n - 1], "rope_node": rope_node[: n - 1], "rope_leaf": rope_leaf, "prim_id": prim, "sorted_boxes": sorted_boxes}
 
 
 def trueknn(points, k, start_radius, **kw):

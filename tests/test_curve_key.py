@@ -7,58 +7,16 @@ of the Hilbert index written here, and against the properties the tree and the p
   * a point with a NaN coordinate gets bit 63;
   * sorted along it, blocks of 16 consecutive points have tighter boxes than along the Z curve: a query's box meets
     clearly fewer of them (the block-list model the packet kernel's lists were sized on)."""
-import ctypes
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HILBERT, MORTON = 0, 1
-
-_SHIM = r"""
-#include "curve_key.h"
-extern "C" {
-void keys(int curve, int levels, long n, const unsigned *x, const unsigned *y, const unsigned *z, unsigned long long *out) {
-  for (long i = 0; i < n; i++) out[i] = curve_key3(curve, x[i], y[i], z[i], levels);
-}
-void point_keys(int curve, int levels, long n, const float *xyz, const float *lo, float ext, unsigned long long *out) {
-  for (long i = 0; i < n; i++)
-    out[i] = curve_point_key(curve, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], lo[0], lo[1], lo[2], ext, levels);
-}
-}
-"""
+import curve_key_host
+from curve_key_host import HILBERT, MORTON, keys as _keys, point_keys as _point_keys
 
 
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "no host C++ compiler"
-    d = tmp_path_factory.mktemp("curve_key")
-    src, so = d / "shim.cpp", d / "libcurvekey.so"
-    src.write_text(_SHIM)
-    subprocess.run([cxx, "-O2", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off", "-I" + os.path.join(ROOT, "owlraytracing_amd", "csrc"),
-                    str(src), "-o", str(so)], check=True, capture_output=True, text=True)
-    return ctypes.CDLL(str(so))
-
-
-def _keys(lib, curve, levels, x, y, z):
-    x, y, z = (np.ascontiguousarray(v, dtype=np.uint32) for v in (x, y, z))
-    out = np.empty(len(x), np.uint64)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    lib.keys(ctypes.c_int(curve), ctypes.c_int(levels), ctypes.c_long(len(x)), p(x), p(y), p(z), p(out))
-    return out
-
-
-def _point_keys(lib, curve, levels, xyz, lo, ext):
-    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
-    lo = np.ascontiguousarray(lo, dtype=np.float32)
-    out = np.empty(len(xyz), np.uint64)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    lib.point_keys(ctypes.c_int(curve), ctypes.c_int(levels), ctypes.c_long(len(xyz)), p(xyz), p(lo), ctypes.c_float(ext), p(out))
-    return out
+    return curve_key_host.compile_shim(tmp_path_factory.mktemp("curve_key"))
 
 
 # ---- the restatement: bit loops instead of magic masks, whole arrays instead of one cell ----
