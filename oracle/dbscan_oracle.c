@@ -310,7 +310,7 @@ int dbref_dbscan_mt(const float *xyz, int64_t n, float eps, int min_pts, int32_t
           int64_t cell = ((int64_t)z * g.dim[1] + y) * g.dim[0] + x;
           for (int64_t s = g.start[cell]; s < g.start[cell + 1]; s++) {
             int32_t p = g.items[s];
-            if (!core[p] || db_dist(xyz + 3 * (int64_t)p, c) > eps) continue;
+            if (!core[p] || !(db_dist(xyz + 3 * (int64_t)p, c) <= eps)) continue; /* (a NaN distance is no neighbour, as in dbref_dbscan) */
             int32_t r = db_find_mt(parent, p);
             if (best < 0 || r < best) best = r;
           }
@@ -454,7 +454,7 @@ int64_t dbref_ball_check(const float *xyz, int64_t n, float eps, int min_pts, co
           int64_t cell = ((int64_t)z * g.dim[1] + y) * g.dim[0] + x;
           for (int64_t s = g.start[cell]; s < g.start[cell + 1]; s++) {
             int32_t p = g.items[s];
-            if (db_dist(xyz + 3 * (int64_t)p, c) > eps) continue;
+            if (!(db_dist(xyz + 3 * (int64_t)p, c) <= eps)) continue; /* (NaN: no neighbour) */
             count++;
             if (!core[p]) continue;
             if (labels[p] != labels[q]) differs = 1;

@@ -9,7 +9,8 @@
 //
 // Same machinery as TrueKNN: points are primitives with box c +- eps (deviceCode.cu:38-56
 // pattern), every point is also a query, the "intersection program" does the true sphere test.
-// Three traversal launches over the point LBVH (one query per lane, stackless ropes):
+// Three traversal launches over the point LBVH (one query per lane, stackless ropes: lane_walk.h has the walk and
+// the node tests, the kernels here say what happens at a node and at a point):
 //   1. core flags: count neighbours, stop at minPts unless counts were asked for
 //   2. union: every core point unites with each core neighbour of smaller index (lock-free
 //      union-find; the smaller index stays root, so a root is its cluster's smallest core index)
@@ -25,6 +26,7 @@
 // Union-find reads/writes go through agent-scope atomics: a workgroup's L1 (and another XCD's L2)
 // would otherwise keep serving a stale parent and a failed CAS could retry forever.
 #include "db_workspace.h"
+#include "lane_walk.h"
 #include "trueknn_engine.h"
 
 #include <hipcub/hipcub.hpp>
@@ -112,15 +114,6 @@ __device__ __forceinline__ void db_add_stats_wave(unsigned long long *stats, uin
   }
 }
 
-// squared distances from q to the farthest and the nearest point of a box
-__device__ __forceinline__ void box_dist2(const LbvhNode &nd, const LbvhPoint &q, float &far2, float &near2) {
-  const float ax = fmaxf(fabsf(q.x - nd.lo[0]), fabsf(q.x - nd.hi[0])), ay = fmaxf(fabsf(q.y - nd.lo[1]), fabsf(q.y - nd.hi[1])),
-              az = fmaxf(fabsf(q.z - nd.lo[2]), fabsf(q.z - nd.hi[2]));
-  const float bx = fmaxf(fmaxf(nd.lo[0] - q.x, q.x - nd.hi[0]), 0.f), by = fmaxf(fmaxf(nd.lo[1] - q.y, q.y - nd.hi[1]), 0.f),
-              bz = fmaxf(fmaxf(nd.lo[2] - q.z, q.z - nd.hi[2]), 0.f);
-  far2 = ax * ax + ay * ay + az * az;
-  near2 = bx * bx + by * by + bz * bz;
-}
 // per-axis reach of a union pass's box prefilter from the pass's bound on the squared distance of nearest faces: at
 // least its square root (sqrtf is correctly rounded; two parts in 10^6 cover that rounding and the squares' in near2)
 inline float db_reach_of(float near_hi2) { return sqrtf(near_hi2) * 1.000002f; }
@@ -164,73 +157,51 @@ __device__ __forceinline__ void for_each_core_group(const DbArgs &a, const LbvhP
                                                     uint32_t &node_tests, uint32_t &point_tests) {
   const LbvhView &bvh = a.bvh;
   const float r = a.eps_wide;
-  int32_t ref = bvh.root;
   // A tight node the sphere cuts through is PROBED, not scanned: the walk goes on below it (its
   // descendants are tight too: inside -> hit, outside -> skipped) and leaves the subtree through the
   // node's own rope at the first core point found within eps -- one is enough, the node is one group.
   int32_t probe_rep = -1, probe_exit = LBVH_END;
-  while (ref != LBVH_END) {
-    if (probe_rep >= 0 && ref == probe_exit) probe_rep = -1;  // left the probed subtree without a hit
-    if (ref >= 0) {
-      const LbvhNode nd = bvh.nodes[ref];
-      const int32_t rope = bvh.rope_node[ref];  // with the node, not after it: half the chain of dependent loads
-      node_tests++;
-      const bool hit = (nd.lo[0] - r <= q.x) & (q.x <= nd.hi[0] + r) & (nd.lo[1] - r <= q.y) & (q.y <= nd.hi[1] + r) &
-                       (nd.lo[2] - r <= q.z) & (q.z <= nd.hi[2] + r);
-      if (!hit) {
-        ref = rope;
-        continue;
-      }
-      const bool probing = probe_rep >= 0;
-      if (probing || node_is_tight(nd, a.eps_in2)) {
-        const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
-        const int32_t s = a.next_core[first];
-        if (s > last || (first <= own_slot && own_slot <= last)) {  // no core point here / my own group
-          ref = rope;
-          continue;
-        }
-        if (!probing && settled(s)) {
-          ref = rope;
-          continue;
-        }
-        float far2, near2;
-        box_dist2(nd, q, far2, near2);
-        if (far2 <= a.eps_in2) {  // every point of the node is within eps
-          f(probing ? probe_rep : s);
-          ref = probing ? probe_exit : rope;
-          probe_rep = -1;
-          continue;
-        }
-        if (near2 > a.eps_out2) {  // none is
-          ref = rope;
-          continue;
-        }
-        if (!probing) {
-          probe_rep = s;
-          probe_exit = rope;
-        }
-      }
-      ref = lbvh_left_ref(ref, nd);
-    } else {
-      const int32_t slot = ~ref;
-      const uint8_t is_core = a.core_sorted[slot];  // three independent loads at once (nearly every leaf reached is core)
-      const LbvhPoint p = bvh.points[slot];
-      const int32_t rope = bvh.rope_leaf[slot];
-      if (is_core && slot != own_slot) {
-        point_tests++;
-        if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) {
-          if (probe_rep >= 0) {
-            f(probe_rep);
-            ref = probe_exit;
-            probe_rep = -1;
-            continue;
+  auto arrive = [&](int32_t ref) { probe_rep = ref == probe_exit ? -1 : probe_rep; };  // left the probed subtree without a hit
+  auto found = [&]() {  // the probe's answer: its group is within eps, on behind its subtree
+    f(probe_rep);
+    probe_rep = -1;
+    return lane_goto(probe_exit);
+  };
+  // (the rope with the node, and at a leaf three independent loads at once -- nearly every leaf reached is core)
+  lane_walk<LaneRope::kWithNode>(bvh,
+      [&](int32_t ref, const LbvhNode &nd, int32_t rope) {
+        arrive(ref);
+        node_tests++;
+        if (!lane_box_hit(nd, q, r)) return lane_rope();
+        const bool probing = probe_rep >= 0;
+        if (probing || node_is_tight(nd, a.eps_in2)) {
+          const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
+          const int32_t s = a.next_core[first];
+          if (s > last || (first <= own_slot && own_slot <= last)) return lane_rope();  // no core point here / my own group
+          if (!probing && settled(s)) return lane_rope();
+          float far2, near2;
+          lane_box_dist2(nd, q, far2, near2);
+          if (far2 <= a.eps_in2) {  // every point of the node is within eps
+            if (probing) return found();
+            f(s);
+            return lane_rope();
           }
-          f(slot);
+          if (near2 > a.eps_out2) return lane_rope();  // none is
+          if (!probing) probe_rep = s, probe_exit = rope;
         }
-      }
-      ref = rope;
-    }
-  }
+        return lane_descend();
+      },
+      [&](int32_t slot, const LbvhPoint &p) {
+        arrive(~slot);
+        if (a.core_sorted[slot] && slot != own_slot) {
+          point_tests++;
+          if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) {
+            if (probe_rep >= 0) return found();
+            f(slot);
+          }
+        }
+        return lane_rope();
+      });
 }
 
 // Core flags.  Every point first looks at its GROUP, the first tight node on its own root path (db_group_kernel): its
@@ -245,7 +216,7 @@ __device__ __forceinline__ void db_core_body(const DbArgs &a, int32_t t, uint32_
   const LbvhPoint q = bvh.points[t];
   int32_t cnt = 0;
   const int stop_at = a.want_counts ? 0x7fffffff : a.min_pts;
-  const int32_t clean_end = bvh.n - (bvh.nan_count ? *bvh.nan_count : 0);  // NaN points sort last
+  const int32_t clean_end = lane_clean_end(bvh);
   const float r = a.eps_wide;
   int32_t ref = bvh.root;
   // the last nodes above my group on my root path (anc[0]: kNear levels above it).  A point whose group is too small to
@@ -300,26 +271,17 @@ __device__ __forceinline__ void db_core_body(const DbArgs &a, int32_t t, uint32_
     if (a.near_node) a.near_node[t] = anc[0];
   }
   if (TKNN_DIAG_BUILD && (a.diag & 64)) ref = LBVH_END;  // (times only) no neighbour count
-  // rope walk from `from` until the walk would leave through `until` (the rope of the subtree's root; LBVH_END: the whole tree)
+  // the count over the subtree `from` .. `until`, the subtree `skip` stepped over (lane_walk); it ends at stop_at neighbours
+  // (every call starts below that).  The rope is fetched WITH the node, not after the box test has asked for it.
   auto count_from = [&](int32_t from, int32_t until, int32_t skip, int32_t skip_rope) {
-    int32_t at = from;
-    while (at != until && cnt < stop_at) {
-      if (at == skip) {  // the subtree counted already
-        at = skip_rope;
-        continue;
-      }
-      if (at >= 0) {
-        // the rope is fetched WITH the node, not after the box test has asked for it: a walk is a chain of dependent loads
-        // (a wave lives as long as its longest walk), and this halves the chain for four more bytes per step
-        const LbvhNode nd = bvh.nodes[at];
-        const int32_t rope = bvh.rope_node[at];
-        node_tests++;
-        const bool hit = (nd.lo[0] - r <= q.x) & (q.x <= nd.hi[0] + r) & (nd.lo[1] - r <= q.y) & (q.y <= nd.hi[1] + r) &
-                         (nd.lo[2] - r <= q.z) & (q.z <= nd.hi[2] + r);
-        if (hit) {
+    auto on = [&]() { return cnt < stop_at ? lane_rope() : lane_stop(); };
+    lane_walk<LaneRope::kWithNode>(bvh, from, until, skip, skip_rope,
+        [&](int32_t at, const LbvhNode &nd, int32_t) {
+          node_tests++;
+          if (!lane_box_hit(nd, q, r)) return lane_rope();
           // a node inside the sphere is counted, not walked
           float far2, near2;
-          box_dist2(nd, q, far2, near2);
+          lane_box_dist2(nd, q, far2, near2);
           const int32_t first = lbvh_first(at, nd.other), last = lbvh_last(at, nd.other);
           // (a node that holds my own slot while a subtree is being stepped over is an ANCESTOR of that subtree -- the subtree
           // itself is stepped over before it gets here, its descendants are never reached --: its points were counted in part
@@ -327,19 +289,15 @@ __device__ __forceinline__ void db_core_body(const DbArgs &a, int32_t t, uint32_
           const bool over_skipped = skip != LBVH_END && first <= t && t <= last;
           if (far2 <= a.eps_in2 && last < clean_end && !over_skipped) {
             cnt += last - first + 1;
-            at = rope;
-            continue;
+            return on();
           }
-        }
-        at = hit ? lbvh_left_ref(at, nd) : rope;
-      } else {
-        const int32_t slot = ~at;
-        const LbvhPoint p = bvh.points[slot];
-        point_tests++;
-        if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) cnt++;
-        at = bvh.rope_leaf[slot];
-      }
-    }
+          return lane_descend();
+        },
+        [&](int32_t, const LbvhPoint &p) {
+          point_tests++;
+          if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) cnt++;
+          return on();
+        });
   };
   if (ref != LBVH_END) {
     const int32_t near = anc[0];
@@ -1397,43 +1355,24 @@ __device__ __forceinline__ bool db_has_core_neighbour(const DbArgs &a, const Lbv
                                                       int32_t skip_rope, uint32_t &node_tests, uint32_t &point_tests) {
   const LbvhView &bvh = a.bvh;
   const float r = a.eps_wide;
-  int32_t ref = from;
-  while (ref != until) {
-    if (ref == skip) {  // the subtree searched already
-      ref = skip_rope;
-      continue;
-    }
-    if (ref >= 0) {
-      const LbvhNode nd = bvh.nodes[ref];
-      const int32_t rope = bvh.rope_node[ref];  // with the node: half the chain of dependent loads
-      node_tests++;
-      const bool hit = (nd.lo[0] - r <= q.x) & (q.x <= nd.hi[0] + r) & (nd.lo[1] - r <= q.y) & (q.y <= nd.hi[1] + r) &
-                       (nd.lo[2] - r <= q.z) & (q.z <= nd.hi[2] + r);
-      if (!hit || a.next_core[lbvh_first(ref, nd.other)] > lbvh_last(ref, nd.other)) {  // out of reach, or no core point below
-        ref = rope;
-        continue;
-      }
-      float far2, near2;
-      box_dist2(nd, q, far2, near2);
-      if (far2 <= a.eps_in2) return true;  // all of it within eps, and a core point among it
-      if (near2 > a.eps_out2) {
-        ref = rope;
-        continue;
-      }
-      ref = lbvh_left_ref(ref, nd);
-    } else {
-      const int32_t slot = ~ref;
-      const uint8_t is_core = a.core_sorted[slot];
-      const LbvhPoint p = bvh.points[slot];
-      const int32_t rope = bvh.rope_leaf[slot];
-      if (is_core) {
-        point_tests++;
-        if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) return true;
-      }
-      ref = rope;
-    }
-  }
-  return false;
+  // (the rope with the node: half the chain of dependent loads; the walk stops at the first core neighbour)
+  return lane_walk<LaneRope::kWithNode>(bvh, from, until, skip, skip_rope,
+      [&](int32_t ref, const LbvhNode &nd, int32_t) {
+        node_tests++;
+        // out of reach, or no core point below
+        if (!lane_box_hit(nd, q, r) || a.next_core[lbvh_first(ref, nd.other)] > lbvh_last(ref, nd.other)) return lane_rope();
+        float far2, near2;
+        lane_box_dist2(nd, q, far2, near2);
+        if (far2 <= a.eps_in2) return lane_stop();  // all of it within eps, and a core point among it
+        return near2 > a.eps_out2 ? lane_rope() : lane_descend();
+      },
+      [&](int32_t slot, const LbvhPoint &p) {
+        if (a.core_sorted[slot]) {
+          point_tests++;
+          if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) return lane_stop();
+        }
+        return lane_rope();
+      });
 }
 // ... first in the subtree a few levels above the point's own group (the core-flag kernel has left its root in near_node): a
 // point that is not noise has its core neighbour next to it, and a walk from the root spends two dozen steps getting there

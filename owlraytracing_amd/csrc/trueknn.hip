@@ -1,13 +1,14 @@
 // trueknn.hip -- the TrueKNN engine behind include/owlknn.h: LBVH build, the per-round "lane"
-// kernel (one query per lane, stackless rope traversal) and the result writers.  The persistent
-// wave-packet kernel lives in trueknn_wave.hip.
+// kernel and the exact repair (one query per lane, the stackless rope traversal of lane_walk.h) and
+// the result writers.  The persistent wave-packet kernel lives in trueknn_wave.hip.
 //
 // Reference functions this file replaces (samples/s01-trueknn):
 //   deviceCode.cu:140-153  __raygen__rayGen            -> active test + point query per lane
-//   owl_device.h:150-174   optixTrace (RT cores)       -> rope traversal of the LBVH
+//   owl_device.h:150-174   optixTrace (RT cores)       -> rope traversal of the LBVH (lane_walk.h)
 //   deviceCode.cu:62-138   __intersection__Spheres     -> box test + register k-list insert
 //   hostCode.cpp:285-340   round loop                  -> Engine::solve_lane
 #include "knn_thresholds.h"  // knn_gate_from_worst
+#include "lane_walk.h"
 #include "trueknn_engine.h"
 
 #include <algorithm>
@@ -21,7 +22,6 @@ namespace owlmi {
 namespace {
 
 constexpr int kLaneBlock = 256;
-constexpr int kCountedSubtree = 32;  // smallest subtree the lane kernel tries to count instead of walking
 
 struct LaneRoundArgs {
   LbvhView bvh;
@@ -71,7 +71,7 @@ __device__ __forceinline__ void write_row(const LaneRoundArgs &a, int32_t row, c
   if (a.out_level) a.out_level[row] = a.level;
 }
 
-// SUBTREES: count fully covered subtrees beyond the gate instead of walking them (see below).  In a
+// SUBTREES: count fully covered subtrees beyond the gate instead of walking them (lane_counts_subtree, lane_walk.h).  In a
 // wave some lane is at a large node most of the time, so the test is paid on most steps: launches
 // whose boxes hold few points run without it (Engine::lane_rounds decides per round).
 template <int K, bool SUBTREES>
@@ -91,59 +91,32 @@ __global__ void __launch_bounds__(kLaneBlock) lane_round_kernel(LaneRoundArgs a)
   float tau2 = INFINITY;  // squared-distance gate from the list's last entry: beyond it nothing enters
   for (int tree = 0; tree < 2; tree++) {
     const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
-    if (tv.n <= 0) continue;
-    const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-    int32_t ref = active ? tv.root : LBVH_END;
-    while (ref != LBVH_END) {
-      if (ref >= 0) {
-        const LbvhNode nd = tv.nodes[ref];
-        node_tests++;
-        // conservative: any point p in the node has lo <= c_p <= hi, and fp32 rounding is monotone,
-        // so fl(c_p - r) >= fl(lo - r) and fl(c_p + r) <= fl(hi + r)
-        bool hit = (nd.lo[0] - r <= q.x) & (q.x <= nd.hi[0] + r) & (nd.lo[1] - r <= q.y) &
-                   (q.y <= nd.hi[1] + r) & (nd.lo[2] - r <= q.z) & (q.z <= nd.hi[2] + r);
-        // The same monotonicity the other way round: if even the largest centre passes the lower
-        // test and the smallest the upper one, EVERY point of the node is a candidate
-        // (deviceCode.cu:74 would count each).  If, besides, none of them can enter the list any
-        // more -- the node lies beyond the gate -- the subtree is counted, not walked: a query
-        // whose box has grown over a whole cluster costs O(log n) instead of O(cluster).
-        // Only tried for subtrees of at least kCountedSubtree points: near the leaves the test would
-        // cost as much as the node test itself and save nothing.
-        const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
-        const bool inside = SUBTREES && hit && last - first + 1 >= kCountedSubtree && (nd.hi[0] - r <= q.x) & (q.x <= nd.lo[0] + r) &
-                                       (nd.hi[1] - r <= q.y) & (q.y <= nd.lo[1] + r) & (nd.hi[2] - r <= q.z) & (q.z <= nd.lo[2] + r);
-        if (inside) {
-          const float gx = fmaxf(fmaxf(nd.lo[0] - q.x, q.x - nd.hi[0]), 0.f);
-          const float gy = fmaxf(fmaxf(nd.lo[1] - q.y, q.y - nd.hi[1]), 0.f);
-          const float gz = fmaxf(fmaxf(nd.lo[2] - q.z, q.z - nd.hi[2]), 0.f);
-          const float m2 = (gx * gx + gy * gy) + gz * gz;  // <= every point's squared distance, up to rounding
-          // 5e-6 covers the roundings of m2 and of the points' own distance arithmetic; a node that
-          // holds the query itself has m2 = 0 and is never skipped, so `others` stays right
-          if (m2 * 0.999995f > tau2 && last < clean_end) {
-            const int32_t c = last - first + 1;
-            cnt += c;
-            others += c;
-            ref = tv.rope_node[ref];
-            continue;
+    if (tv.n <= 0 || !active) continue;
+    const int32_t clean_end = lane_clean_end(tv);
+    lane_walk<LaneRope::kWhenTaken>(tv,
+        [&](int32_t ref, const LbvhNode &nd, int32_t) {
+          node_tests++;
+          const bool hit = lane_box_hit(nd, q, r);
+          int32_t c;
+          if (SUBTREES && hit && lane_counts_subtree(ref, nd, q, r, tau2, clean_end, c)) {
+            cnt += c, others += c;
+            return lane_rope();
           }
-        }
-        ref = hit ? lbvh_left_ref(ref, nd) : tv.rope_node[ref];
-      } else {
-        const int32_t slot = ~ref;
-        const LbvhPoint p = tv.points[slot];
-        point_tests++;
-        if (knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z)) {
-          cnt++;                 // deviceCode.cu:74
-          if (p.id != q.id) {    // deviceCode.cu:103
-            others++;
-            float d = knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z));
-            list.insert(knn_key(d, p.id));
-            if (SUBTREES) tau2 = knn_gate_from_worst(knn_key_dist(list.worst()));
+          return hit ? lane_descend() : lane_rope();
+        },
+        [&](int32_t, const LbvhPoint &p) {
+          point_tests++;
+          if (knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z)) {
+            cnt++;                 // deviceCode.cu:74
+            if (p.id != q.id) {    // deviceCode.cu:103
+              others++;
+              float d = knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z));
+              list.insert(knn_key(d, p.id));
+              if (SUBTREES) tau2 = knn_gate_from_worst(knn_key_dist(list.worst()));
+            }
           }
-        }
-        ref = tv.rope_leaf[slot];
-      }
-    }
+          return lane_rope();
+        });
   }
   int64_t isect = 0;
   bool finished = false;
@@ -241,21 +214,12 @@ __global__ void __launch_bounds__(kLaneBlock) repair_kernel(RepairArgs a) {
   for (int tree = 0; tree < 2; tree++) {
     const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
     if (tv.n <= 0) continue;
-    int32_t ref = tv.root;
-    while (ref != LBVH_END) {
-      if (ref >= 0) {
-        const LbvhNode nd = tv.nodes[ref];
-        const bool hit = (nd.lo[0] - r <= q.x) & (q.x <= nd.hi[0] + r) & (nd.lo[1] - r <= q.y) &
-                         (q.y <= nd.hi[1] + r) & (nd.lo[2] - r <= q.z) & (q.z <= nd.hi[2] + r);
-        ref = hit ? lbvh_left_ref(ref, nd) : tv.rope_node[ref];
-      } else {
-        const int32_t slot = ~ref;
-        const LbvhPoint p = tv.points[slot];
-        if (p.id != q.id && knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z))
-          list.insert(knn_key(knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)), p.id));
-        ref = tv.rope_leaf[slot];
-      }
-    }
+    lane_walk<LaneRope::kWhenTaken>(tv, [&](int32_t, const LbvhNode &nd, int32_t) { return lane_box_hit(nd, q, r) ? lane_descend() : lane_rope(); },
+        [&](int32_t, const LbvhPoint &p) {
+          if (p.id != q.id && knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z))
+            list.insert(knn_key(knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)), p.id));
+          return lane_rope();
+        });
   }
   bool changed = false;
 #pragma unroll

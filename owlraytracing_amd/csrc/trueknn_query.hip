@@ -11,11 +11,12 @@
 //      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
 //   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
 //      walk of team_walk_kernel (trueknn_team.hip; both on team_walk.h) without anything that is per slot;
-//   3. query_lane_kernel: one query per lane, rope traversal, keys that carry the level -- for the few queries
+//   3. query_lane_kernel: one query per lane, rope traversal (lane_walk.h), keys that carry the level -- for the few queries
 //      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
 //   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).
 #include "curve_key.h"
 #include "knn_thresholds.h"  // knn_gate_from_worst
+#include "lane_walk.h"
 #include "team_lanes.h"
 #include "team_walk.h"
 #include "trueknn_engine.h"
@@ -35,7 +36,6 @@ namespace {
 constexpr int kQueryBlock = 64;       // one wave per workgroup, four teams
 constexpr int kQueryBlocksPerCu = 16;  // 7.3 KB of LDS each: far inside what a CU holds
 constexpr int kLaneBlock = 256;
-constexpr int kCountedSubtree = 32;   // smallest subtree the lane kernel tries to count instead of walking
 constexpr int kCodeBits = 30;         // ten bits per axis order 10 M queries well enough, and sort in half the passes
 
 // words of the call's own counters (in the workspace, zeroed per pass)
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(kQueryBlock) __attribute__((amdgpu_waves_per_e
   walk_fill_levels<1>(levels, &a.wide, lane);
   t_wave_sync();
   const LbvhWideView &wv = a.wide;
-  const int32_t clean_end = a.bvh.n - (a.bvh.nan_count ? *a.bvh.nan_count : 0);  // NaN points sort last
+  const int32_t clean_end = lane_clean_end(a.bvh);
   unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
   unsigned int unfinished = 0, failed = 0, tied_rows = 0;
   int max_level = 0;
@@ -260,8 +260,8 @@ __global__ void __launch_bounds__(kLaneBlock) query_lane_kernel(QueryKernelArgs 
   const bool has_q = t < (int64_t)a.ws[kWsRedo];
   const int32_t qi = has_q ? a.redo[t] : 0;
   const LbvhView &tv = a.bvh;
-  const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-  const float qx = a.queries[3 * (int64_t)qi], qy = a.queries[3 * (int64_t)qi + 1], qz = a.queries[3 * (int64_t)qi + 2];
+  const int32_t clean_end = lane_clean_end(tv);
+  const LbvhPoint q = {a.queries[3 * (int64_t)qi], a.queries[3 * (int64_t)qi + 1], a.queries[3 * (int64_t)qi + 2], -1};  // no self
   float r = a.start_radius;
   bool active = has_q;
   if (a.exact) {
@@ -277,46 +277,30 @@ __global__ void __launch_bounds__(kLaneBlock) query_lane_kernel(QueryKernelArgs 
   while (active) {
     list.clear();
     int32_t cnt = 0;
-    int32_t ref = tv.root;
-    while (ref != LBVH_END) {
-      if (ref >= 0) {
-        const LbvhNode nd = tv.nodes[ref];
-        node_tests++;
-        // conservative: rounding is monotone, so a point of the node passes only if the node's corners do (lane_round_kernel)
-        const bool hit = (nd.lo[0] - r <= qx) & (qx <= nd.hi[0] + r) & (nd.lo[1] - r <= qy) & (qy <= nd.hi[1] + r) &
-                         (nd.lo[2] - r <= qz) & (qz <= nd.hi[2] + r);
-        // The same monotonicity the other way round: if even the largest centre passes the lower test and the smallest the
-        // upper one, every point of the node is a candidate; if the node also lies beyond the list's gate none of them can
-        // enter the list or tie with its last entry, and the subtree is counted, not walked (lane_round_kernel, trueknn.hip)
-        const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
-        if (hit && last - first + 1 >= kCountedSubtree && (nd.hi[0] - r <= qx) & (qx <= nd.lo[0] + r) & (nd.hi[1] - r <= qy) &
-                                                           (qy <= nd.lo[1] + r) & (nd.hi[2] - r <= qz) & (qz <= nd.lo[2] + r)) {
-          const float gx = fmaxf(fmaxf(nd.lo[0] - qx, qx - nd.hi[0]), 0.f), gy = fmaxf(fmaxf(nd.lo[1] - qy, qy - nd.hi[1]), 0.f),
-                      gz = fmaxf(fmaxf(nd.lo[2] - qz, qz - nd.hi[2]), 0.f);
-          const float m2 = (gx * gx + gy * gy) + gz * gz;  // <= every point's squared distance, up to rounding
-          if (m2 * 0.999995f > knn_gate_from_worst(__uint_as_float(list.d[K - 1])) && last < clean_end) {
-            cnt += last - first + 1;
-            ref = tv.rope_node[ref];
-            continue;
+    lane_walk<LaneRope::kWhenTaken>(tv,
+        [&](int32_t ref, const LbvhNode &nd, int32_t) {
+          node_tests++;
+          const bool hit = lane_box_hit(nd, q, r);
+          int32_t c;  // a subtree of candidates that can neither enter the list nor tie with its last entry is counted
+          if (hit && lane_counts_subtree(ref, nd, q, r, knn_gate_from_worst(__uint_as_float(list.d[K - 1])), clean_end, c)) {
+            cnt += c;
+            return lane_rope();
           }
-        }
-        ref = hit ? lbvh_left_ref(ref, nd) : tv.rope_node[ref];
-      } else {
-        const int32_t slot = ~ref;
-        const LbvhPoint p = tv.points[slot];
-        point_tests++;
-        if (knn_in_box(p.x, p.y, p.z, r, qx, qy, qz)) {
-          cnt++;
-          // the first level whose box held the query (not beyond this one: its test has just passed)
-          uint32_t first = 0;
-          if (!a.exact)
-            for (float rr = a.start_radius; (int)first < level && !knn_in_box(p.x, p.y, p.z, rr, qx, qy, qz); rr = rr * 2.0f) first++;
-          const float d = knn_sqrt(knn_dist2(p.x, p.y, p.z, qx, qy, qz));
-          list.insert(__float_as_uint(d), ((uint64_t)first << 32) | (uint32_t)p.id);
-        }
-        ref = tv.rope_leaf[slot];
-      }
-    }
+          return hit ? lane_descend() : lane_rope();
+        },
+        [&](int32_t, const LbvhPoint &p) {
+          point_tests++;
+          if (knn_in_box(p.x, p.y, p.z, r, q.x, q.y, q.z)) {
+            cnt++;
+            // the first level whose box held the query (not beyond this one: its test has just passed)
+            uint32_t first = 0;
+            if (!a.exact)
+              for (float rr = a.start_radius; (int)first < level && !knn_in_box(p.x, p.y, p.z, rr, q.x, q.y, q.z); rr = rr * 2.0f) first++;
+            const float d = knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z));
+            list.insert(__float_as_uint(d), ((uint64_t)first << 32) | (uint32_t)p.id);
+          }
+          return lane_rope();
+        });
     isect += cnt;
     if (a.exact || cnt >= a.k) {
       const int64_t base = (int64_t)qi * a.k;

@@ -330,6 +330,12 @@ def test_threaded_spec_equals_the_serial_spec():
     xyz = datasets.gaussian_mixture3d(120_000, components=64, sigma=0.02, seed=1)
     a, b = oracle.dbscan(xyz, float(np.float32(0.01)), 4), oracle.dbscan_threaded(xyz, float(np.float32(0.01)), 4)
     assert np.array_equal(a["labels"], b["labels"]) and np.array_equal(a["core"], b["core"])
+    # a point with a NaN coordinate is nobody's neighbour: noise in both, whatever eps (the growth rounds of dbscan_auto are threaded runs)
+    xyz = datasets.uniform3d(17, seed=117)
+    xyz[8, 1] = np.nan
+    for eps in (0.05, 0.8, 4.0):
+        a, b = oracle.dbscan(xyz, eps, 2), oracle.dbscan_threaded(xyz, eps, 2)
+        assert a["labels"][8] == -1 and np.array_equal(a["labels"], b["labels"]) and np.array_equal(a["core"], b["core"]), eps
 
 
 @pytest.mark.gpu
