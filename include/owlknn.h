@@ -279,6 +279,35 @@ TKNN_API int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels,
 TKNN_API int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32_t *d_labels,
                               tknnDbscanInfo *info, void *stream);
 
+/* ---- cluster labels for points that are not in the set ---------------------------------------------------------
+ * tknnDbscan and tknnDbscanAssign answer for the points of the built set P.  tknnDbscanQuery answers for m arbitrary
+ * points Q against the tree of P and a clustering of P the caller hands in as d_core_label (by row, as
+ * tknnDbscanAssign takes it: >= 0 core with that label, < 0 not core; core points within eps of each other must carry
+ * the same label).  With dist the fp32 formula sqrt((dx*dx + dy*dy) + dz*dz) of every RT-DBSCAN kernel:
+ *   d_labels[j]  the smallest d_core_label[p] over the core points p of P with dist(p, q_j) <= eps, -1 if there is
+ *                none (the rule by which a border point joins the lowest-numbered adjacent cluster)
+ *   d_counts[j]  the number of points p of P, core or not, with dist(p, q_j) <= eps.  Whether q_j would be core itself
+ *                (d_counts[j] + 1 >= min_pts) is the caller's to decide: the call takes no min_pts.
+ * There is no self: a point of P that coincides with q_j is an ordinary neighbour at distance 0, so with Q = P the
+ * labels are tknnDbscan's labels and the counts its d_counts.  A query with a NaN coordinate gets label -1 and count 0;
+ * NaN points of P are nobody's neighbour.  Rows of P are rows, not ids; results are addressed by the caller's j
+ * whatever order the engine works in.  The tree, the state of tknnSolve and d_core_label are not modified; a halo tree,
+ * if set, is ignored as by the other RT-DBSCAN calls.  info is filled as tknnDbscanAssign fills it (clusters = -1,
+ * node_tests, point_tests, label_point_tests); label_ms is the traversal kernel alone, solve_ms the whole call with
+ * the ordering of the queries along the tree's curve.
+ * Errors, in this order: NULL engine / options / d_core_label / d_labels / d_queries with m > 0: TKNN_E_ARG; not
+ * built: TKNN_E_STATE; eps not finite-positive, m < 0 or m >= 2^31 - 1: TKNN_E_ARG.  m = 0 succeeds with a zeroed info. */
+typedef struct {
+  const float *d_queries;       /* m packed fp32 triples (2-D data: z = 0) */
+  int64_t m;
+  float eps;                    /* finite, > 0 */
+  int32_t reserved_;
+  const int32_t *d_core_label;  /* n, by row, as tknnDbscanAssign */
+  int32_t *d_labels;            /* m, required */
+  int32_t *d_counts;            /* m, may be NULL; asking for it adds the counted walk */
+} tknnDbscanQueryOptions;
+TKNN_API int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream);
+
 /* ---- RT-DBSCAN with an auto-grown eps (BASELINE.json configs[4]) ----------------------------------------------
  * No counterpart in the reference (it has no RT-DBSCAN source; BASELINE.md section 4: "spec TBD"), so the rule is this
  * build's own spec (oracle/dbscan_oracle.c, dbref_dbscan_auto), built on the reference's one growth rule, the radius

@@ -79,6 +79,18 @@ class QueryOptions(ctypes.Structure):
     ]
 
 
+class DbscanQueryOptions(ctypes.Structure):
+    _fields_ = [
+        ("d_queries", ctypes.c_void_p),
+        ("m", ctypes.c_int64),
+        ("eps", ctypes.c_float),
+        ("reserved_", ctypes.c_int32),
+        ("d_core_label", ctypes.c_void_p),
+        ("d_labels", ctypes.c_void_p),
+        ("d_counts", ctypes.c_void_p),
+    ]
+
+
 class DbscanInfo(ctypes.Structure):
     _fields_ = [("clusters", ctypes.c_int32), ("solve_ms", ctypes.c_float), ("core_ms", ctypes.c_float),
                 ("union_ms", ctypes.c_float), ("label_ms", ctypes.c_float), ("union_launches", ctypes.c_int32),
@@ -142,6 +154,7 @@ SIGNATURES = {
                                   ctypes.c_void_p, ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnDbscanAssign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
+    "tknnDbscanQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DbscanQueryOptions), ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnDbscanAuto": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.POINTER(DbscanAutoInfo), ctypes.c_void_p]),
     "tknnHaloSelectFixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,

@@ -1,7 +1,8 @@
 // db_workspace.h -- RT-DBSCAN's scratch (dbscan.hip) as byte offsets into the engine's workspace: one layout for the full
-// clustering (tknnDbscan, tknnDbscanAssign), one for a growth round (tknnDbscanNoise, the rounds of tknnDbscanAuto).  The
+// clustering (tknnDbscan, tknnDbscanAssign), one for a growth round (tknnDbscanNoise, the rounds of tknnDbscanAuto), one for
+// the labels of points that are not in the set (tknnDbscanQuery).  The
 // offsets are computed here and nowhere else; no HIP in this file (tests/test_db_workspace.py compiles it for the host).
-// n: points of the tree, one sorted slot each.  Words are int32.
+// n: points of the tree, one sorted slot each; m: query points of tknnDbscanQuery.  Words are int32.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -93,6 +94,32 @@ struct DbProbeWs {
     return w;
   }
   static size_t bytes(size_t n) { return of(n).end; }
+};
+
+// Labels for m points that are not in the set: core flags from the caller's labels, next_core, the queries' order along the
+// tree's curve (query_order.h), one traversal.  Nothing is shared.  The library's temporary storage (the sum over the
+// workgroups' counts, then the sort of the queries: one after the other, so the larger of the two) follows the layout as
+// it follows the others.
+struct DbQueryWs {
+  size_t pos;           // n + 1 words: slot of the r-th core point (+ a sentinel)
+  size_t next_core;     // n + 1 words
+  size_t block_places;  // db_block_places_bytes(n): core slots per workgroup and their sums
+  size_t core_sorted;   // n bytes: core flag per slot
+  size_t codes;         // m words: the queries' curve keys, caller order; query_code_kernel .. the sort
+  size_t codes_sorted;  // m words: the sort's other key column
+  size_t order_in;      // m words: 0 .. m - 1; query_code_kernel .. the sort
+  size_t order;         // m words: the caller's index of the query at each sorted position; the sort .. db_query_kernel
+  size_t end;
+
+  static DbQueryWs of(size_t n, size_t m) {
+    DbCarver c;
+    DbQueryWs w;
+    w.pos = c.take((n + 1) * 4), w.next_core = c.take((n + 1) * 4), w.block_places = c.take(db_block_places_bytes(n));
+    w.core_sorted = c.take(n), w.codes = c.take(m * 4), w.codes_sorted = c.take(m * 4), w.order_in = c.take(m * 4);
+    w.order = c.take(m * 4), w.end = c.end;
+    return w;
+  }
+  static size_t bytes(size_t n, size_t m) { return of(n, m).end; }
 };
 
 }  // namespace owlmi

@@ -27,6 +27,7 @@
 // would otherwise keep serving a stale parent and a failed CAS could retry forever.
 #include "db_workspace.h"
 #include "lane_walk.h"
+#include "query_order.h"
 #include "trueknn_engine.h"
 
 #include <hipcub/hipcub.hpp>
@@ -204,6 +205,38 @@ __device__ __forceinline__ void for_each_core_group(const DbArgs &a, const LbvhP
       });
 }
 
+// The counted neighbour walk: adds to `cnt` the points within eps of q over the subtree `from` .. `until`, the subtree `skip`
+// stepped over (lane_walk); it ends at stop_at neighbours (every call starts below that).  `own_slot`: q's sorted slot, or -1
+// for a q that is not in the tree.  The rope is fetched WITH the node, not after the box test has asked for it.
+__device__ __forceinline__ void db_count_from(const DbArgs &a, const LbvhPoint &q, int32_t own_slot, int32_t clean_end, int32_t stop_at, int32_t from,
+                                              int32_t until, int32_t skip, int32_t skip_rope, int32_t &cnt, uint32_t &node_tests, uint32_t &point_tests) {
+  const float r = a.eps_wide;
+  auto on = [&]() { return cnt < stop_at ? lane_rope() : lane_stop(); };
+  lane_walk<LaneRope::kWithNode>(a.bvh, from, until, skip, skip_rope,
+      [&](int32_t at, const LbvhNode &nd, int32_t) {
+        node_tests++;
+        if (!lane_box_hit(nd, q, r)) return lane_rope();
+        // a node inside the sphere is counted, not walked
+        float far2, near2;
+        lane_box_dist2(nd, q, far2, near2);
+        const int32_t first = lbvh_first(at, nd.other), last = lbvh_last(at, nd.other);
+        // (a node that holds my own slot while a subtree is being stepped over is an ANCESTOR of that subtree -- the subtree
+        // itself is stepped over before it gets here, its descendants are never reached --: its points were counted in part
+        // already, so it is walked, not added whole)
+        const bool over_skipped = skip != LBVH_END && first <= own_slot && own_slot <= last;
+        if (far2 <= a.eps_in2 && last < clean_end && !over_skipped) {
+          cnt += last - first + 1;
+          return on();
+        }
+        return lane_descend();
+      },
+      [&](int32_t, const LbvhPoint &p) {
+        point_tests++;
+        if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) cnt++;
+        return on();
+      });
+}
+
 // Core flags.  Every point first looks at its GROUP, the first tight node on its own root path (db_group_kernel): its
 // points are pairwise within eps, so if it holds minPts of them the point is core without looking any further.  (Listing the
 // points that do have to look and walking for them with full waves, as the label pass does, was tried: on BASELINE config 3
@@ -217,7 +250,6 @@ __device__ __forceinline__ void db_core_body(const DbArgs &a, int32_t t, uint32_
   int32_t cnt = 0;
   const int stop_at = a.want_counts ? 0x7fffffff : a.min_pts;
   const int32_t clean_end = lane_clean_end(bvh);
-  const float r = a.eps_wide;
   int32_t ref = bvh.root;
   // the last nodes above my group on my root path (anc[0]: kNear levels above it).  A point whose group is too small to
   // decide looks for its minPts neighbours there FIRST: they are next to it, a walk from the root spends two dozen steps
@@ -271,33 +303,8 @@ __device__ __forceinline__ void db_core_body(const DbArgs &a, int32_t t, uint32_
     if (a.near_node) a.near_node[t] = anc[0];
   }
   if (TKNN_DIAG_BUILD && (a.diag & 64)) ref = LBVH_END;  // (times only) no neighbour count
-  // the count over the subtree `from` .. `until`, the subtree `skip` stepped over (lane_walk); it ends at stop_at neighbours
-  // (every call starts below that).  The rope is fetched WITH the node, not after the box test has asked for it.
   auto count_from = [&](int32_t from, int32_t until, int32_t skip, int32_t skip_rope) {
-    auto on = [&]() { return cnt < stop_at ? lane_rope() : lane_stop(); };
-    lane_walk<LaneRope::kWithNode>(bvh, from, until, skip, skip_rope,
-        [&](int32_t at, const LbvhNode &nd, int32_t) {
-          node_tests++;
-          if (!lane_box_hit(nd, q, r)) return lane_rope();
-          // a node inside the sphere is counted, not walked
-          float far2, near2;
-          lane_box_dist2(nd, q, far2, near2);
-          const int32_t first = lbvh_first(at, nd.other), last = lbvh_last(at, nd.other);
-          // (a node that holds my own slot while a subtree is being stepped over is an ANCESTOR of that subtree -- the subtree
-          // itself is stepped over before it gets here, its descendants are never reached --: its points were counted in part
-          // already, so it is walked, not added whole)
-          const bool over_skipped = skip != LBVH_END && first <= t && t <= last;
-          if (far2 <= a.eps_in2 && last < clean_end && !over_skipped) {
-            cnt += last - first + 1;
-            return on();
-          }
-          return lane_descend();
-        },
-        [&](int32_t, const LbvhPoint &p) {
-          point_tests++;
-          if (knn_sqrt(knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z)) <= a.eps) cnt++;
-          return on();
-        });
+    db_count_from(a, q, t, clean_end, stop_at, from, until, skip, skip_rope, cnt, node_tests, point_tests);
   };
   if (ref != LBVH_END) {
     const int32_t near = anc[0];
@@ -1346,6 +1353,48 @@ __global__ void __launch_bounds__(kDbBlock) db_assign_kernel(DbArgs a, const int
   db_add_stats(a.stats + kDbStatLabel, blk_stats, node_tests, point_tests);
 }
 
+// tknnDbscanQuery: the same two questions for points that are NOT in the tree.  One query per lane, the lanes of a wave = 64
+// queries that follow each other on the tree's curve (query_order.h); results go to the caller's index order[i].  The label:
+// the smallest caller-decided label among the core points within eps (for_each_core_group without a slot of its own: nothing is
+// "self", a point of the set that coincides with the query is a neighbour at distance 0); a tree without a core point is not
+// walked.  The count, if asked for: db_count_from over the whole tree, no early stop.  A query with a NaN coordinate fails every
+// box test and every distance test: label -1, count 0.
+struct DbQueryArgs {
+  const float *queries;   // m packed triples, caller order
+  const uint32_t *order;  // m: the query worked on at sorted position i
+  int32_t m;
+  const int32_t *core_label;  // n, by row
+  int32_t *labels;            // m
+  int32_t *counts;            // m, or null
+};
+__global__ void __launch_bounds__(kDbBlock) db_query_kernel(DbArgs a, DbQueryArgs qa) {
+  __shared__ unsigned long long blk_stats[2];
+  if (threadIdx.x < 2) blk_stats[threadIdx.x] = 0ull;
+  __syncthreads();
+  uint32_t node_tests = 0, point_tests = 0;
+  const int64_t i = (int64_t)blockIdx.x * kDbBlock + threadIdx.x;
+  if (i < (int64_t)qa.m) {
+    const int64_t j = (int64_t)qa.order[i];
+    const LbvhPoint q = {qa.queries[3 * j], qa.queries[3 * j + 1], qa.queries[3 * j + 2], -1};
+    int32_t best = -1;
+    if (a.next_core[0] < a.bvh.n)
+      for_each_core_group(
+          a, q, -1, [](int32_t) { return false; },
+          [&](int32_t other) {
+            const int32_t l = qa.core_label[a.bvh.prim_id[other]];  // a tight node's core points share one label: its first stands for all
+            if (best < 0 || l < best) best = l;
+          },
+          node_tests, point_tests);
+    qa.labels[j] = best;
+    if (qa.counts) {
+      int32_t cnt = 0;
+      db_count_from(a, q, -1, lane_clean_end(a.bvh), 0x7fffffff, a.bvh.root, LBVH_END, LBVH_END, LBVH_END, cnt, node_tests, point_tests);
+      qa.counts[j] = cnt;
+    }
+  }
+  db_add_stats(a.stats + kDbStatLabel, blk_stats, node_tests, point_tests);
+}
+
 // ---- "eps auto-grown" (tknnDbscanAuto; spec: oracle/dbscan_oracle.c, dbref_dbscan_auto) ----------------------------
 // A round of the growth loop only has to COUNT the noise points: is there a core point within eps of a point that is
 // not core itself?  One traversal with an early exit; a subtree without a core point (next_core) is skipped, a node
@@ -1587,14 +1636,16 @@ struct Engine::DbCall {
     // every point's group, for the union pass; kept in the caller's label array, which is written last
     a.group_of = groups_wanted ? d_labels : nullptr;
     a.diag_out = e.counters_ + kDbDiag;
-    if (e.db_side_pending_) {
-      // a call that threw between its side launch and its rejoin has left db_border_walk_kernel running on the workspace
-      // and the counters this call is about to reset: nothing of this call before that kernel has ended
-      OWLMI_HIP(hipStreamWaitEvent(s, e.ev_side_b_, 0));
-      e.db_side_pending_ = false;
-    }
+    join_side();
     reset_counters();
     OWLMI_HIP(hipEventRecord(e.ev_a_, s));
+  }
+  void join_side() {
+    if (!e.db_side_pending_) return;
+    // a call that threw between its side launch and its rejoin has left db_border_walk_kernel running on the workspace
+    // and the counters this call is about to reset: nothing of this call before that kernel has ended
+    OWLMI_HIP(hipStreamWaitEvent(s, e.ev_side_b_, 0));
+    e.db_side_pending_ = false;
   }
   void core_flags() {
     // the flags BY ROW are written by the label kernel, which scatters to the rows anyway: a one-byte store at the
@@ -1749,6 +1800,41 @@ struct Engine::DbCall {
     info->node_tests = (int64_t)e.h_counters_[kDbStatLabel];
     info->point_tests = info->label_point_tests = (int64_t)e.h_counters_[kDbStatLabel + 1];
   }
+  // tknnDbscanQuery: the core flags and next_core as assign() makes them, the queries put in order along the tree's curve,
+  // one traversal for their labels (and counts).  The tree, the solve state and core_label are only read.
+  void query(float eps, const float *d_queries, int64_t m, const int32_t *core_label, int32_t *d_labels, int32_t *d_counts, tknnDbscanInfo *info) {
+    const size_t sort_bytes = query_order_sort_bytes(m, s);
+    scan_bytes = std::max(scan_bytes, sort_bytes);  // one after the other in the same place
+    const DbQueryWs w = DbQueryWs::of((size_t)n, (size_t)m);
+    reserve(w.end);
+    a = common;
+    set_eps(eps);
+    a.rank = db_at<int32_t>(ws, w.pos), a.next_core = next_core = db_at<int32_t>(ws, w.next_core);
+    a.core_sorted = db_at<uint8_t>(ws, w.core_sorted), block_places = db_at<int32_t>(ws, w.block_places);
+    uint32_t *order = db_at<uint32_t>(ws, w.order);
+    join_side();
+    reset_counters();
+    OWLMI_HIP(hipEventRecord(e.ev_a_, s));
+    hipLaunchKernelGGL(db_core_from_labels_kernel, dim3(blocks), dim3(kDbBlock), 0, s, a, core_label);
+    build_next_core(true, nullptr);
+    OWLMI_HIP(hipGetLastError());
+    query_order(d_queries, m, e.bvh_.scene_device(), e.bvh_.curve(), db_at<uint32_t>(ws, w.codes), db_at<uint32_t>(ws, w.codes_sorted),
+                db_at<uint32_t>(ws, w.order_in), order, scan_tmp, sort_bytes, s);
+    OWLMI_HIP(hipEventRecord(e.ev_c_, s));
+    const DbQueryArgs qa = {d_queries, order, (int32_t)m, core_label, d_labels, d_counts};
+    hipLaunchKernelGGL(db_query_kernel, dim3((unsigned)((m + kDbBlock - 1) / kDbBlock)), dim3(kDbBlock), 0, s, a, qa);
+    OWLMI_HIP(hipGetLastError());
+    OWLMI_HIP(hipEventRecord(e.ev_b_, s));
+    OWLMI_HIP(hipStreamSynchronize(s));
+    e.db_read_stats(s);
+    if (!info) return;
+    std::memset(info, 0, sizeof *info);
+    info->clusters = -1;
+    OWLMI_HIP(hipEventElapsedTime(&info->solve_ms, e.ev_a_, e.ev_b_));
+    OWLMI_HIP(hipEventElapsedTime(&info->label_ms, e.ev_c_, e.ev_b_));
+    info->node_tests = (int64_t)e.h_counters_[kDbStatLabel];
+    info->point_tests = info->label_point_tests = (int64_t)e.h_counters_[kDbStatLabel + 1];
+  }
   void cluster_info(tknnDbscanInfo *info) const;
   void print_diagnostics() const;
 };
@@ -1855,6 +1941,12 @@ void Engine::dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, 
     c.cluster_info(info);
     c.print_diagnostics();
   }
+}
+
+void Engine::dbscan_query(float eps, const float *d_queries, int64_t m, const int32_t *core_label, int32_t *d_labels, int32_t *d_counts,
+                          tknnDbscanInfo *info, hipStream_t s) {
+  DbCall c(*this, 1, s);
+  c.query(eps, d_queries, m, core_label, d_labels, d_counts, info);
 }
 
 // tknnDbscanAuto: the growth loop of the spec -- rounds of (core flags of the points not core yet, noise probe of the

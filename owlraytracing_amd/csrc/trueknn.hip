@@ -886,6 +886,22 @@ int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32
   });
 }
 
+int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream) {
+  if (!e || !options || !options->d_core_label || !options->d_labels || (options->m > 0 && !options->d_queries)) {
+    g_last_error = "tknnDbscanQuery: engine, options, core labels, labels and (for m > 0) the queries are required";
+    return TKNN_E_ARG;
+  }
+  return guarded_on(e, [&] {
+    const tknnDbscanQueryOptions &o = *options;
+    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscanQuery: call tknnBuild first"};
+    if (!(o.eps > 0.f) || !std::isfinite(o.eps)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanQuery: eps must be finite and > 0"};
+    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanQuery: need 0 <= m < 2^31-1"};
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (o.m == 0) return;
+    e->impl.dbscan_query(o.eps, o.d_queries, o.m, o.d_core_label, o.d_labels, o.d_counts, info, (hipStream_t)stream);
+  });
+}
+
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, void *stream) {
   if (!e || !d_labels) {

@@ -133,6 +133,9 @@ class Engine {
   // the assignment runs: core points keep their label, others take the smallest among their core neighbours
   void dbscan(float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, tknnDbscanInfo *info,
               hipStream_t s, const int32_t *core_label = nullptr);
+  // dbscan.hip: labels (and neighbour counts) for m points that are not in the tree (tknnDbscanQuery); m > 0
+  void dbscan_query(float eps, const float *d_queries, int64_t m, const int32_t *core_label, int32_t *d_labels, int32_t *d_counts,
+                    tknnDbscanInfo *info, hipStream_t s);
   // "eps auto-grown" (BASELINE config 5; spec: oracle/dbscan_oracle.c dbref_dbscan_auto)
   int64_t dbscan_noise(float eps, int min_pts, uint8_t *d_noise, hipStream_t s);  // tknnDbscanNoise
   void db_read_stats(hipStream_t s);

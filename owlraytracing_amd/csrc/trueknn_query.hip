@@ -7,21 +7,19 @@
 //
 // The self-solve's packet kernel lives on queries being tree slots (64 consecutive sorted slots share leaf
 // blocks).  External queries have no slot, so:
-//   1. query_code_kernel + a radix sort: the queries along the tree's own curve (curve_key.h) over the tree's own quantisation, so that
+//   1. query_code_kernel + a radix sort (query_order.h): the queries along the tree's own curve (curve_key.h) over the tree's own quantisation, so that
 //      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
 //   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
 //      walk of team_walk_kernel (trueknn_team.hip; both on team_walk.h) without anything that is per slot;
 //   3. query_lane_kernel: one query per lane, rope traversal (lane_walk.h), keys that carry the level -- for the few queries
 //      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
 //   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).
-#include "curve_key.h"
 #include "knn_thresholds.h"  // knn_gate_from_worst
 #include "lane_walk.h"
+#include "query_order.h"
 #include "team_lanes.h"
 #include "team_walk.h"
 #include "trueknn_engine.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cfloat>
@@ -36,7 +34,6 @@ namespace {
 constexpr int kQueryBlock = 64;       // one wave per workgroup, four teams
 constexpr int kQueryBlocksPerCu = 16;  // 7.3 KB of LDS each: far inside what a CU holds
 constexpr int kLaneBlock = 256;
-constexpr int kCodeBits = 30;         // ten bits per axis order 10 M queries well enough, and sort in half the passes
 
 // words of the call's own counters (in the workspace, zeroed per pass)
 enum { kWsCursor = 0, kWsRedo = 1, kWsTies = 2, kWsFailed = 3, kWsWords = 8 };
@@ -61,20 +58,7 @@ struct QueryKernelArgs {
   unsigned long long *stats;  // the engine's statistics stripes (kStatBase)
 };
 
-// ---- 1. the order ------------------------------------------------------------------------------------------
-// The tree's quantisation (cubic cells over the scene box, one scale for all axes: lbvh.hip) at ten bits per
-// axis, along the curve the tree was sorted by (the key is hierarchical: ten levels order the queries as the first ten
-// of the tree's 21 order its points); queries outside the box are clamped to its faces, queries with a NaN coordinate sort last.
-__global__ void __launch_bounds__(kLaneBlock) query_code_kernel(const float *__restrict__ queries, int32_t m, const float *__restrict__ scene,
-                                                               uint32_t *__restrict__ codes, uint32_t *__restrict__ order, int curve) {
-  const int32_t i = blockIdx.x * kLaneBlock + threadIdx.x;
-  if (i >= m) return;
-  const float c[3] = {queries[3 * (int64_t)i], queries[3 * (int64_t)i + 1], queries[3 * (int64_t)i + 2]};
-  const float ext = fmaxf(fmaxf(scene[3] - scene[0], scene[4] - scene[1]), scene[5] - scene[2]);
-  const uint32_t code = (uint32_t)curve_point_key(curve, c[0], c[1], c[2], scene[0], scene[1], scene[2], ext, kCodeBits / 3);
-  codes[i] = code;
-  order[i] = (uint32_t)i;
-}
+// ---- 1. the order: query_order.h (shared with tknnDbscanQuery) ----------------------------------------------------
 
 // ---- 2. the walk -------------------------------------------------------------------------------------------
 // A team walks the 64-ary pyramid for one query (walk_tree, team_walk.h): a child box inside the part of the
@@ -381,9 +365,7 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   const int k = qa.k;
   // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | levels | distances | sort space
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  uint32_t *null_u32 = nullptr;
-  size_t sort_bytes = 0;
-  OWLMI_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, null_u32, null_u32, null_u32, null_u32, (int)m, 0, kCodeBits + 1, s));
+  const size_t sort_bytes = query_order_sort_bytes(m, s);
   const bool own_levels = qa.d_levels == nullptr, own_dist = qa.exact && qa.d_dist == nullptr;
   const size_t words_b = align(kWsWords * sizeof(unsigned long long)), col_b = align((size_t)m * sizeof(uint32_t)),
                dist_b = own_dist ? align((size_t)m * k * sizeof(float)) : 0;
@@ -418,10 +400,7 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)m * sizeof(int32_t), s));
   reset_stat_stripes(s);
-  hipLaunchKernelGGL(query_code_kernel, dim3((unsigned)((m + kLaneBlock - 1) / kLaneBlock)), dim3(kLaneBlock), 0, s, qa.d_queries, (int32_t)m,
-                     bvh_.scene_device(), codes, order_in, bvh_.curve());
-  OWLMI_HIP(hipGetLastError());
-  OWLMI_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, codes, codes_alt, order_in, order, (int)m, 0, kCodeBits + 1, s));
+  query_order(qa.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   unsigned long long failed = 0, tied = 0, failed_exact = 0, tied_exact = 0;
   query_pass(a, cu_count_, h_counters_, ev_c_, ev_d_, failed, tied, s);

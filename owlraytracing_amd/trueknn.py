@@ -347,6 +347,54 @@ class TrueKNN:
                                                   ctypes.c_void_p(labels.data_ptr()), ctypes.byref(info), self._stream()))
         return labels
 
+    def dbscan_query(self, queries, eps, labels, core=None, want_counts=False):
+        """Cluster labels for points that are NOT in the built set (tknnDbscanQuery): labels[j] is the smallest label among
+        the core points of the set within ``eps`` of q_j, -1 if there is none; counts[j] the number of points of the set
+        within ``eps`` (nothing is "self": a point of the set that coincides with q_j counts).  ``queries``: numpy (m,2|3) or
+        a contiguous float32 CUDA tensor (m,3) on the engine's device.  ``labels`` (n,) int32 by row, with ``core`` (n,) bool
+        the labels and core flags of a clustering (``dbscan``'s); without ``core`` it is the core-label array itself (>= 0:
+        core with that label, < 0: not core, as ``dbscan_assign`` takes it).
+        Returns dict(labels (m,) int32, [counts (m,) int32], info)."""
+        torch = self._torch
+        if isinstance(queries, np.ndarray):
+            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
+                raise ValueError("dbscan_query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
+            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
+        if not isinstance(queries, torch.Tensor):
+            raise ValueError("dbscan_query: queries must be a numpy array or a torch tensor")
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("dbscan_query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
+        if queries.device != self.device:
+            raise ValueError("dbscan_query: queries are on %s, the engine on %s" % (queries.device, self.device))
+        if not queries.is_contiguous():
+            raise ValueError("dbscan_query: queries must be contiguous (packed fp32 triples)")
+        m = int(queries.shape[0])
+        with torch.cuda.device(self.device):
+            core_label = torch.as_tensor(labels, dtype=torch.int32, device=self.device)
+            if core_label.shape != (self.n,):
+                raise ValueError("dbscan_query: labels must have one entry per point of the built set")
+            if core is not None:
+                core = torch.as_tensor(core, device=self.device).to(torch.bool)
+                if core.shape != (self.n,):
+                    raise ValueError("dbscan_query: core must have one entry per point of the built set")
+                core_label = torch.where(core, core_label, torch.full_like(core_label, -1))
+            core_label = core_label.contiguous()
+            out = {"labels": torch.empty((m,), dtype=torch.int32, device=self.device)}
+            if want_counts:
+                out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
+            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device) if m == 0 else None
+            opt = _lib.DbscanQueryOptions()
+            opt.m, opt.eps = m, float(eps)
+            opt.d_queries = queries.data_ptr() if m > 0 else None
+            opt.d_core_label = core_label.data_ptr() if self.n > 0 else None
+            opt.d_labels = out["labels"].data_ptr() if m > 0 else spare.data_ptr()
+            opt.d_counts = None if not want_counts else (out["counts"].data_ptr() if m > 0 else spare.data_ptr())
+            info = _lib.DbscanInfo()
+            _lib.check(self._lib.tknnDbscanQuery(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -458,5 +506,19 @@ def trueknn_query(points, queries, k, start_radius, **kw):
         res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
         res["build_info"] = eng.build_info
         return res
+    finally:
+        eng.close()
+
+
+def dbscan_query(points, queries, eps, min_pts):
+    """One-shot helper: cluster ``points`` (TrueKNN.dbscan), then label ``queries`` against that clustering
+    (TrueKNN.dbscan_query).  dict(labels (m,), counts (m,), point_labels (n,), point_core (n,), clusters) as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points)
+        c = eng.dbscan(eps, min_pts)
+        r = eng.dbscan_query(queries, eps, c["labels"], core=c["core"], want_counts=True)
+        return {"labels": r["labels"].cpu().numpy(), "counts": r["counts"].cpu().numpy(), "point_labels": c["labels"].cpu().numpy(),
+                "point_core": c["core"].cpu().numpy(), "clusters": c["info"]["clusters"], "info": r["info"]}
     finally:
         eng.close()
