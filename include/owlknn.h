@@ -308,6 +308,49 @@ typedef struct {
 } tknnDbscanQueryOptions;
 TKNN_API int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream);
 
+/* ---- fixed-radius neighbour lists for points that are not in the set ------------------------------------------------
+ * tknnRadiusQuery returns, for m arbitrary points Q, the points of the built set P within `radius` of each, as CSR rows.
+ * Row j holds the points p of P with sqrt((dx*dx + dy*dy) + dz*dz) <= radius, every operation fp32 and uncontracted -- the
+ * predicate of the RT-DBSCAN calls, so a row's length is tknnDbscanQuery's d_counts[j] at eps = radius.  Distance exactly
+ * `radius` is inside.  Nothing is "self": a point of P that coincides with q_j is a neighbour at distance 0.  A query with a
+ * NaN coordinate has an empty row; NaN points of P are nobody's neighbour.  An entry names its point by id on trees built with
+ * tknnBuildIds, by row otherwise.  A halo tree, if set, is ignored as by the RT-DBSCAN calls; the tree and the state of
+ * tknnSolve are not modified; results are addressed by the caller's j whatever order the engine works in.
+ * Two passes, as tknnHaloSelect's:
+ *   count pass (d_idx = d_dist = NULL): d_offsets[0 .. m] receives the exclusive scan of the row lengths; d_offsets[m] and
+ *     info->total are the number of entries the fill pass needs room for.
+ *   fill pass  (d_idx given): row j is written at d_offsets[j] .. d_offsets[j + 1] of d_idx (and of d_dist, if given) and
+ *     never outside that segment.  The host reads d_offsets[m] once: if it exceeds `capacity`, TKNN_E_ARG before anything is
+ *     launched.  A row whose true length differs from its segment (stale offsets, another radius) is counted in
+ *     info->mismatched, and the call then returns TKNN_E_STATE (text: tknnLastError); what it has written lies inside the
+ *     segments.  sort = 1: every row ascending in (fp32 distance, index) -- fully determined; sort = 0: the order inside a
+ *     row is unspecified, the sort is skipped.
+ * info: total and max_row over the rows, node_tests / point_tests as the other calls count them (the count pass adds boxes
+ * wholly inside the sphere without reading their points), solve_ms the whole call, order_ms the ordering of the queries
+ * along the tree's curve, walk_ms the traversal kernels, sort_ms the fill pass's row sort.
+ * Errors, in this order: NULL engine / options / d_offsets / d_queries with m > 0: TKNN_E_ARG; not built: TKNN_E_STATE;
+ * radius not finite-positive, m < 0, m >= 2^31 - 1, d_dist without d_idx, or capacity < 0: TKNN_E_ARG; 2^31 or more
+ * neighbours in one call: TKNN_E_UNSUPPORTED (split the queries).  m = 0 succeeds with d_offsets[0] = 0 (count pass) and a
+ * zeroed info. */
+typedef struct {
+  const float *d_queries;  /* m packed fp32 triples (2-D data: z = 0), any points, in the set or not */
+  int64_t m;
+  float radius;            /* finite, > 0 */
+  int32_t sort;            /* 1: every row in (dist, index) order; 0: order inside a row unspecified */
+  int64_t *d_offsets;      /* m + 1, required. count pass: written; fill pass: read */
+  int32_t *d_idx;          /* NULL (with d_dist NULL) = count pass; else >= capacity entries */
+  float *d_dist;           /* may be NULL in a fill pass */
+  int64_t capacity;        /* entries d_idx / d_dist hold (fill pass) */
+} tknnRadiusOptions;
+typedef struct {
+  int64_t total;           /* neighbours over all rows = d_offsets[m] */
+  int64_t max_row;         /* longest row */
+  int64_t mismatched;      /* fill pass: rows whose length differs from their segment in d_offsets */
+  int64_t node_tests, point_tests;
+  float solve_ms, order_ms, walk_ms, sort_ms;
+} tknnRadiusInfo;
+TKNN_API int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *o, tknnRadiusInfo *info, void *stream);
+
 /* ---- RT-DBSCAN with an auto-grown eps (BASELINE.json configs[4]) ----------------------------------------------
  * No counterpart in the reference (it has no RT-DBSCAN source; BASELINE.md section 4: "spec TBD"), so the rule is this
  * build's own spec (oracle/dbscan_oracle.c, dbref_dbscan_auto), built on the reference's one growth rule, the radius

@@ -91,6 +91,28 @@ class DbscanQueryOptions(ctypes.Structure):
     ]
 
 
+class RadiusOptions(ctypes.Structure):
+    _fields_ = [
+        ("d_queries", ctypes.c_void_p),
+        ("m", ctypes.c_int64),
+        ("radius", ctypes.c_float),
+        ("sort", ctypes.c_int32),
+        ("d_offsets", ctypes.c_void_p),
+        ("d_idx", ctypes.c_void_p),
+        ("d_dist", ctypes.c_void_p),
+        ("capacity", ctypes.c_int64),
+    ]
+
+
+class RadiusInfo(ctypes.Structure):
+    _fields_ = [("total", ctypes.c_int64), ("max_row", ctypes.c_int64), ("mismatched", ctypes.c_int64),
+                ("node_tests", ctypes.c_int64), ("point_tests", ctypes.c_int64), ("solve_ms", ctypes.c_float),
+                ("order_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("sort_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class DbscanInfo(ctypes.Structure):
     _fields_ = [("clusters", ctypes.c_int32), ("solve_ms", ctypes.c_float), ("core_ms", ctypes.c_float),
                 ("union_ms", ctypes.c_float), ("label_ms", ctypes.c_float), ("union_launches", ctypes.c_int32),
@@ -155,6 +177,7 @@ SIGNATURES = {
     "tknnDbscanAssign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnDbscanQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DbscanQueryOptions), ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
+    "tknnRadiusQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RadiusOptions), ctypes.POINTER(RadiusInfo), ctypes.c_void_p]),
     "tknnDbscanAuto": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.POINTER(DbscanAutoInfo), ctypes.c_void_p]),
     "tknnHaloSelectFixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
@@ -200,8 +223,8 @@ def check(rc):
 # native sources a kernel's code does NOT depend on, by kernel-name prefix: a committed profile of the packet kernel stays
 # valid when only the clustering kernels change, and the other way round
 _NOT_IN = {
-    "team_": ("dbscan.hip", "halo_select.hip", "owl_runtime.cpp"),
-    "db_": ("trueknn_team.hip", "trueknn_wave.hip", "halo_select.hip", "owl_runtime.cpp"),
+    "team_": ("dbscan.hip", "halo_select.hip", "radius_query.hip", "owl_runtime.cpp"),
+    "db_": ("trueknn_team.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "owl_runtime.cpp"),
 }
 
 

@@ -902,6 +902,39 @@ int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbs
   });
 }
 
+int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusInfo *info, void *stream) {
+  if (!e || !options || !options->d_offsets || (options->m > 0 && !options->d_queries)) {
+    g_last_error = "tknnRadiusQuery: engine, options, d_offsets and (for m > 0) the queries are required";
+    return TKNN_E_ARG;
+  }
+  return guarded_on(e, [&] {
+    const tknnRadiusOptions &o = *options;
+    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRadiusQuery: call tknnBuild first"};
+    if (!(o.radius > 0.f) || !std::isfinite(o.radius)) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: radius must be finite and > 0"};
+    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: need 0 <= m < 2^31-1"};
+    if (o.d_dist && !o.d_idx) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: d_dist needs d_idx (both NULL: the count pass)"};
+    if (o.capacity < 0) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: capacity must not be negative"};
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (o.m == 0) {
+      if (!o.d_idx) {
+        OWLMI_HIP(hipMemsetAsync(o.d_offsets, 0, sizeof(int64_t), (hipStream_t)stream));
+        OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
+      }
+      return;
+    }
+    owlmi::RadiusArgs ra;
+    ra.d_queries = o.d_queries;
+    ra.m = o.m;
+    ra.radius = o.radius;
+    ra.sort = o.sort != 0;
+    ra.d_offsets = o.d_offsets;
+    ra.d_idx = o.d_idx;
+    ra.d_dist = o.d_dist;
+    ra.capacity = o.capacity;
+    e->impl.radius_query(ra, info, (hipStream_t)stream);
+  });
+}
+
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, void *stream) {
   if (!e || !d_labels) {

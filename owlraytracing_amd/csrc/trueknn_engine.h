@@ -47,6 +47,18 @@ struct QueryArgs {
   int32_t *d_levels = nullptr;
 };
 
+// tknnRadiusOptions as the engine takes it (d_idx == nullptr: the count pass)
+struct RadiusArgs {
+  const float *d_queries = nullptr;
+  int64_t m = 0;
+  float radius = 0;
+  bool sort = true;
+  int64_t *d_offsets = nullptr;
+  int32_t *d_idx = nullptr;
+  float *d_dist = nullptr;
+  int64_t capacity = 0;
+};
+
 template <int... C>
 struct CapacityTable {
   // smallest capacity >= k, or -1
@@ -143,6 +155,8 @@ class Engine {
                    tknnDbscanAutoInfo *info, hipStream_t s);
   // trueknn_query.hip: TrueKNN rows for m points that are not in the tree (tknnQuery); per-slot solve state is not touched
   void query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s);
+  // radius_query.hip: the points within a radius of m points that are not in the tree, as CSR rows (tknnRadiusQuery); m > 0
+  void radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_t s);
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }

@@ -395,6 +395,50 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def radius_query(self, queries, radius, sort=True, want_dist=True):
+        """The points of the built set within ``radius`` of each query, as CSR rows (tknnRadiusQuery): row j, the entries
+        offsets[j] .. offsets[j + 1] of ``idx`` and ``dist``, holds the points p with the fp32 distance
+        sqrt((dx*dx + dy*dy) + dz*dz) <= radius -- ``dbscan_query``'s predicate; nothing is "self".  ``queries``: numpy (m,2|3)
+        or a contiguous float32 CUDA tensor (m,3) on the engine's device.  ``sort``: every row ascending in (distance, index);
+        without it the order inside a row is unspecified.  The count pass sizes ``idx`` and ``dist``, the fill pass writes them.
+        Returns dict(offsets (m+1,) int64, idx (total,) int32, dist (total,) float32 [with ``want_dist``], info); ``info`` is
+        the fill pass's (the count pass's where there is nothing to fill), ``count_info`` the count pass's."""
+        torch = self._torch
+        if isinstance(queries, np.ndarray):
+            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
+                raise ValueError("radius_query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
+            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
+        if not isinstance(queries, torch.Tensor):
+            raise ValueError("radius_query: queries must be a numpy array or a torch tensor")
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("radius_query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
+        if queries.device != self.device:
+            raise ValueError("radius_query: queries are on %s, the engine on %s" % (queries.device, self.device))
+        if not queries.is_contiguous():
+            raise ValueError("radius_query: queries must be contiguous (packed fp32 triples)")
+        m = int(queries.shape[0])
+        with torch.cuda.device(self.device):
+            offsets = torch.empty((m + 1,), dtype=torch.int64, device=self.device)
+            opt = _lib.RadiusOptions()
+            opt.m, opt.radius, opt.sort = m, float(radius), int(bool(sort))
+            opt.d_queries = queries.data_ptr() if m > 0 else None
+            opt.d_offsets = offsets.data_ptr()
+            count_info = _lib.RadiusInfo()
+            _lib.check(self._lib.tknnRadiusQuery(self._h, ctypes.byref(opt), ctypes.byref(count_info), self._stream()))
+            total = int(count_info.total)
+            out = {"offsets": offsets, "idx": torch.empty((total,), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((total,), dtype=torch.float32, device=self.device)
+            info = count_info
+            if total > 0:  # (an empty tensor has no address, and a NULL d_idx would ask for the count pass again)
+                opt.d_idx, opt.capacity = out["idx"].data_ptr(), total
+                opt.d_dist = out["dist"].data_ptr() if want_dist else None
+                info = _lib.RadiusInfo()
+                _lib.check(self._lib.tknnRadiusQuery(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        out["count_info"] = count_info.as_dict()
+        return out
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -503,6 +547,20 @@ def trueknn_query(points, queries, k, start_radius, **kw):
     try:
         eng.build(points)
         r = eng.query(queries, k, start_radius, **kw)
+        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
+        res["build_info"] = eng.build_info
+        return res
+    finally:
+        eng.close()
+
+
+def radius_query(points, queries, radius, **kw):
+    """One-shot helper: build over ``points``, the neighbours of ``queries`` within ``radius`` (TrueKNN.radius_query), results
+    as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points)
+        r = eng.radius_query(queries, radius, **kw)
         res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
         res["build_info"] = eng.build_info
         return res
