@@ -351,6 +351,51 @@ typedef struct {
 } tknnRadiusInfo;
 TKNN_API int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *o, tknnRadiusInfo *info, void *stream);
 
+/* ---- at most k nearest within a radius, for points that are not in the set ------------------------------------------------
+ * tknnRadiusKnn returns, for m arbitrary points Q, the at most k nearest points of the built set P that are no farther than a
+ * radius, as dense rows of k: radius(.., max_num_neighbors = k), hybrid search, neighbour lists with a cap.  One pass, no host
+ * read of device data before the walk.  With r_j = d_radii[j] where d_radii is given, `radius` otherwise:
+ *   row j  is the first min(k, len_j) entries of the row tknnRadiusQuery gives q_j at radius r_j with sort = 1, after the skipped
+ *          point, if any, is removed.  Spelled out: the points p of P with sqrt((dx*dx + dy*dy) + dz*dz) <= r_j, every operation
+ *          fp32 and uncontracted (the predicate of the RT-DBSCAN calls; distance exactly r_j is inside), ascending in (fp32
+ *          distance, index) -- fully determined, ties at the k-th place included --, cut after k.  It is written at
+ *          d_idx[j * k ..] (and d_dist[j * k ..]); the unused tail of a row is idx = -1, dist = +inf.
+ *   d_counts[j] = min(k, len_j).
+ * Nothing is "self" unless d_skip_ids says so: the point named d_skip_ids[j] (by id on trees built with tknnBuildIds, by row
+ * otherwise) is left out of row j and of its count -- for Q = P, d_skip_ids[j] = j gives neighbour lists without the point
+ * itself, while another point that coincides with it stays, at distance 0.  A negative value skips nothing.  A query with a NaN
+ * coordinate has an empty row; NaN points of P are nobody's neighbour.  With d_radii, a row whose radius is NaN, not finite or
+ * <= 0 is empty; the host never reads the radii.  An entry names its point by id on trees built with tknnBuildIds, by row
+ * otherwise.  k may exceed the size of the set (rows are then never full).  A halo tree, if set, is ignored; the tree and the
+ * state of tknnSolve are not modified; results are addressed by the caller's j whatever order the engine works in.
+ * info: total = the sum of d_counts, full_rows the rows with k entries, node_tests / point_tests as the other calls count them,
+ * lane_rows the rows the one-query-per-lane kernel answered (team stack exhausted, or a tree too small for a box pyramid),
+ * solve_ms the whole call, order_ms the ordering of the queries along the tree's curve, walk_ms the traversal kernels.
+ * Errors, in this order: NULL engine / options / d_idx / d_queries with m > 0: TKNN_E_ARG; not built: TKNN_E_STATE; k < 1,
+ * m < 0, m >= 2^31 - 1, or, without d_radii, a radius that is not finite-positive: TKNN_E_ARG; k > TKNN_MAX_K_REGISTERS:
+ * TKNN_E_UNSUPPORTED.  m = 0 succeeds with a zeroed info. */
+typedef struct {
+  const float *d_queries;     /* m packed fp32 triples (2-D data: z = 0) */
+  int64_t m;
+  int32_t k;                  /* 1 .. TKNN_MAX_K_REGISTERS; k > n is allowed (rows are then never full) */
+  float radius;               /* finite, > 0; ignored for row j where d_radii is given */
+  const float *d_radii;       /* NULL, or m floats: row j uses d_radii[j] */
+  const int32_t *d_skip_ids;  /* NULL, or m int32: the point named d_skip_ids[j] (id on trees built with ids, row otherwise)
+                                 is left out of row j and of its count -- "self" for Q = P; a negative value skips nothing */
+  int32_t *d_idx;             /* m*k, required */
+  float *d_dist;              /* m*k, may be NULL */
+  int32_t *d_counts;          /* m, may be NULL */
+} tknnRadiusKnnOptions;
+typedef struct {
+  int64_t total;              /* entries over all rows = sum of d_counts */
+  int64_t full_rows;          /* rows with k entries */
+  int64_t node_tests, point_tests;
+  int64_t lane_rows;          /* rows the one-query-per-lane kernel answered */
+  float solve_ms, order_ms, walk_ms;
+  int32_t reserved_;
+} tknnRadiusKnnInfo;
+TKNN_API int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *o, tknnRadiusKnnInfo *info, void *stream);
+
 /* ---- RT-DBSCAN with an auto-grown eps (BASELINE.json configs[4]) ----------------------------------------------
  * No counterpart in the reference (it has no RT-DBSCAN source; BASELINE.md section 4: "spec TBD"), so the rule is this
  * build's own spec (oracle/dbscan_oracle.c, dbref_dbscan_auto), built on the reference's one growth rule, the radius

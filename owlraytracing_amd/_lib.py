@@ -113,6 +113,29 @@ class RadiusInfo(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class RadiusKnnOptions(ctypes.Structure):
+    _fields_ = [
+        ("d_queries", ctypes.c_void_p),
+        ("m", ctypes.c_int64),
+        ("k", ctypes.c_int32),
+        ("radius", ctypes.c_float),
+        ("d_radii", ctypes.c_void_p),
+        ("d_skip_ids", ctypes.c_void_p),
+        ("d_idx", ctypes.c_void_p),
+        ("d_dist", ctypes.c_void_p),
+        ("d_counts", ctypes.c_void_p),
+    ]
+
+
+class RadiusKnnInfo(ctypes.Structure):
+    _fields_ = [("total", ctypes.c_int64), ("full_rows", ctypes.c_int64), ("node_tests", ctypes.c_int64),
+                ("point_tests", ctypes.c_int64), ("lane_rows", ctypes.c_int64), ("solve_ms", ctypes.c_float),
+                ("order_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("reserved_", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
+
+
 class DbscanInfo(ctypes.Structure):
     _fields_ = [("clusters", ctypes.c_int32), ("solve_ms", ctypes.c_float), ("core_ms", ctypes.c_float),
                 ("union_ms", ctypes.c_float), ("label_ms", ctypes.c_float), ("union_launches", ctypes.c_int32),
@@ -178,6 +201,7 @@ SIGNATURES = {
                                         ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnDbscanQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DbscanQueryOptions), ctypes.POINTER(DbscanInfo), ctypes.c_void_p]),
     "tknnRadiusQuery": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RadiusOptions), ctypes.POINTER(RadiusInfo), ctypes.c_void_p]),
+    "tknnRadiusKnn": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(RadiusKnnOptions), ctypes.POINTER(RadiusKnnInfo), ctypes.c_void_p]),
     "tknnDbscanAuto": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.POINTER(DbscanAutoInfo), ctypes.c_void_p]),
     "tknnHaloSelectFixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
@@ -223,8 +247,8 @@ def check(rc):
 # native sources a kernel's code does NOT depend on, by kernel-name prefix: a committed profile of the packet kernel stays
 # valid when only the clustering kernels change, and the other way round
 _NOT_IN = {
-    "team_": ("dbscan.hip", "halo_select.hip", "radius_query.hip", "owl_runtime.cpp"),
-    "db_": ("trueknn_team.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "owl_runtime.cpp"),
+    "team_": ("dbscan.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp"),
+    "db_": ("trueknn_team.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp"),
 }
 
 

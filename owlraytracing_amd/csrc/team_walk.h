@@ -182,6 +182,8 @@ __device__ __forceinline__ float t_kth_dist(const uint32_t (&bd)[NREG], int k, i
   for (int j = 1; j < NREG; j++) reg = ((k - 1) >> 4) == j ? bd[j] : reg;
   return __uint_as_float(t_lane_read(reg, (team << 4) + ((k - 1) & 15)));
 }
+// registers per lane of a team's list of k <= 64 entries (host side: which instantiation of a walk kernel serves k)
+inline int query_nreg(int k) { return k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 48 ? 3 : 4)); }
 // min over the 16 lanes of my team, result in every lane of the team
 __device__ __forceinline__ uint32_t t_team_min_u32(uint32_t v) {
   v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128 /*row_ror:8*/, 0xf, 0xf, false));

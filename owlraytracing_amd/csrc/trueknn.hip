@@ -935,6 +935,36 @@ int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusIn
   });
 }
 
+int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusKnnInfo *info, void *stream) {
+  if (!e || !options || !options->d_idx || (options->m > 0 && !options->d_queries)) {
+    g_last_error = "tknnRadiusKnn: engine, options, d_idx and (for m > 0) the queries are required";
+    return TKNN_E_ARG;
+  }
+  return guarded_on(e, [&] {
+    const tknnRadiusKnnOptions &o = *options;
+    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRadiusKnn: call tknnBuild first"};
+    if (o.k < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: k must be positive"};
+    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: need 0 <= m < 2^31-1"};
+    if (!o.d_radii && (!(o.radius > 0.f) || !std::isfinite(o.radius)))
+      throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: radius must be finite and > 0 (or give d_radii)"};
+    if (o.k > TKNN_MAX_K_REGISTERS)
+      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnRadiusKnn: k out of range (1 .. 64: the kernels keep their lists in registers)"};
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (o.m == 0) return;
+    owlmi::RadiusKnnArgs ra;
+    ra.d_queries = o.d_queries;
+    ra.m = o.m;
+    ra.k = o.k;
+    ra.radius = o.radius;
+    ra.d_radii = o.d_radii;
+    ra.d_skip_ids = o.d_skip_ids;
+    ra.d_idx = o.d_idx;
+    ra.d_dist = o.d_dist;
+    ra.d_counts = o.d_counts;
+    e->impl.radius_knn(ra, info, (hipStream_t)stream);
+  });
+}
+
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, void *stream) {
   if (!e || !d_labels) {

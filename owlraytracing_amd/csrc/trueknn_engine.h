@@ -59,6 +59,19 @@ struct RadiusArgs {
   int64_t capacity = 0;
 };
 
+// tknnRadiusKnnOptions as the engine takes it
+struct RadiusKnnArgs {
+  const float *d_queries = nullptr;
+  int64_t m = 0;
+  int k = 0;
+  float radius = 0;
+  const float *d_radii = nullptr;
+  const int32_t *d_skip_ids = nullptr;
+  int32_t *d_idx = nullptr;
+  float *d_dist = nullptr;
+  int32_t *d_counts = nullptr;
+};
+
 template <int... C>
 struct CapacityTable {
   // smallest capacity >= k, or -1
@@ -157,6 +170,8 @@ class Engine {
   void query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s);
   // radius_query.hip: the points within a radius of m points that are not in the tree, as CSR rows (tknnRadiusQuery); m > 0
   void radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_t s);
+  // radius_knn.hip: at most k nearest points within a radius of m points that are not in the tree, as dense rows (tknnRadiusKnn); m > 0
+  void radius_knn(const RadiusKnnArgs &ra, tknnRadiusKnnInfo *info, hipStream_t s);
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }

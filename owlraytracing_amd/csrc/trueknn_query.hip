@@ -331,7 +331,6 @@ __global__ void __launch_bounds__(kLaneBlock) query_lane_kernel(QueryKernelArgs 
 
 using WalkEntry = void (*)(QueryKernelArgs);
 const WalkEntry kWalks[4] = {query_walk_kernel<1>, query_walk_kernel<2>, query_walk_kernel<3>, query_walk_kernel<4>};
-inline int query_nreg(int k) { return k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 48 ? 3 : 4)); }
 
 }  // namespace
 

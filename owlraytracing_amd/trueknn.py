@@ -439,6 +439,63 @@ class TrueKNN:
         out["count_info"] = count_info.as_dict()
         return out
 
+    def radius_knn(self, queries, k, radius=None, radii=None, skip_ids=None, want_dist=True):
+        """At most ``k`` nearest points of the built set within a radius of each query, as dense rows (tknnRadiusKnn): row j is
+        the first min(k, len) entries of ``radius_query``'s sorted row at its radius -- the points p with the fp32 distance
+        sqrt((dx*dx + dy*dy) + dz*dz) <= r_j, ascending in (distance, index) --, padded with idx -1 / dist +inf.  Exactly one of
+        ``radius`` (one for all rows) and ``radii`` (length m, row j uses radii[j]; a row whose radius is NaN, not finite or <= 0
+        is empty) is given.  ``skip_ids`` (length m, int32): the point named skip_ids[j] (its id on trees built with ids, its
+        row otherwise) is left out of row j; a negative value skips nothing.  ``radii`` and ``skip_ids`` may be numpy arrays or
+        tensors on the engine's device.  ``queries``: numpy (m,2|3) or a contiguous float32 CUDA tensor (m,3) on the engine's
+        device.  Returns dict(idx (m,k) int32, dist (m,k) float32 [with ``want_dist``], counts (m,) int32, info)."""
+        torch = self._torch
+        if isinstance(queries, np.ndarray):
+            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
+                raise ValueError("radius_knn: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
+            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
+        if not isinstance(queries, torch.Tensor):
+            raise ValueError("radius_knn: queries must be a numpy array or a torch tensor")
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("radius_knn: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
+        if queries.device != self.device:
+            raise ValueError("radius_knn: queries are on %s, the engine on %s" % (queries.device, self.device))
+        if not queries.is_contiguous():
+            raise ValueError("radius_knn: queries must be contiguous (packed fp32 triples)")
+        if (radius is None) == (radii is None):
+            raise ValueError("radius_knn: give exactly one of radius and radii")
+        m, k = int(queries.shape[0]), int(k)
+
+        def column(values, dtype, name):
+            if isinstance(values, torch.Tensor) and values.device != self.device:
+                raise ValueError("radius_knn: %s is on %s, the engine on %s" % (name, values.device, self.device))
+            values = torch.as_tensor(values, device=self.device).to(dtype).contiguous()
+            if values.shape != (m,):
+                raise ValueError("radius_knn: %s must have one entry per query" % name)
+            return values
+
+        with torch.cuda.device(self.device):
+            radii = None if radii is None else column(radii, torch.float32, "radii")
+            skip_ids = None if skip_ids is None else column(skip_ids, torch.int32, "skip_ids")
+            rows = max(k, 0)
+            out = {"idx": torch.empty((m, rows), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((m, rows), dtype=torch.float32, device=self.device)
+            out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
+            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _lib.RadiusKnnOptions()
+            opt.m, opt.k, opt.radius = m, k, 0.0 if radius is None else float(radius)
+            opt.d_queries = queries.data_ptr() if m > 0 else None
+            opt.d_radii = None if radii is None else (radii.data_ptr() if m > 0 else spare.data_ptr())
+            opt.d_skip_ids = None if skip_ids is None or m == 0 else skip_ids.data_ptr()
+            opt.d_idx = out["idx"].data_ptr() if m * rows > 0 else spare.data_ptr()
+            opt.d_dist = out["dist"].data_ptr() if want_dist and m * rows > 0 else None
+            opt.d_counts = out["counts"].data_ptr() if m > 0 else None
+            info = _lib.RadiusKnnInfo()
+            _lib.check(self._lib.tknnRadiusKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -566,6 +623,29 @@ def radius_query(points, queries, radius, **kw):
         return res
     finally:
         eng.close()
+
+
+def radius_knn(points, queries, k, **kw):
+    """One-shot helper: build over ``points``, at most ``k`` nearest points within a radius of ``queries`` (TrueKNN.radius_knn),
+    results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points)
+        r = eng.radius_knn(queries, k, **kw)
+        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
+        res["build_info"] = eng.build_info
+        return res
+    finally:
+        eng.close()
+
+
+def radius_graph(points, k, radius, loop=False):
+    """One-shot helper: for every point of ``points`` its at most ``k`` nearest other points within ``radius`` -- radius_knn with
+    the points as their own queries and every point skipped in its own row; with ``loop`` the point itself is an entry (at
+    distance 0, where k leaves room).  Results as numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
+    points = pad_to_3d(np.asarray(points, np.float32))
+    skip = None if loop else np.arange(len(points), dtype=np.int32)
+    return radius_knn(points, points, k, radius=radius, skip_ids=skip)
 
 
 def dbscan_query(points, queries, eps, min_pts):
