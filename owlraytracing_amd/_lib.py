@@ -244,11 +244,17 @@ def check(rc):
         raise TknnError(rc, (load().tknnLastError() or b"").decode())
 
 
-# native sources a kernel's code does NOT depend on, by kernel-name prefix: a committed profile of the packet kernel stays
-# valid when only the clustering kernels change, and the other way round
+# native sources a kernel's code does NOT depend on, by kernel-name prefix (the FIRST matching prefix counts: team_walk_ stands
+# before team_): a committed profile of the packet kernel stays valid when only the tie pass, the k > 64 walk or the
+# clustering kernels change, and the other way round
+_NOT_TEAM = ("dbscan.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp")
 _NOT_IN = {
-    "team_": ("dbscan.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp"),
-    "db_": ("trueknn_team.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp"),
+    "team_walk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),  # trueknn_tail.hip
+    "tie_fix_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),
+    "bigk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_tail.hip"),  # trueknn_bigk.hip
+    "team_": _NOT_TEAM + ("trueknn_tail.hip", "trueknn_bigk.hip"),  # trueknn_team.hip: team_kernel, team_prep_kernel
+    "db_": ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip",
+            "owl_runtime.cpp"),
 }
 
 

@@ -42,7 +42,7 @@ __device__ __forceinline__ int32_t knn_key_prim(uint64_t key) {
 }
 
 // Rows whose order depends on how bit-identical distances are ordered (KList::has_ties below) are
-// flagged by whichever kernel finishes them and redone by tie_fix_kernel (trueknn_team.hip):
+// flagged by whichever kernel finishes them and redone by tie_fix_kernel (trueknn_tail.hip):
 // tie[slot] = 1 + the level the query finished at (bit 7: see `edge` below), counters[kTieCounter] counts them, and the first
 // kTieListCap slots are also listed so that the usual handful needs no compaction pass.
 // counters[kTieCounter + 1]: tie_fix_kernel's work cursor, [kTieCounter + 2]: rows it had to leave, [kTieCounter + 3]: rows that
@@ -130,7 +130,7 @@ struct KList {
   // True if two of entries 0..k have the same distance (entry k: the best candidate left out of the
   // row).  The reference orders such keys by the round in which each was first a candidate
   // (deviceCode.cu:77-85 keeps what is listed), the lists here by index: flagged rows are redone by
-  // tie_fix_kernel (trueknn_team.hip).  False positives are harmless.  Candidates the callers drop
+  // tie_fix_kernel (trueknn_tail.hip).  False positives are harmless.  Candidates the callers drop
   // at their gates are strictly farther than the k-th entry (knn_gate_from_worst) and never tie.
   __device__ __forceinline__ bool has_ties(int k) const {
     bool t = false;

@@ -1,5 +1,5 @@
 // team_lanes.h -- what a 16-lane team of the TrueKNN kernels is made of: the lane exchanges, the sorting networks and the
-// merge of buffered candidates into a team's sorted register list.  Shared by the team kernels (trueknn_team.hip) and the
+// merge of buffered candidates into a team's sorted register list.  Shared by the team kernels (trueknn_team.hip, trueknn_tail.hip, trueknn_bigk.hip) and the
 // kernel for query points that are not in the tree (trueknn_query.hip); every function is inlined into its caller.  What a
 // team does with these lanes when it walks the box pyramid for one query is team_walk.h, on top of this file.
 #pragma once

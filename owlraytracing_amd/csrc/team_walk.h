@@ -1,6 +1,6 @@
 // team_walk.h -- one 16-lane team's walk of the 64-ary box pyramid for ONE query, and the pieces around it, shared by the
-// kernels that walk it: team_walk_kernel, tie_fix_kernel and bigk_walk_kernel (trueknn_team.hip) and query_walk_kernel
-// (trueknn_query.hip).  Four teams of a wave walk in lock step, so there is no __syncthreads, only t_wave_sync.  What a kernel
+// kernels that walk it: team_walk_kernel and tie_fix_kernel (trueknn_tail.hip), bigk_walk_kernel (trueknn_bigk.hip) and
+// query_walk_kernel (trueknn_query.hip).  Four teams of a wave walk in lock step, so there is no __syncthreads, only t_wave_sync.  What a kernel
 // does differently comes in as callables (the box rule, the block visitor, the end-of-chunk hook) or as template parameters;
 // every function is inlined into its caller.  The box test, its margins and the counting rule below are what make rows equal
 // the reference's bit for bit: they are written here once.

@@ -12,6 +12,8 @@
 
 namespace owlmi {
 
+struct TeamArgs;  // team_args.h: the team kernels' argument block
+
 struct RoundsExceeded {};
 struct ArgError {
   int code;
@@ -190,29 +192,27 @@ class Engine {
   // trueknn_team.hip; returns false if a packet needed more leaf blocks than the kernel can name
   bool solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
   static bool team_kernel_supports(int k);
-  // trueknn_team.hip: 64 < k <= TKNN_MAX_K, the lists in memory (bigk_walk_kernel)
+  // trueknn_bigk.hip: 64 < k <= TKNN_MAX_K, the lists in memory (bigk_walk_kernel)
   static bool bigk_supports(int k);
   void solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
-  // trueknn_team.hip: redo the rows flagged in tie_ with the reference's order of exact-distance ties
+  // trueknn_tail.hip: redo the rows flagged in tie_ with the reference's order of exact-distance ties
   void fix_ties(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
+  // trueknn_tail.hip: the team kernels' end-of-wave statistics, striped (kStatBase)
   void reset_stat_stripes(hipStream_t s);
   void fetch_stat_stripes(hipStream_t s);
   KernelStats fold_stat_stripes(bool with_min) const;
-  // trueknn_team.hip: a solve from level 0 without the packet kernel's prep launch (levels: preset to -1 if not null)
+  // trueknn_tail.hip: a solve from level 0 without the packet kernel's prep launch (levels: preset to -1 if not null)
   void reset_solve_state(int32_t *levels, hipStream_t s);
-  // trueknn_team.hip: a zeroed TeamArgs (the team kernels' argument block) with the fields every team launch reads ...
-  template <class A>
-  A team_args(const SolveArgs &sa) const;
+  // trueknn_tail.hip: a zeroed TeamArgs (the team kernels' argument block) with the fields every team launch reads ...
+  TeamArgs team_args(const SolveArgs &sa) const;
   // ... and the fields only the solves read (team_kernel, team_walk_kernel, bigk_walk_kernel; not tie_fix_kernel)
-  template <class A>
-  void set_solve_args(A &a, const SolveArgs &sa) const;
-  // trueknn_team.hip: team_walk_kernel over nslots sorted slots (slots null: every slot), lane rounds for what outgrew its stack
-  template <class A>
-  tknnSolveInfo walk(const SolveArgs &sa, A a, int nreg, const int32_t *slots, int32_t nslots, int lane_level,
+  void set_solve_args(TeamArgs &a, const SolveArgs &sa) const;
+  // trueknn_tail.hip: team_walk_kernel over nslots sorted slots (slots null: every slot), lane rounds for what outgrew its stack
+  tknnSolveInfo walk(const SolveArgs &sa, TeamArgs a, int nreg, const int32_t *slots, int32_t nslots, int lane_level,
                      bool count_lane_launches, hipStream_t s);
-  // trueknn_team.hip: the sorted slots whose byte passes `flag`, ascending, into slot_list_; returns their count's device address
-  template <class Flag>
-  int32_t *compact_flagged_slots(const uint8_t *bytes, Flag flag, hipStream_t s);
+  // trueknn_tail.hip: the sorted slots that were handed over (done_[slot] == 0) or, with `ties`, flagged in tie_, ascending,
+  // into slot_list_; returns their count's device address
+  int32_t *compact_slots(bool ties, hipStream_t s);
   void launch_tie_fix(const SolveArgs &sa, const int32_t *slots, int32_t nslots, int blocks, hipStream_t s,
                       const int32_t *d_slot_count = nullptr, int64_t expected_rows = 0);
   int first_step_estimate(const SolveArgs &sa) const;

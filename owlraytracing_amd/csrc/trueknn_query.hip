@@ -10,7 +10,7 @@
 //   1. query_code_kernel + a radix sort (query_order.h): the queries along the tree's own curve (curve_key.h) over the tree's own quantisation, so that
 //      the four teams of a wave and the waves of a workgroup's neighbours walk neighbouring nodes;
 //   2. query_walk_kernel: persistent, one 16-lane team per query, every radius level inside the kernel -- the
-//      walk of team_walk_kernel (trueknn_team.hip; both on team_walk.h) without anything that is per slot;
+//      walk of team_walk_kernel (trueknn_tail.hip; both on team_walk.h) without anything that is per slot;
 //   3. query_lane_kernel: one query per lane, rope traversal (lane_walk.h), keys that carry the level -- for the few queries
 //      the walk leaves: stack exhausted, or a row whose order depends on how bit-identical distances are ordered;
 //   4. exact = 1: both kernels once more with a fixed radius per row (the box of half-width d_k), (dist, index).

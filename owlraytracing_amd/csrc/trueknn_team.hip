@@ -26,11 +26,10 @@
 // cheap bound cannot decide it (see the record layout below), same distance arithmetic, keys ordered
 // by (dist, index).
 #include "knn_thresholds.h"  // knn_gate_from_worst
+#include "team_args.h"
 #include "team_lanes.h"
 #include "team_walk.h"
 #include "trueknn_engine.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -38,17 +37,10 @@
 #include <cstdlib>
 #include <cstring>
 
-// Diagnostic build only (make DIAG=1 -> libowl_mi355x_diag.so, never the shipped library): lets
-// scripts/diag_team.py price the phases by switching them off; results are wrong when any bit is set.
-#ifndef TKNN_DIAG_BUILD
-#define TKNN_DIAG_BUILD 0
-#endif
-
 namespace owlmi {
 
 namespace {
 
-constexpr int kTeamBlock = 64;      // one wave per workgroup: LDS, not the block shape, limits residency
 // leaf blocks one packet may need per level.  A per-query list names them by byte slots: 256 -- except with four list
 // registers per lane (k > 48), where the lists of the last level outgrow that (10 M uniform points at k = 64: 36 % of the queries
 // were handed to the team walk, two thirds of the solve): 512, the ninth bit of a slot in a word of its own
@@ -91,44 +83,12 @@ inline int lds_workgroups_per_cu(size_t lds) {
   const size_t granule = 1280, total = 160 * 1024;  // gfx950
   return lds ? (int)((total / granule) / ((lds + granule - 1) / granule)) : 1 << 20;
 }
-// slots (in fours) a wave takes per turn at the tie pass's work cursor (TeamArgs::grab): so many that a wave comes `turns` times in
-// all, at most `cap`; TKNN_GRAB overrides (measurements)
-inline int grab_for(int64_t count, int blocks, int turns, int cap) {
-  if (const char *g = getenv("TKNN_GRAB")) return std::max(1, atoi(g));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(cap, count / ((int64_t)std::max(1, blocks) * 4 * turns)));
-}
-// list registers per lane for k: 16 entries each.  Three (k = 33 .. 48; round 4) spare those k the four-register
-// instantiation's fourth merge step and its 13 granules of LDS (10 M uniform points: 22.2 -> 15.0 ms at k = 33, 14.2 -> 12.7 at k = 32)
-#ifndef TKNN_NREG3
-#define TKNN_NREG3 1
-#endif
-inline int nreg_for(int k) { return k <= 16 ? 1 : (k <= 32 ? 2 : (k <= 48 && TKNN_NREG3 ? 3 : 4)); }
 #ifndef TKNN_SORT_FIRST
 #define TKNN_SORT_FIRST 1  // k <= 16: 1 = sort the query's own block on the spot instead of buffering its candidates
 #endif
 #ifndef TKNN_TEAM_WAVES
 #define TKNN_TEAM_WAVES 4  // waves per SIMD the packet kernel's register allocation aims at
 #endif
-#ifndef TKNN_WALK_WAVES
-// waves per SIMD the walks' register allocation aims at (0: the compiler's choice, 3 with 131 .. 147 registers).  Round 4: 4 --
-// a few words of scratch outside the loops; 10 M points: the hand-over walk 12 .. 18 % faster (taxi-like set at k = 10: 4.4 -> 3.9 ms,
-// uniform at k = 48: 5.3 -> 4.4 ms), the k > 64 walk 17 % (k = 65: 209 -> 174 ms); 5 and 6 spill inside the loops and lose
-#define TKNN_WALK_WAVES 4
-#endif
-#if TKNN_WALK_WAVES
-#define TKNN_WALK_ATTR __attribute__((amdgpu_waves_per_eu(TKNN_WALK_WAVES)))
-#else
-#define TKNN_WALK_ATTR
-#endif
-#ifndef TKNN_BIGK_WAVES
-#define TKNN_BIGK_WAVES 4
-#endif
-#if TKNN_BIGK_WAVES
-#define TKNN_BIGK_ATTR __attribute__((amdgpu_waves_per_eu(TKNN_BIGK_WAVES)))
-#else
-#define TKNN_BIGK_ATTR
-#endif
-constexpr int kWalkBlocksPerCu = 4 * (TKNN_WALK_WAVES > 4 ? TKNN_WALK_WAVES : 4);  // one-wave workgroups of the walks' launches
 // the per-XCD packet counters: 256 bytes apart, behind the kCounters words (the words RT-DBSCAN stripes its statistics over: not in
 // use during a solve).  Side by side in one cache line (round 3: counters[16 + x]) their atomics -- one per packet, 156 000 per launch
 // of the benchmark -- queued at one place (see TeamArgs::grab for what a turn at one address costs)
@@ -188,54 +148,6 @@ struct TeamLayout {
 // NaN) proves it false -- the rounding of fl(c-r), fl(c+r) and fl(c-q) is below 2^-23 (|q| + 2r),
 // an eighth of M -- and only candidates inside that 2M band (about 1e-4 of them) run the literal
 // test.  Three instructions instead of stored per-axis thresholds, and 2.5 KB less LDS per wave.
-struct TeamArgs {
-  LbvhView bvh, halo;
-  LbvhWideView wide[2];
-  float start_radius;
-  // per-query radius schedule (tknnSolveOptions.d_start_radii): per ROW the radius query `row` starts
-  // with, or null -- then every query starts with start_radius, as in the reference (hostCode.cpp:185,325)
-  const float *start_radii;
-  int k;
-  int max_rounds;
-  int allow_unfinished;
-  int first_step;  // levels the first gather of every packet serves (density estimate, 1..kMaxStep)
-  int first_ext;   // ... and whether that gather also lists the blocks of the level after them (see the level loop)
-  float tie_span;  // sqrt(number of axes along which the points differ), rounded up: d <= tie_span * Chebyshev distance
-  int diag;        // TKNN_DIAG_BUILD only: 1 skip inserts, 2 skip SELECT passes, 4 skip COUNT passes, 8 skip per-block query tests,
-                   // 16 / 32 step and gather statistics (atomics: slow), 64 every block visit of a query reads its first listed block
-  int32_t ngroups;
-  int32_t *out_idx;
-  float *out_dist;
-  int64_t *out_isect;
-  tknnNeigh *out_fb;
-  int32_t *out_level;
-  // continuation state for queries whose candidate lists outgrow the LDS lists (finished by the
-  // lane kernel): per sorted slot, preset by the host to done=1
-  uint8_t *done;
-  int64_t *isect_sorted;
-  int32_t *next_level;
-  // per sorted slot: 1 + level (| 0x80: knn_flag_tie's `edge`) for rows that finished with bit-identical distances among entries
-  // 0..k of the list (entry k: the best candidate left out); tie_fix_kernel redoes them in the reference's tie order
-  uint8_t *tie;
-  int32_t *tie_list;
-  const uint8_t *skip;  // per sorted slot, or null: queries with skip[slot] == skip_is sit this solve out (tknnSolveOptions.phase)
-  int32_t skip_is;
-  const int32_t *slot_count;  // tie_fix_kernel, nslots == -2: length of `slots` as hipCUB's select wrote it (device side)
-  // a wave takes 4 * grab consecutive slots per turn at the work cursor (>= 1).  One address, device scope: a turn costs some
-  // 12 ns whoever asks -- at four rows a turn that was ALL of the tie pass on duplicate-heavy sets (10 M taxi-like points, k = 10 / 24:
-  // 0.78 / 2.3 M rows in 2.5 / 7.2 ms; with longer turns 1.1 / 2.8 ms).  The walks keep 1: their queries differ too much in cost
-  // (turns of up to 64 slots: the hand-over walk 4.0 -> 4.5 ms on that set, the k = 65 walk 173 -> 189 ms on 10 M uniform points).
-  int grab;
-  // tie_fix_kernel: the sorted slot of row i (Lbvh::row_slot_device), or null: no look at the written row first.  The look
-  // turns a written neighbour into its point through this table, which is indexed by input ROW: right only where a point's
-  // id is its row.  An engine built with ids (tknnBuildIds) names neighbours by the caller's id, so it gets null and every
-  // flagged row is walked (an id below n would otherwise fetch some other point and let a wrongly ordered row stand).
-  const int32_t *row_slot;
-  // [0] (unused here) [kXcdCounter + 32 x] per-XCD packet counters [1] max levels [2] node tests [3] point tests [4] sum isect
-  // [5] error flags (1 max_rounds) [6] sum levels [7] unfinished [8] handed over [9] min hand-over level
-  unsigned long long *counters;
-};
-
 struct TeamLds {
   float *qrec;        // [64][kQrecStride]
   int32_t *blk;       // [kMaxBlocks] block entries of the packet (bit 31: halo tree)
@@ -1146,154 +1058,6 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
 }
 
 
-// ---- team walk: the stragglers, one query per team, no packet lists --------------------------------
-// Queries the packet kernel hands over (outliers whose boxes have grown over whole clusters, dense
-// duplicates) have candidate sets far beyond its LDS lists.  Here a team walks the pyramid for ONE
-// query: its 16 lanes test 16 child boxes of a wide node at a time and push the survivors on the
-// team's LDS stack; a leaf block is 16 points = 16 lanes, tested, counted and selected exactly like
-// in the passes above.  A child box that lies inside the part of the query's box where the
-// candidate test is certain, and beyond the list's gate, is COUNTED (its points are consecutive
-// sorted slots: the count is arithmetic) instead of walked -- a box over a cluster of 100 000 points
-// costs a few hundred steps.  Levels loop inside the kernel (hostCode.cpp:285-340 per query).
-// The walk itself, its box and block tests and the counting rule are team_walk.h's.
-
-struct NotDone {
-  __host__ __device__ bool operator()(uint8_t d) const { return d == 0; }
-};
-
-template <bool HALO, int NREG>
-__global__ void __launch_bounds__(kTeamBlock) TKNN_WALK_ATTR team_walk_kernel(TeamArgs a, const int32_t *slots, int32_t nslots) {
-  __shared__ int32_t stack_mem[4 * kWalkStack];
-  __shared__ WalkLevel levels[2][LBVH_WIDE_LEVELS];
-  __shared__ unsigned long long cand_mem[4 * kCandCapacity];  // per team: candidates waiting to be merged into its list (t_merge_rows)
-  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kWalkStack;
-  walk_fill_levels<2>(levels[0], a.wide, lane);
-  t_wave_sync();
-  unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
-  unsigned int unfinished = 0, failed = 0;
-  int max_level = 0;
-  int turn_next = 0, turn_left = 0;  // (t_next_slots)
-  for (;;) {
-    const int base = t_next_slots(&a.counters[0], a.grab, lane, turn_next, turn_left);
-    if (base >= nslots) break;
-    const bool has_q = base + team < nslots;
-    const int32_t slot = has_q ? (slots ? slots[base + team] : base + team) : 0;
-    const LbvhPoint q = a.bvh.points[slot];
-    const int32_t row = a.bvh.prim_id[slot];
-    int level = has_q ? a.next_level[slot] : 0;
-    int64_t isect = has_q ? a.isect_sorted[slot] : 0;
-    const float q_r0 = a.start_radii ? a.start_radii[row] : a.start_radius;  // per-query schedule, if asked for
-    float r = q_r0;
-    for (int i = 0; i < level; i++) r = r * 2.0f;
-    bool active = has_q;
-    while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
-      const WalkBox qb(q, r);
-      uint32_t part = 0;  // my lane's share of the candidate count of this level
-      uint32_t bd[NREG], bi[NREG];  // register j of lane t holds list entry 16 j + t (indices are compile-time: stays in VGPRs)
-#pragma unroll
-      for (int j = 0; j < NREG; j++) {
-        bd[j] = 0x7f7fffffu;  // KNN_EMPTY_KEY = {FLT_MAX, 0}
-        bi[j] = 0u;
-      }
-      float tau2 = INFINITY;
-      bool overflow = false;
-      const bool full = a.k == 16 * NREG;  // see team_pass
-      uint32_t left_out = 0xffffffffu;
-      // candidates wait in the team's buffer and are merged sixteen at a time, as in the passes (one insert per lock-step
-      // round was most of this kernel's time at k = 64: some 200 inserts per query)
-      unsigned long long *my_cand = cand_mem + team * kCandCapacity;
-      uint32_t fill_n = 0;
-      auto merge_buffer = [&]() __attribute__((always_inline)) {
-        t_wave_sync();
-        t_merge_rows<NREG>(bd, bi, left_out, full, my_cand, fill_n, tl);
-        t_wave_sync();
-        fill_n = 0;
-        tau2 = knn_gate_from_worst(t_kth_dist<NREG>(bd, a.k, team));
-      };
-      for (int tree = 0; tree < (HALO ? 2 : 1); tree++) {
-        const LbvhWideView &wv = a.wide[tree];
-        const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
-        if (tv.n <= 0 || wv.levels <= 0) continue;
-        const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-        walk_tree<false>(
-            levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
-            [&](const LbvhBox &bx, int32_t c, int lvl) { return !walk_count_box(bx, q, qb, tau2, c, lvl, clean_end, part); },
-            [&](int32_t b, bool has_b) {
-              LbvhPoint p;
-              float d2;
-              const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
-              point_tests += has_b ? 1u : 0u;
-              part = t_count(part, in_m);
-              unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
-              if (TKNN_DIAG_BUILD && (a.diag & 1)) pm = 0;
-              if (pm) {
-                const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
-                if ((mine16 >> tl) & 1u) my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)p.id;
-                fill_n += __popc(mine16);
-                if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
-              }
-            },
-            [&]() {  // a tighter gate for what comes next as soon as a handful of candidates wait
-              if (__ballot(fill_n >= (uint32_t)TKNN_MERGE_AT) != 0ull) merge_buffer();
-            }, overflow);
-      }
-      if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
-      if (full) left_out = t_team_min_u32(left_out);  // the smallest key left out by any merge, where the tie test below looks for it: lane 15
-      // ---- the level's outcome, per team ----
-      const uint32_t cnt = t_team_sum(part);
-      const uint32_t others = cnt ? cnt - 1u : 0u;  // a query lies in its own box
-      const bool fin = active && !overflow && others >= (uint32_t)a.k;
-      if (active && overflow) {  // stack exhausted: leave the query to the lane rounds, state untouched
-        failed += tl == 0 ? 1u : 0u;
-        active = false;
-      } else if (active) {
-        isect += cnt;
-        levels_sum += tl == 0 ? 1ull : 0ull;
-        if (fin) {
-#pragma unroll
-          for (int reg = 0; reg < NREG; reg++) {
-            const int j = tl + 16 * reg;
-            if (j >= a.k) continue;
-            t_write_entry(a.out_idx, a.out_dist, a.out_fb, (int64_t)row * a.k + j, knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]),
-                          __uint_as_float(bd[reg]), j, a.k, isect);
-          }
-          bool tie, edge;
-          t_row_ties<NREG>(bd, left_out, full, a.k, tl, q, q_r0, r, a.tie_span, true, tie, edge);
-          const bool tied = t_team_any(tie, team), tied_edge = t_team_any(edge, team);
-          if (tl == 0) {
-            if (a.out_isect) a.out_isect[row] = isect;
-            if (a.out_level) a.out_level[row] = level;
-            if (tied) knn_flag_tie(a.tie, a.tie_list, a.counters, slot, level, tied_edge ? 1 : 0);
-            a.done[slot] = 1;
-            isect_sum += (unsigned long long)isect;
-          }
-          max_level = max(max_level, level + 1);
-          active = false;
-        } else {
-          level++;
-          r = r * 2.0f;  // hostCode.cpp:321
-          if (level >= a.max_rounds) {
-            // out of rounds: the caller decides (allow_unfinished); the state says where it stopped
-            if (tl == 0) {
-              a.isect_sorted[slot] = isect;
-              a.next_level[slot] = level;
-              unfinished++;
-            }
-            max_level = max(max_level, level);
-            active = false;
-          }
-        }
-      }
-    }
-  }
-  unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
-  t_add_stats(st, lane, max_level, node_tests, point_tests, isect_sum, levels_sum, unfinished);
-  const unsigned long long fsum = t_wave_sum((unsigned long long)failed);
-  if (lane == 0 && fsum) atomicAdd(&st[8], fsum);
-}
-
-
 // Start-of-solve state of the packet kernel in one launch: done[] = 1 (a query is "done" unless handed
 // over), tie[] = 0, counters = 0 except [9] = ~0 (min hand-over level), levels[] = -1 if asked for.
 __global__ void __launch_bounds__(256) team_prep_kernel(uint8_t *done, uint8_t *tie, int64_t n, unsigned long long *counters, int32_t *levels) {
@@ -1316,628 +1080,9 @@ __global__ void __launch_bounds__(256) team_prep_kernel(uint8_t *done, uint8_t *
     for (int64_t i = tid; i < n; i += nth) levels[i] = -1;
 }
 
-// ---- exact-distance ties in the reference's order ---------------------------------------------------
-// The reference's per-query lists persist over the rounds (deviceCode.cu:77-85 skips what is listed
-// already, :116,:125 insert with a strict '<'): of two candidates at bit-identical fp32 distances the
-// one that became a candidate in an EARLIER round stays ahead, whatever its index; inside one round
-// the canonical order is by index (oracle/trueknn_oracle.c, decision 2).  The kernels above list by
-// (dist, index) only -- the age would cost every insert a third key word -- and flag the rows where
-// that can matter (a.tie).  Here a team redoes one flagged row with the full key (dist, first level,
-// index): the first level of a candidate is the first radius of the doubling sequence whose box test
-// it passes (the test is monotone in r).  Only neighbours within the row's k-th distance can be
-// part of the answer, and that distance is already known (it does not depend on the order of ties):
-// the walk prunes with it from the start, so a row costs a few wide nodes and leaf blocks.
-// (The stack is the walk's: 6 KB of LDS per wave leaves room for 16 waves per CU; the ball pruning keeps stacks far below.)
-struct HasTie {
-  __host__ __device__ bool operator()(uint8_t t) const { return (t & 0x7f) != 0; }  // (bit 7 alone: team_pass's note, no flag)
-};
-
-template <bool HALO, int NREG>
-__global__ void __launch_bounds__(kTeamBlock) tie_fix_kernel(TeamArgs a, const int32_t *slots, int32_t nslots) {
-  // nslots < 0: `slots` is the kernels' own list (knn_flag_tie), as long as the device-side count says --
-  // launched without the host knowing whether anything was flagged; nothing was: every wave leaves at once
-  // nslots == -2: `slots` is a compacted list whose length hipCUB's select wrote to a.slot_count.  The host's
-  // count of knn_flag_tie calls is only an upper bound of it (a wave-kernel solve that gives up on its
-  // LDS stack is redone by the lane kernel, which flags the same rows a second time).
-  if (nslots == -2)
-    nslots = *a.slot_count;
-  else if (nslots < 0)
-    nslots = (int32_t)min(a.counters[kTieCounter], (unsigned long long)kTieListCap);
-  if (nslots <= 0) return;
-  __shared__ int32_t stack_mem[4 * kWalkStack];
-  __shared__ WalkLevel levels[2][LBVH_WIDE_LEVELS];
-  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kWalkStack;
-  walk_fill_levels<2>(levels[0], a.wide, lane);
-  t_wave_sync();
-  unsigned int failed = 0, stood = 0;
-  int turn_next = 0, turn_left = 0;  // (t_next_slots)
-  for (;;) {
-    const int base = t_next_slots(&a.counters[kTieCounter + 1], a.grab, lane, turn_next, turn_left);
-    if (base >= nslots) break;
-    bool active = base + team < nslots;
-    const int32_t slot = active ? slots[base + team] : 0;
-    const LbvhPoint q = a.bvh.points[slot];
-    const int32_t row = a.bvh.prim_id[slot];
-    const uint32_t tie_word = active ? (uint32_t)a.tie[slot] : 0u;
-    active = active && (tie_word & 0x7fu) != 0u;  // a listed slot that is not flagged (any more) keeps its row
-    const int level = active ? (int)(tie_word & 0x7fu) - 1 : 0;
-    const float q_r0 = a.start_radii ? a.start_radii[row] : a.start_radius;
-    float r = q_r0;
-    for (int i = 0; i < level; i++) r = r * 2.0f;
-    const WalkBox qb(q, r);
-    uint32_t bd[NREG], bl[NREG], bi[NREG];
-#pragma unroll
-    for (int j = 0; j < NREG; j++) {
-      bd[j] = 0x7f7fffffu;  // KNN_EMPTY_KEY = {FLT_MAX, 0}
-      bl[j] = 0u;
-      bi[j] = 0u;
-    }
-    // the row's k-th distance, if the caller asked for distances (else the gate closes as the list fills)
-    float tau2 = INFINITY;
-    if (active) {
-      const int64_t last = (int64_t)row * a.k + (a.k - 1);
-      if (a.out_dist)
-        tau2 = knn_gate_from_worst(a.out_dist[last]);
-      else if (a.out_fb)
-        tau2 = knn_gate_from_worst(a.out_fb[last].dist);
-    }
-    // Every tie of the row between two WRITTEN entries (no `edge`): the row is in (distance, index) order already, which is the
-    // full key's order unless two tied neighbours became candidates at different levels.  Look that up from the row -- two
-    // points per tied pair -- before walking for it: the duplicates of a data set (taxi pick-ups at one street corner) tie in
-    // every row that holds both, always at one level, and are most of what is flagged on such sets (10 M taxi-like points with
-    // 5 % duplicates, k = 10: 0.78 M rows flagged, 2.5 of the solve's 13.1 ms in this pass before this check).
-    if (!HALO && a.row_slot && __ballot(active && !(tie_word & 0x80u)) != 0ull) {
-      bool differs = false;
-      const bool look = active && !(tie_word & 0x80u);
-      uint32_t rd[NREG], ri[NREG];
-#pragma unroll
-      for (int reg = 0; reg < NREG; reg++) {
-        const int j = tl + 16 * reg;
-        rd[reg] = 0xffffffffu;  // (no entry: never equal to a distance)
-        ri[reg] = 0u;
-        if (look && j < a.k) {
-          const int64_t o = (int64_t)row * a.k + j;
-          if (a.out_dist && a.out_idx) {
-            rd[reg] = __float_as_uint(a.out_dist[o]);
-            ri[reg] = (uint32_t)a.out_idx[o];
-          } else if (a.out_fb) {
-            rd[reg] = __float_as_uint(a.out_fb[o].dist);
-            ri[reg] = (uint32_t)a.out_fb[o].ind;
-          } else {
-            differs = true;  // (indices without distances: nothing to compare)
-          }
-        }
-      }
-#pragma unroll
-      for (int reg = 0; reg < NREG; reg++) {
-        uint32_t pd = t_team_shr1(rd[reg]), pi = t_team_shr1(ri[reg]);
-        if (reg > 0) {
-          const uint32_t lane0 = tl == 0 ? 0xffffffffu : 0u;
-          pd = (pd & ~lane0) | (t_dpp<0x121>(rd[reg - 1]) & lane0);
-          pi = (pi & ~lane0) | (t_dpp<0x121>(ri[reg - 1]) & lane0);
-        }
-        const int j = tl + 16 * reg;
-        if (look && j >= 1 && j < a.k && rd[reg] == pd) {
-          if (ri[reg] >= (uint32_t)a.bvh.n || pi >= (uint32_t)a.bvh.n) {
-            differs = true;
-          } else {
-            const LbvhPoint pa = a.bvh.points[a.row_slot[ri[reg]]], pb = a.bvh.points[a.row_slot[pi]];
-            differs |= first_level(pa, q, q_r0, level) != first_level(pb, q, q_r0, level);
-          }
-        }
-      }
-      if (look && !t_team_any(differs, team)) {  // the row stands
-        active = false;
-        stood += tl == 0 ? 1u : 0u;
-      }
-    }
-    bool overflow = false;
-    unsigned long long node_tests = 0;  // (this pass reports no statistics)
-    for (int tree = 0; tree < (HALO ? 2 : 1); tree++) {
-      const LbvhWideView &wv = a.wide[tree];
-      const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
-      if (tv.n <= 0 || wv.levels <= 0) continue;
-      walk_tree<false>(
-          levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
-          // every box beyond the gate goes: nothing is counted here
-          [&](const LbvhBox &bx, int32_t, int) { return !beyond_gate(box_min_dist2(bx, q), tau2); },
-          [&](int32_t b, bool has_b) {
-            LbvhPoint p;
-            float d2;
-            const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
-            unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2);
-            if (pm) {
-              const uint32_t key_d = __float_as_uint(knn_sqrt(d2));
-              const uint32_t key_l = ((pm >> lane) & 1ull) ? first_level(p, q, q_r0, level) : 0u;
-              const uint32_t key_i = (uint32_t)p.id;
-              do {
-                const uint32_t pending_mine = (uint32_t)(pm >> (team * 16)) & 0xffffu;
-                const bool has = pending_mine != 0u;
-                const int src = (team << 4) + (has ? __ffs((int)pending_mine) - 1 : 0);
-                const uint32_t cd = t_lane_read(key_d, src), cl = t_lane_read(key_l, src), ci = t_lane_read(key_i, src);
-                const uint64_t chi = ((uint64_t)cd << 32) | cl;
-                const uint32_t lane0 = tl == 0 ? 0xffffffffu : 0u;
-                uint32_t nd_[NREG], nl_[NREG], ni_[NREG];
-#pragma unroll
-                for (int j = 0; j < NREG; j++) {
-                  uint32_t pd = t_team_shr1(bd[j]), pl = t_team_shr1(bl[j]), pi = t_team_shr1(bi[j]);
-                  if (j > 0) {
-                    pd |= t_dpp<0x121>(bd[j - 1]) & lane0;
-                    pl |= t_dpp<0x121>(bl[j - 1]) & lane0;
-                    pi |= t_dpp<0x121>(bi[j - 1]) & lane0;
-                  }
-                  const uint64_t cur_hi = ((uint64_t)bd[j] << 32) | bl[j], prev_hi = ((uint64_t)pd << 32) | pl;
-                  const bool below_cur = (chi < cur_hi) | ((chi == cur_hi) & (ci < bi[j]));
-                  const bool below_prev = (chi < prev_hi) | ((chi == prev_hi) & (ci < pi));
-                  const bool take_prev = has & ((j > 0) | (tl != 0)) & below_prev;  // entry 0 has no entry before it
-                  const bool take_c = has & below_cur;
-                  nd_[j] = take_prev ? pd : (take_c ? cd : bd[j]);
-                  nl_[j] = take_prev ? pl : (take_c ? cl : bl[j]);
-                  ni_[j] = take_prev ? pi : (take_c ? ci : bi[j]);
-                }
-#pragma unroll
-                for (int j = 0; j < NREG; j++) {
-                  bd[j] = nd_[j];
-                  bl[j] = nl_[j];
-                  bi[j] = ni_[j];
-                }
-                pm &= ~__ballot(lane == src);
-              } while (pm);
-              tau2 = fminf(tau2, knn_gate_from_worst(t_kth_dist<NREG>(bd, a.k, team)));
-            }
-          },
-          [] {}, overflow);
-    }
-    if (active && overflow) {
-      failed += tl == 0 ? 1u : 0u;  // the row keeps its (dist, index) order; reported in tknnSolveInfo.tie_rows_left
-    } else if (active) {
-#pragma unroll
-      for (int reg = 0; reg < NREG; reg++) {
-        const int j = tl + 16 * reg;
-        if (j >= a.k) continue;
-        const int64_t o = (int64_t)row * a.k + j;
-        const int32_t prim = knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]);
-        const float d = __uint_as_float(bd[reg]);
-        if (a.out_idx) a.out_idx[o] = prim;
-        if (a.out_dist) a.out_dist[o] = d;
-        if (a.out_fb) {
-          a.out_fb[o].ind = prim;
-          a.out_fb[o].dist = d;
-        }
-      }
-    }
-  }
-  const unsigned long long fsum = t_wave_sum((unsigned long long)failed);
-  if (lane == 0 && fsum) atomicAdd(&a.counters[kTieCounter + 2], fsum);
-  const unsigned long long ssum = t_wave_sum((unsigned long long)stood);
-  if (lane == 0 && ssum) atomicAdd(&a.counters[kTieCounter + 3], ssum);
-}
-
-
-// ---- k > 64: the list in memory -----------------------------------------------------------------------------------------
-// The reference keeps every query's k-list in global memory and takes any k from its command line (hostCode.cpp:111,
-// deviceCode.cu:77-134).  The kernels above hold up to 64 entries in registers.  Larger lists live in memory, sixteen keys
-// to a CHUNK (lane j of the team reads and writes entry 16 c + j of chunk c: one coalesced 256-byte access, and always the
-// lane's own words), per team that is resident on the device, not per query: a query's list is built anew at every radius
-// level, as in team_walk_kernel, whose walk of the pyramid this kernel shares -- one query per team, its sixteen lanes the
-// child boxes of a wide node or the points of a leaf block.  Candidates wait in the team's LDS buffer and are merged a sorted
-// row of sixteen at a time (t_merge_rows with the registers in memory): the row goes to the first chunk whose largest distance
-// is not below the row's smallest (the chunks' maxima sit in LDS), meets it mirrored -- the sixteen smallest of both stay, the
-// sixteen largest travel on to the next chunk -- until what travels is empty.
-// Keys carry THREE words, (distance, level at which the neighbour first was a candidate, index): the reference's order of
-// bit-identical distances (section 1 of DESIGN.md; tie_fix_kernel's key), so rows come out final and no tie pass follows.
-struct BigKey {
-  uint32_t d, l, i, pad;
-};
-constexpr int kBigMaxChunks = TKNN_MAX_K / 16;
-static_assert(TKNN_MAX_K % 16 == 0 && kBigMaxChunks <= 64, "chunk maxima: 64 words of LDS per team");
-
-__device__ __forceinline__ bool t_less3(uint32_t ad, uint32_t al, uint32_t ai, uint32_t bd, uint32_t bl, uint32_t bi) {
-  const uint64_t ah = ((uint64_t)ad << 32) | al, bh = ((uint64_t)bd << 32) | bl;
-  return (ah < bh) | ((ah == bh) & (ai < bi));
-}
-// one compare-exchange of three-word keys with the lane whose key is (pd, pl, pi): the lower lane keeps the smaller key
-__device__ __forceinline__ void t_exchange3(uint32_t &kd, uint32_t &kl, uint32_t &ki, uint32_t pd, uint32_t pl, uint32_t pi, bool upper) {
-  const bool take = t_less3(pd, pl, pi, kd, kl, ki) != upper;
-  kd = take ? pd : kd;
-  kl = take ? pl : kl;
-  ki = take ? pi : ki;
-}
-#define T_EX3(CTRL, UP) t_exchange3(kd, kl, ki, t_dpp<CTRL>(kd), t_dpp<CTRL>(kl), t_dpp<CTRL>(ki), UP)
-__device__ __forceinline__ void t_sort16_3(uint32_t &kd, uint32_t &kl, uint32_t &ki, int tl) {
-  const bool up1 = (tl & 1) != 0, up2 = (tl & 2) != 0, up4 = (tl & 4) != 0, up8 = (tl & 8) != 0;
-  T_EX3(0xb1, up1);
-  T_EX3(0x1b, up2);
-  T_EX3(0xb1, up1);
-  T_EX3(0x141, up4);
-  T_EX3(0x4e, up2);
-  T_EX3(0xb1, up1);
-  T_EX3(0x140, up8);
-  t_exchange3(kd, kl, ki, t_xor4(kd), t_xor4(kl), t_xor4(ki), up4);
-  T_EX3(0x4e, up2);
-  T_EX3(0xb1, up1);
-}
-__device__ __forceinline__ void t_clean16_3(uint32_t &kd, uint32_t &kl, uint32_t &ki, int tl) {
-  const bool up1 = (tl & 1) != 0, up2 = (tl & 2) != 0, up4 = (tl & 4) != 0, up8 = (tl & 8) != 0;
-  T_EX3(0x128, up8);
-  t_exchange3(kd, kl, ki, t_xor4(kd), t_xor4(kl), t_xor4(ki), up4);
-  T_EX3(0x4e, up2);
-  T_EX3(0xb1, up1);
-}
-#undef T_EX3
-
-template <bool HALO>
-__global__ void __launch_bounds__(kTeamBlock) TKNN_BIGK_ATTR bigk_walk_kernel(TeamArgs a, BigKey *lists, int chunks) {
-  __shared__ int32_t stack_mem[4 * kWalkStack];
-  __shared__ WalkLevel levels[2][LBVH_WIDE_LEVELS];
-  __shared__ BigKey cand_mem[4 * kCandCapacity];     // per team: candidates waiting to be merged, (squared distance, first level, index)
-  __shared__ uint32_t cmax_mem[4 * kBigMaxChunks];   // per team and chunk of its list: the largest distance in it (bits)
-  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kWalkStack;
-  BigKey *my_cand = cand_mem + team * kCandCapacity;
-  uint32_t *my_cmax = cmax_mem + team * kBigMaxChunks;
-  BigKey *my_list = lists + ((size_t)blockIdx.x * 4 + (size_t)team) * (size_t)chunks * 16;
-  walk_fill_levels<2>(levels[0], a.wide, lane);
-  t_wave_sync();
-  const int32_t n = a.bvh.n;
-  const int kc = (a.k - 1) >> 4;  // the chunk of the k-th entry
-  unsigned long long isect_sum = 0, levels_sum = 0, node_tests = 0, point_tests = 0;
-  unsigned int unfinished = 0, failed = 0;
-  int max_level = 0;
-  int turn_next = 0, turn_left = 0;  // (t_next_slots)
-  for (;;) {
-    const int base = t_next_slots(&a.counters[0], a.grab, lane, turn_next, turn_left);
-    if (base >= n) break;
-    const int32_t slot = min(base + team, n - 1);
-    bool has_q = base + team < n;
-    if (has_q && a.skip && (int32_t)a.skip[slot] == a.skip_is) has_q = false;  // (tknnSolveOptions.phase: not a query of this call)
-    const LbvhPoint q = a.bvh.points[slot];
-    const int32_t row = a.bvh.prim_id[slot];
-    int level = 0;
-    int64_t isect = 0;
-    const float q_r0 = a.start_radii ? a.start_radii[row] : a.start_radius;
-    float r = q_r0;
-    bool active = has_q;
-    // A level only COUNTS (deviceCode.cu:74) as long as the query is unlikely to finish at it -- its box grows eightfold per
-    // level, so: fewer than k / 5 others at the level before, and in the first levels the scene's mean density (a.first_step)
-    // -- and keeps no list; a level that counts k others after all is walked once more, with the list.  (Every level with its
-    // list: 10 M uniform points at k = 65 took three times the k = 64 solve.)
-    uint32_t prev_others = 0;
-    bool again = false;  // this level has counted k others without a list
-    while (__ballot(active) != 0ull) {  // one radius level for every team that is still at work
-      const bool select_on = again || level >= a.first_step || prev_others * 5u >= (uint32_t)a.k;
-      const unsigned long long select_m = __ballot(select_on);
-      const WalkBox qb(q, r);
-      uint32_t part = 0;       // my lane's share of the candidate count of this level
-      uint32_t n_list = 0;     // keys in my team's list (the same in its lanes)
-      uint32_t kth_bits = 0x7f7fffffu;  // distance of the list's k-th entry (FLT_MAX: not that many yet)
-      // (a squared distance that has overflowed is no neighbour: the reference's strict `<` against its initial FLT_MAX,
-      // hostCode.cpp:41, deviceCode.cu:116)
-      float tau2 = 3.402823466e+38f;
-      bool overflow = false;
-      uint32_t fill_n = 0;
-      auto merge_buffer = [&]() {
-        t_wave_sync();
-#pragma unroll 1
-        for (int rw = 0; rw < kCandCapacity / 16; rw++) {
-          if (rw > 0 && __ballot(fill_n > 16u * (uint32_t)rw) == 0ull) break;
-          const uint32_t at = 16u * (uint32_t)rw + (uint32_t)tl;
-          const bool have = at < fill_n;
-          BigKey c = {0u, 0u, 0u, 0u};
-          if (have) c = my_cand[at];
-          const float dist = knn_sqrt(__uint_as_float(c.d));
-          uint32_t kd = have ? __float_as_uint(dist) : 0x7f7fffffu, kl = have ? c.l : 0u, ki = have ? c.i : 0u;  // the empty key past the end
-          t_sort16_3(kd, kl, ki, tl);
-          const uint32_t in_row = fill_n > 16u * (uint32_t)rw ? min(fill_n - 16u * (uint32_t)rw, 16u) : 0u;
-          const uint32_t row_min = t_lane_read(kd, team << 4);
-          const int nch = (int)((n_list + 15u) >> 4);  // chunks that hold keys
-          // the first chunk a key of the row can get into: the chunks whose largest distance is below the row's smallest stay
-          uint32_t below = 0;
-          for (int j = tl; j < nch; j += 16) below += my_cmax[j] < row_min ? 1u : 0u;
-          const int j0 = (int)t_team_sum(below);
-          const int jend = min(nch, chunks - 1);  // ... and the last: the first chunk without keys, if the list has room for one
-          bool live = in_row > 0u;                // what travels still holds keys
-          int j_first = live ? j0 : 0x7fffffff;
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) j_first = min(j_first, __shfl_xor(j_first, off));
-          for (int j = j_first; __ballot(live && j <= jend) != 0ull; j++) {
-            const bool on = live && j >= j0 && j <= jend;
-            BigKey e = {0x7f7fffffu, 0u, 0u, 0u};
-            if (on && j < nch) e = my_list[(size_t)j * 16 + tl];
-            const uint32_t od = t_dpp<0x140>(kd), ol = t_dpp<0x140>(kl), oi = t_dpp<0x140>(ki);  // the row's key 15 - tl
-            const bool take = t_less3(od, ol, oi, e.d, e.l, e.i);
-            uint32_t hd = take ? e.d : od, hl = take ? e.l : ol, hi_i = take ? e.i : oi;  // the larger of the pair: travels on
-            uint32_t ld = take ? od : e.d, ll = take ? ol : e.l, li = take ? oi : e.i;    // the smaller: stays in this chunk
-            t_clean16_3(ld, ll, li, tl);
-            t_clean16_3(hd, hl, hi_i, tl);
-            const uint32_t kth_here = t_lane_read(ld, (team << 4) + ((a.k - 1) & 15));
-            if (on) {
-              my_list[(size_t)j * 16 + tl] = BigKey{ld, ll, li, 0u};
-              if (tl == 15) my_cmax[j] = ld;
-              if (j == kc) kth_bits = kth_here;
-              kd = hd, kl = hl, ki = hi_i;
-            }
-            const bool more = ((uint32_t)(__ballot(kd != 0x7f7fffffu) >> (team * 16)) & 0xffffu) != 0u;
-            if (on) live = more && j < nch;  // (a chunk that held no key takes all that travels)
-          }
-          n_list = min((uint32_t)chunks * 16u, n_list + in_row);
-          t_wave_sync();  // (the chunk maxima are read by the next row's lanes)
-        }
-        fill_n = 0;
-        tau2 = fminf(3.402823466e+38f, knn_gate_from_worst(__uint_as_float(kth_bits)));
-      };
-      for (int tree = 0; tree < (HALO ? 2 : 1); tree++) {
-        const LbvhWideView &wv = a.wide[tree];
-        const LbvhView &tv = tree == 0 ? a.bvh : a.halo;
-        if (tv.n <= 0 || wv.levels <= 0) continue;
-        const int32_t clean_end = tv.n - (tv.nan_count ? *tv.nan_count : 0);  // NaN points sort last
-        // (the chunk loop of a node is not unrolled: the merge is large)
-        walk_tree<true>(
-            levels[tree], wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
-            [&](const LbvhBox &bx, int32_t c, int lvl) { return !walk_count_box(bx, q, qb, tau2, c, lvl, clean_end, part); },
-            [&](int32_t b, bool has_b) {
-              LbvhPoint p;
-              float d2;
-              const unsigned long long in_m = walk_block_test(tv.points, b, has_b, tl, q, qb, p, d2);
-              point_tests += has_b ? 1u : 0u;
-              part = t_count(part, in_m);
-              const unsigned long long pm = in_m & __ballot(p.id != q.id) & __ballot(d2 <= tau2) & select_m;
-              if (pm) {
-                const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;  // my team's lanes with a candidate
-                if ((mine16 >> tl) & 1u)
-                  my_cand[fill_n + __popc(mine16 & ((1u << tl) - 1u))] = BigKey{__float_as_uint(d2), first_level(p, q, q_r0, level), (uint32_t)p.id, 0u};
-                fill_n += __popc(mine16);
-                if (__ballot(fill_n >= 16u) != 0ull) merge_buffer();
-              }
-            },
-            [] {}, overflow);
-      }
-      if (__ballot(fill_n > 0u) != 0ull) merge_buffer();
-      // ---- the level's outcome, per team ----
-      const uint32_t cnt = t_team_sum(part);
-      const uint32_t others = cnt ? cnt - 1u : 0u;  // a query lies in its own box
-      const bool fin = active && !overflow && others >= (uint32_t)a.k;
-      if (active && overflow) {  // (cannot happen: 63 siblings wait on each of at most six levels; reported, never wrong)
-        failed += tl == 0 ? 1u : 0u;
-        active = false;
-      } else if (active && fin && !select_on) {
-        again = true;  // the same level once more, with its list
-      } else if (active) {
-        again = false;
-        prev_others = others;
-        isect += cnt;
-        levels_sum += tl == 0 ? 1ull : 0ull;
-        if (fin) {
-          for (int j = 0; j <= kc; j++) {
-            const int en = 16 * j + tl;
-            if (en >= a.k) continue;
-            const BigKey ky = my_list[(size_t)j * 16 + tl];
-            const int32_t prim = (ky.d == 0x7f7fffffu && ky.i == 0u) ? -1 : (int32_t)ky.i;
-            t_write_entry(a.out_idx, a.out_dist, a.out_fb, (int64_t)row * a.k + en, prim, __uint_as_float(ky.d), en, a.k, isect);
-          }
-          if (tl == 0) {
-            if (a.out_isect) a.out_isect[row] = isect;
-            if (a.out_level) a.out_level[row] = level;
-            a.done[slot] = 1;
-            isect_sum += (unsigned long long)isect;
-          }
-          max_level = max(max_level, level + 1);
-          active = false;
-        } else {
-          level++;
-          r = r * 2.0f;  // hostCode.cpp:321
-          if (level >= a.max_rounds) {
-            if (tl == 0) {
-              a.isect_sorted[slot] = isect;
-              a.next_level[slot] = level;
-              unfinished++;
-            }
-            max_level = max(max_level, level);
-            active = false;
-          }
-        }
-      }
-    }
-  }
-  unsigned long long *st = a.counters + kStatBase + (blockIdx.x & (kStatStripes - 1)) * kStatStride;  // (my stripe: see kStatBase)
-  t_add_stats(st, lane, max_level, node_tests, point_tests, isect_sum, levels_sum, unfinished);
-  const unsigned long long fsum = t_wave_sum((unsigned long long)failed);
-  if (lane == 0 && fsum) atomicAdd(&st[8], fsum);
-}
-
 }  // namespace
 
 bool Engine::team_kernel_supports(int k) { return k >= 1 && k <= 64; }
-
-bool Engine::bigk_supports(int k) { return k > 64 && k <= TKNN_MAX_K; }
-
-// The team kernels' end-of-wave statistics live in stripes (kStatBase): zeroed before a launch of a walk (the packet kernel's
-// prep launch does it itself), copied behind h_counters_[16] after it and folded once the stream is idle
-void Engine::reset_stat_stripes(hipStream_t s) {
-  OWLMI_HIP(hipMemsetAsync(counters_ + kStatBase, 0, kStatStripes * kStatStride * sizeof(unsigned long long), s));
-}
-void Engine::fetch_stat_stripes(hipStream_t s) {
-  OWLMI_HIP(hipMemcpyAsync(h_counters_ + kHostStripes, counters_ + kStatBase, kStatStripes * kStatStride * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-}
-KernelStats Engine::fold_stat_stripes(bool with_min) const {
-  KernelStats sum;
-  if (with_min) sum.first_handover_level = ~0ull;
-  for (int j = 0; j < kStatStripes; j++) {
-    const KernelStats st = KernelStats::from_words(h_counters_ + kHostStripes + j * kStatStride);
-    sum.rounds = std::max(sum.rounds, st.rounds);
-    sum.node_tests += st.node_tests;
-    sum.point_tests += st.point_tests;
-    sum.intersections += st.intersections;
-    sum.flags |= st.flags;
-    sum.active_rounds += st.active_rounds;
-    sum.unfinished += st.unfinished;
-    sum.handed_over += st.handed_over;
-    if (with_min) sum.first_handover_level = std::min(sum.first_handover_level, st.first_handover_level);
-  }
-  return sum;
-}
-
-void Engine::reset_solve_state(int32_t *levels, hipStream_t s) {
-  const int64_t n = bvh_.size();
-  OWLMI_HIP(hipMemsetAsync(tie_, 0, (size_t)n, s));
-  OWLMI_HIP(hipMemsetAsync(counters_, 0, kCounters * sizeof(unsigned long long), s));
-  OWLMI_HIP(hipMemsetAsync(done_, 0, (size_t)n, s));
-  OWLMI_HIP(hipMemsetAsync(isect_sorted_, 0, (size_t)n * sizeof(int64_t), s));
-  OWLMI_HIP(hipMemsetAsync(next_level_, 0, (size_t)n * sizeof(int32_t), s));
-  if (levels) OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)n * sizeof(int32_t), s));
-}
-
-template <class A>
-A Engine::team_args(const SolveArgs &sa) const {
-  A a;
-  std::memset(&a, 0, sizeof a);
-  a.bvh = bvh_.view();
-  a.halo = halo_view();
-  a.wide[0] = bvh_.wide_view();
-  if (halo_count() > 0) a.wide[1] = halo_.wide_view();
-  a.start_radius = sa.start_radius;
-  a.start_radii = sa.d_start_radii;
-  a.k = sa.k;
-  a.out_idx = sa.d_idx;
-  a.out_dist = sa.d_dist;
-  a.out_fb = sa.d_fb;
-  a.tie = tie_;
-  a.tie_list = tie_list_;
-  a.counters = counters_;
-  return a;
-}
-
-template <class A>
-void Engine::set_solve_args(A &a, const SolveArgs &sa) const {
-  a.max_rounds = sa.max_rounds;
-  a.allow_unfinished = sa.allow_unfinished ? 1 : 0;
-  a.out_isect = sa.d_isect;
-  a.out_level = sa.d_levels;
-  a.done = done_;
-  a.skip = sa.phase ? boundary_ : nullptr;
-  a.skip_is = sa.phase == 1 ? 1 : 0;
-  a.isect_sorted = isect_sorted_;
-  a.next_level = next_level_;
-}
-
-template <class Flag>
-int32_t *Engine::compact_flagged_slots(const uint8_t *bytes, Flag flag, hipStream_t s) {
-  const int64_t n = bvh_.size();
-  int32_t *slots = slot_list(n), *d_count = slots + n;
-  hipcub::CountingInputIterator<int32_t> iota(0);
-  hipcub::TransformInputIterator<bool, Flag, const uint8_t *> flags(bytes, flag);
-  size_t tmp_bytes = 0;
-  OWLMI_HIP(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, iota, flags, slots, d_count, (int)n, s));
-  OWLMI_HIP(hipcub::DeviceSelect::Flagged(workspace(tmp_bytes), tmp_bytes, iota, flags, slots, d_count, (int)n, s));
-  return d_count;
-}
-
-// k > 64: every query through bigk_walk_kernel, one query per team, the k-lists in memory (one per resident team)
-void Engine::solve_bigk(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
-  const int64_t n = bvh_.size();
-  TeamArgs a = team_args<TeamArgs>(sa);
-  set_solve_args(a, sa);
-  // the first level that keeps a list whatever the level before has counted: where a box is expected to hold k / 2 others at the
-  // scene's mean density (a work estimate only; a per-query radius schedule has none: every level keeps its list)
-  a.first_step = sa.d_start_radii ? 0 : first_step_estimate(sa) - 1;
-  a.grab = 1;
-  int per_cu = 4;
-  const void *entry = halo_count() > 0 ? (const void *)bigk_walk_kernel<true> : (const void *)bigk_walk_kernel<false>;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, entry, kTeamBlock, 0) != hipSuccess) per_cu = 4;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)cu_count_ * std::max(1, per_cu)));
-  int chunks = (sa.k + 15) / 16;
-  BigKey *lists = (BigKey *)workspace((size_t)blocks * 4 * (size_t)chunks * 16 * sizeof(BigKey));
-  // (three-word keys: no row is left to the tie pass; phases 2, 3 complete an earlier call's rows and levels)
-  reset_solve_state(sa.phase < 2 ? sa.d_levels : nullptr, s);
-  reset_stat_stripes(s);
-  OWLMI_HIP(hipEventRecord(ev_a_, s));
-  void *kargs[] = {(void *)&a, (void *)&lists, (void *)&chunks};
-  OWLMI_HIP(hipLaunchKernel(entry, dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
-  OWLMI_HIP(hipGetLastError());
-  OWLMI_HIP(hipEventRecord(ev_b_, s));
-  fetch_stat_stripes(s);
-  OWLMI_HIP(hipStreamSynchronize(s));
-  const KernelStats st = fold_stat_stripes(false);
-  float ms = 0;
-  OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  if (st.handed_over) throw ArgError{TKNN_E_UNSUPPORTED, "k > 64: a query's walk outgrew its stack (a pyramid of more than six levels?)"};
-  const tknnSolveInfo mine = solve_info(st, sa.start_radius, TKNN_KERNEL_TEAM, chunks * 16, ms);
-  if (mine.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
-  ties_early_ = true;  // nothing flagged, nothing to redo
-  early_tie_rows_ = early_tie_left_ = 0;
-  early_tie_ms_ = 0.f;
-  if (info) *info = mine;
-}
-
-
-void Engine::launch_tie_fix(const SolveArgs &sa, const int32_t *slots, int32_t nslots, int blocks, hipStream_t s, const int32_t *d_slot_count,
-                            int64_t expected_rows) {
-  TeamArgs a = team_args<TeamArgs>(sa);
-  a.slot_count = d_slot_count;
-  // (10 M taxi-like points, k = 10 / 24, 0.78 / 2.3 M rows, 24 workgroups per CU: turns of 4 / 8 / 12 / 24 / 32 slots 2.55 / 1.42 / 1.08 /
-  // 0.89 / 0.94 ms and 7.2 / 3.8 / 2.6 / 1.81 / 1.85 ms; 64 and more slots a turn: the waves' own chains of loads show, 2.8 ms and up)
-  a.grab = grab_for(expected_rows, blocks, 6, 6);
-  const bool look = !ids_given_ && !(getenv("TKNN_TIE_LOOK") && !strcmp(getenv("TKNN_TIE_LOOK"), "0"));  // (TKNN_TIE_LOOK=0: A/B switch)
-  a.row_slot = look ? bvh_.row_slot_device() : nullptr;
-  using FixEntry = void (*)(TeamArgs, const int32_t *, int32_t);
-  static const FixEntry entries[2][4] = {{tie_fix_kernel<false, 1>, tie_fix_kernel<false, 2>, tie_fix_kernel<false, 3>, tie_fix_kernel<false, 4>},
-                                         {tie_fix_kernel<true, 1>, tie_fix_kernel<true, 2>, tie_fix_kernel<true, 3>, tie_fix_kernel<true, 4>}};
-  const FixEntry entry = entries[halo_count() > 0 ? 1 : 0][nreg_for(sa.k) - 1];
-  void *kargs[] = {(void *)&a, (void *)&slots, (void *)&nslots};
-  OWLMI_HIP(hipLaunchKernel((const void *)entry, dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
-}
-
-void Engine::fix_ties(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
-  if (ties_early_) {  // solve_team's own launch has seen them all
-    if (early_tie_rows_ && getenv("TKNN_VERBOSE"))
-      fprintf(stderr, "[ties] %lld rows redone in the reference's tie order: %.3f ms, %lld left\n", (long long)early_tie_rows_, early_tie_ms_, (long long)early_tie_left_);
-    if (info) {
-      info->tie_rows = early_tie_rows_;
-      info->tie_rows_left = early_tie_left_;
-      info->tie_ms = early_tie_ms_;
-      info->solve_ms += early_tie_ms_;
-    }
-    return;
-  }
-  const int64_t n = bvh_.size();
-  OWLMI_HIP(hipMemsetAsync(counters_ + kTieCounter + 1, 0, 3 * sizeof(unsigned long long), s));  // work cursor, rows left
-  // First go: the kernels' own list, count read on the device -- no host round trip before the launch;
-  // the usual handful of rows (or none) costs one small launch behind the solve.
-  OWLMI_HIP(hipEventRecord(ev_a_, s));
-  launch_tie_fix(sa, tie_list_, -1, std::min(cu_count_ * 4, kTieListCap / 4), s);  // a team per listed row
-  OWLMI_HIP(hipEventRecord(ev_b_, s));
-  OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_ + kTieCounter, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  const int64_t flagged = (int64_t)h_counters_[0];
-  if (flagged > kTieListCap) {
-    // more than the list holds (quantised coordinates, lattices): all flagged slots, compacted from tie_
-    // (rows redone twice come out the same: the gate is the row's k-th distance, which no order changes)
-    const int32_t *d_count = compact_flagged_slots(tie_, HasTie{}, s);
-    OWLMI_HIP(hipMemsetAsync(counters_ + kTieCounter + 1, 0, 3 * sizeof(unsigned long long), s));
-    OWLMI_HIP(hipEventRecord(ev_a_, s));
-    // the list's length is read on the device (d_count): `flagged` counts flag calls, an upper bound
-    const int64_t rows = std::min<int64_t>(flagged, n);
-    launch_tie_fix(sa, slot_list_, -2, (int)std::min<int64_t>((rows + 3) / 4, (int64_t)cu_count_ * 24), s, d_count, rows);
-    OWLMI_HIP(hipEventRecord(ev_b_, s));
-    OWLMI_HIP(hipMemcpyAsync(h_counters_, counters_ + kTieCounter, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    OWLMI_HIP(hipStreamSynchronize(s));
-    float again = 0;
-    OWLMI_HIP(hipEventElapsedTime(&again, ev_a_, ev_b_));
-    ms += again;
-  }
-  if (flagged && getenv("TKNN_VERBOSE"))
-    fprintf(stderr, "[ties] %lld rows redone in the reference's tie order: %.3f ms, %llu left (%llu stood after a look at the written row)\n", (long long)flagged, ms,
-            h_counters_[2], h_counters_[3]);
-  if (info) {
-    info->tie_rows = flagged;
-    info->tie_rows_left = (int64_t)h_counters_[2];
-    info->tie_ms = ms;
-    info->solve_ms += ms;
-  }
-}
 
 
 // How many radius levels the first gather of every packet should serve: with the average density
@@ -1952,45 +1097,10 @@ int Engine::first_step_estimate(const SolveArgs &sa) const {
   return 3;
 }
 
-// One query per team, each from the level its solve state holds: what exhausts its stack keeps that state untouched and goes
-// on to lane rounds from lane_level
-template <class A>
-tknnSolveInfo Engine::walk(const SolveArgs &sa, A a, int nreg, const int32_t *slots, int32_t nslots, int lane_level,
-                           bool count_lane_launches, hipStream_t s) {
-  using WalkEntry = void (*)(A, const int32_t *, int32_t);
-  static const WalkEntry walks[2][4] = {{team_walk_kernel<false, 1>, team_walk_kernel<false, 2>, team_walk_kernel<false, 3>, team_walk_kernel<false, 4>},
-                                        {team_walk_kernel<true, 1>, team_walk_kernel<true, 2>, team_walk_kernel<true, 3>, team_walk_kernel<true, 4>}};
-  OWLMI_HIP(hipMemsetAsync(counters_, 0, 16 * sizeof(unsigned long long), s));
-  reset_stat_stripes(s);
-  const int blocks = (int)std::min<int64_t>(((int64_t)nslots + 3) / 4, (int64_t)cu_count_ * kWalkBlocksPerCu);
-  a.grab = 1;  // (queries differ too much for longer turns: measured, see TeamArgs::grab)
-  void *kargs[] = {(void *)&a, (void *)&slots, (void *)&nslots};
-  OWLMI_HIP(hipEventRecord(ev_a_, s));
-  OWLMI_HIP(hipLaunchKernel((const void *)walks[halo_count() > 0 ? 1 : 0][nreg - 1], dim3(blocks), dim3(kTeamBlock), kargs, 0, s));
-  OWLMI_HIP(hipGetLastError());
-  OWLMI_HIP(hipEventRecord(ev_b_, s));
-  fetch_stat_stripes(s);
-  OWLMI_HIP(hipStreamSynchronize(s));
-  const KernelStats st = fold_stat_stripes(false);
-  float ms = 0;
-  OWLMI_HIP(hipEventElapsedTime(&ms, ev_a_, ev_b_));
-  tknnSolveInfo info = solve_info(st, sa.start_radius, TKNN_KERNEL_TEAM, 16 * nreg, ms);
-  if (info.unfinished && !sa.allow_unfinished) throw RoundsExceeded{};
-  if (st.handed_over) {
-    if (sa.d_start_radii)
-      throw ArgError{TKNN_E_UNSUPPORTED, "per-query start radii: a query's candidate walk outgrew the team walk's stack (the lane rounds that take over otherwise use one radius per launch)"};
-    tknnSolveInfo rest;
-    std::memset(&rest, 0, sizeof rest);
-    continue_lane(sa, lane_level, &rest, s);
-    merge_tail(info, rest, sa.start_radius, count_lane_launches);
-  }
-  return info;
-}
-
 bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s) {
   const int64_t n = bvh_.size();
   if (n >= (1ll << 28)) return false;  // leaf blocks are addressed by 32-bit byte offsets; the caller takes the wave kernel
-  TeamArgs a = team_args<TeamArgs>(sa);
+  TeamArgs a = team_args(sa);
   set_solve_args(a, sa);
   a.first_step = sa.d_start_radii ? 1 : first_step_estimate(sa);  // (the estimate is from ONE start radius and the mean density)
   {
@@ -2130,7 +1240,7 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
       solve_wave(sa, &tail, s, /*only_unfinished=*/true);
     } else if (by_walk) {
       // the stragglers' sorted slots as a compact ascending list
-      compact_flagged_slots(done_, NotDone{}, s);
+      compact_slots(/*ties=*/false, s);
       tail = walk(sa, a, nreg, slot_list_, (int32_t)handed, first_handover_level, /*count_lane_launches=*/true, s);
     } else {
       if (sa.d_start_radii) throw ArgError{TKNN_E_UNSUPPORTED, "per-query start radii are served by the team kernels only (TKNN_TEAM_TAIL=lane)"};

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Developer helper: the working tree's team kernel with extra compile flags as owlraytracing_amd/libowl_mi355x_<tag>.so
+# Developer helper: the working tree's packet kernel (trueknn_team.hip alone: the hand-over walk, the tie pass and the
+# k > 64 walk are objects of their own and stay as built) with extra compile flags as owlraytracing_amd/libowl_mi355x_<tag>.so
 #   scripts/ab_variant.sh v72 -DTKNN_MAX_PER_QUERY=72
 set -e
 tag=$1; shift

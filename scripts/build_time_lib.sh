@@ -7,5 +7,5 @@ cd "$(dirname "$0")/../owlraytracing_amd/csrc"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -I../../include -I../../include/owl_shims -I. -Wno-unused-result -Wno-bitwise-instead-of-logical"
 mkdir -p diagobj
 /opt/rocm/bin/hipcc $FLAGS -DTKNN_DIAG_BUILD=1 "$@" -c dbscan.hip -o diagobj/dbscan_time.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC diagobj/lbvh.o diagobj/trueknn.o diagobj/trueknn_wave.o diagobj/trueknn_team.o diagobj/dbscan_time.o diagobj/halo_select.o diagobj/owl_runtime.o -o ../libowl_mi355x_time.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $(ls diagobj/*.o | grep -v '/dbscan\(_time\)\?\.o$') diagobj/dbscan_time.o -o ../libowl_mi355x_time.so
 echo built owlraytracing_amd/libowl_mi355x_time.so

@@ -1,6 +1,6 @@
 // issue_rate.hip -- developer microbenchmark (not part of the library): how many wave64 instructions per
 // cycle one SIMD of gfx950 issues, per instruction kind and per waves/SIMD.  Settles what "VALU busy"
-// means for trueknn_team.hip.   hipcc --offload-arch=gfx950 -O3 issue_rate.hip -o issue_rate
+// means for the team kernels (trueknn_team.hip, trueknn_tail.hip, trueknn_bigk.hip).   hipcc --offload-arch=gfx950 -O3 issue_rate.hip -o issue_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>

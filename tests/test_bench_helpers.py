@@ -26,6 +26,29 @@ def test_fingerprints_are_per_kernel():
     assert team == _lib.source_fingerprint("team_kernel")
 
 
+def test_fingerprints_follow_the_split_of_the_team_kernels(tmp_path, monkeypatch):
+    """The packet kernel, the hand-over walk with the tie pass, and the k > 64 walk are three files: an edit of
+    trueknn_tail.hip or trueknn_bigk.hip changes the library's fingerprint and that of the file's own kernels, and leaves
+    the packet kernel's, RT-DBSCAN's and the other file's kernels' as they were (on a copy of csrc/ and include/)."""
+    import shutil
+
+    pkg = tmp_path / "owlraytracing_amd"
+    shutil.copytree(os.path.join(_lib._HERE, "csrc"), pkg / "csrc", ignore=shutil.ignore_patterns("*.o", "diagobj"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    monkeypatch.setattr(_lib, "_HERE", str(pkg))
+    kernels = (None, "team_kernel", "team_prep_kernel", "team_walk_kernel", "tie_fix_kernel", "bigk_walk_kernel", "db_group_union_kernel")
+
+    def prints():
+        return {kernel: _lib.source_fingerprint(kernel) for kernel in kernels}
+
+    for name, own in (("trueknn_tail.hip", {None, "team_walk_kernel", "tie_fix_kernel"}), ("trueknn_bigk.hip", {None, "bigk_walk_kernel"})):
+        before = prints()
+        with open(pkg / "csrc" / name, "ab") as fh:
+            fh.write(b"\n")
+        after = prints()
+        assert {kernel for kernel in kernels if after[kernel] != before[kernel]} == own, name
+
+
 def test_committed_records_name_the_sources_they_were_taken_on():
     recs = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
     assert recs, "profiles/hbm_traffic.json is empty"

@@ -175,7 +175,7 @@ def test_tile_with_halo_through_the_team_walk_alone(engines, monkeypatch, k):
     _tile_with_halo(engines, k, "team")
 
 
-_TAIL_KS = (5, 17)
+_TAIL_KS = (5, 17, 33, 48)  # one, two and three list registers per lane (k = 33: the list not full, k = 48: full)
 _TAIL_CHILD = r"""
 import sys
 import numpy as np
@@ -216,7 +216,7 @@ def walk_tail(tmp_path_factory):
 @pytest.mark.parametrize("k", _TAIL_KS)
 def test_tile_with_halo_handed_over_to_the_team_walk(walk_tail, k):
     """(c) with a tail: the clustered set at a start radius far too large for its cores, so that the packet kernel hands
-    its queries over, and the team walk (TKNN_TEAM_TAIL=walk; one and two list registers per lane) finishes them over both
+    its queries over, and the team walk (TKNN_TEAM_TAIL=walk; one, two and three list registers per lane) finishes them over both
     trees.  The engine says so (TKNN_VERBOSE), else the case would pass without the walk."""
     said, rows = walk_tail
     m = re.search(r"\[team\] (\d+) of \d+ queries handed over .* team walk ", said[k])

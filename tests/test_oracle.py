@@ -186,7 +186,7 @@ def test_start_radius_sampler_is_seeded_and_sane():
 
 
 def test_tie_flag_bound_never_misses_a_cross_round_tie():
-    """The team kernels drop a tie from the tie pass when `tie_may_straddle` (trueknn_team.hip) says
+    """The team kernels drop a tie from the tie pass when `tie_may_straddle` (team_lanes.h) says
     that two candidates at that fp32 distance cannot have become candidates in different rounds.
     Restated here in float32 and checked against the literal box test of every round
     (deviceCode.cu:38-56): whenever two points at bit-identical distances from a query have
