@@ -432,7 +432,7 @@ TKNN_API int tknnExportTree(tknnEngine e, void *nodes, int32_t *rope_node, int32
 /* Test hook: the builder's two side tables of a point tree with n > 1 (host buffers).
  *   split_owner  n-1: the internal node that splits its range after sorted position s -- an internal node i is a left
  *                child iff i is the LAST position of its range (parent = split_owner[i]), else a right child (parent =
- *                split_owner[i-1]); RT-DBSCAN climbs with it (owlraytracing_amd/csrc/dbscan.hip, db_uniform_kernel)
+ *                split_owner[i-1]); RT-DBSCAN climbs with it (owlraytracing_amd/csrc/dbscan_union.hip, db_uniform_kernel)
  *   block_paths  ceil(n/64) x 5: per block of 64 sorted slots the deepest internal node whose range holds the whole block
  *                (last word) and its four nearest ancestors, farthest first, the root where the path is shorter            */
 TKNN_API int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_paths, void *stream);

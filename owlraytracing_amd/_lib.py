@@ -246,15 +246,26 @@ def check(rc):
 
 # native sources a kernel's code does NOT depend on, by kernel-name prefix (the FIRST matching prefix counts: team_walk_ stands
 # before team_): a committed profile of the packet kernel stays valid when only the tie pass, the k > 64 walk or the
-# clustering kernels change, and the other way round
-_NOT_TEAM = ("dbscan.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip", "owl_runtime.cpp")
+# clustering kernels change, and the other way round; one of the label pass when only the union pass changes
+_NOT_TEAM = ("dbscan.hip", "dbscan_core.hip", "dbscan_union.hip", "dbscan_label.hip", "db_device.h", "db_call.h", "halo_select.hip", "radius_query.hip",
+             "radius_knn.hip", "owl_runtime.cpp")
+# RT-DBSCAN's kernels are in three files by pass; dbscan.hip, the host side that decides their grids and arguments, counts for all
+_NOT_DB = ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip",
+           "owl_runtime.cpp")
+_NOT_DB_CORE, _NOT_DB_UNION = _NOT_DB + ("dbscan_union.hip", "dbscan_label.hip"), _NOT_DB + ("dbscan_core.hip", "dbscan_label.hip")
 _NOT_IN = {
     "team_walk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),  # trueknn_tail.hip
     "tie_fix_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),
     "bigk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_tail.hip"),  # trueknn_bigk.hip
     "team_": _NOT_TEAM + ("trueknn_tail.hip", "trueknn_bigk.hip"),  # trueknn_team.hip: team_kernel, team_prep_kernel
-    "db_": ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip",
-            "owl_runtime.cpp"),
+    "db_core_": _NOT_DB_CORE,  # dbscan_core.hip: db_core_kernel, db_core_pos_blocks_kernel, db_core_from_labels_kernel
+    "db_flag_count_": _NOT_DB_CORE,
+    "db_next_core_": _NOT_DB_CORE,
+    "db_noise_probe_": _NOT_DB_CORE,
+    "db_union_": _NOT_DB_UNION,  # dbscan_union.hip
+    "db_group_": _NOT_DB_UNION,  # db_group_kernel, db_group_list_kernel, db_group_union_kernel
+    "db_uniform_": _NOT_DB_UNION,
+    "db_": _NOT_DB + ("dbscan_core.hip", "dbscan_union.hip"),  # dbscan_label.hip: every other db_ kernel (db_rows_kernel and db_rows_from_slots_kernel among them)
 }
 
 

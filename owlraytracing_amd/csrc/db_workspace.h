@@ -1,4 +1,4 @@
-// db_workspace.h -- RT-DBSCAN's scratch (dbscan.hip) as byte offsets into the engine's workspace: one layout for the full
+// db_workspace.h -- RT-DBSCAN's scratch (db_call.h, dbscan.hip) as byte offsets into the engine's workspace: one layout for the full
 // clustering (tknnDbscan, tknnDbscanAssign), one for a growth round (tknnDbscanNoise, the rounds of tknnDbscanAuto), one for
 // the labels of points that are not in the set (tknnDbscanQuery).  The
 // offsets are computed here and nowhere else; no HIP in this file (tests/test_db_workspace.py compiles it for the host).

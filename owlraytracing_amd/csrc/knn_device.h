@@ -50,7 +50,7 @@ __device__ __forceinline__ int32_t knn_key_prim(uint64_t key) {
 constexpr int kTieCounter = 32;  // no kernel's own counter reset reaches this far
 constexpr int kCounters = 40;
 constexpr int kTieListCap = 4096;
-// RT-DBSCAN's words of the counter array (dbscan.hip; a call zeroes the whole array first):
+// RT-DBSCAN's words of the counter array (db_device.h, dbscan.hip; a call zeroes the whole array first):
 constexpr int kDbGroups = 8;      // length of the group list
 constexpr int kDbOverflows = 17;  // packet walks of db_group_union_kernel that ran out of stack (the host then falls back)
 constexpr int kDbNotCore = 19;    // length of the list of the slots that are not core

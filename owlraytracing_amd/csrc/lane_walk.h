@@ -1,6 +1,7 @@
 // lane_walk.h -- ONE LANE's stackless rope walk of the binary LBVH for one query, and the box arithmetic around it, shared by the
 // kernels that walk one query per lane: lane_round_kernel and repair_kernel (trueknn.hip), query_lane_kernel (trueknn_query.hip),
-// and in dbscan.hip for_each_core_group (unions, border, label, assign), db_core_body's neighbour count and db_has_core_neighbour.
+// and RT-DBSCAN's for_each_core_group (unions, border, label, assign, query) and db_count_from (db_core_body's neighbour count) in
+// db_device.h and db_has_core_neighbour in dbscan_core.hip.
 // What a walk does at a node and at a point comes in as two callables; every function is inlined into its caller.  The box tests
 // below, their parenthesisation and the counting rule's margin are what make rows equal the reference's bit for bit: they are
 // written here once.  (The 16-lane team walk of the box pyramid is team_walk.h; the wave-uniform walks keep their own loops.)

@@ -1,5 +1,5 @@
 // query_order.h -- the order in which the engine works through query points that are NOT in the tree (tknnQuery in
-// trueknn_query.hip, tknnDbscanQuery in dbscan.hip): along the tree's own curve, so that the lanes of a wave and the waves of a
+// trueknn_query.hip, tknnDbscanQuery in dbscan.hip, its kernel in dbscan_label.hip): along the tree's own curve, so that the lanes of a wave and the waves of a
 // workgroup's neighbours walk neighbouring nodes.  The key kernel and the radix sort are written here once; a caller brings the
 // four columns and the sort's temporary storage from its own workspace layout.
 #pragma once

@@ -1,7 +1,7 @@
 // radius_query.hip -- fixed-radius neighbour lists for query points that are NOT in the tree (tknnRadiusQuery, include/owlknn.h).
 //
 // Row j holds the points p of the built set with sqrt((dx*dx + dy*dy) + dz*dz) <= radius, every operation fp32 and uncontracted:
-// knn_sqrt(knn_dist2(..)) <= r, the predicate of dbscan.hip, so a row's length is the count tknnDbscanQuery gives.  Rows are
+// knn_sqrt(knn_dist2(..)) <= r, the predicate of RT-DBSCAN (db_device.h), so a row's length is the count tknnDbscanQuery gives.  Rows are
 // CSR: a COUNT pass writes the exclusive scan of the row lengths into d_offsets, a FILL pass writes row j into its segment
 // d_offsets[j] .. d_offsets[j + 1] and never outside it (the two passes of tknnHaloSelect).
 //   1. query_order (query_order.h): the queries along the tree's own curve, as tknnQuery orders them;

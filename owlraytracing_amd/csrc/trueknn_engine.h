@@ -132,7 +132,7 @@ tknnSolveInfo solve_info(const KernelStats &st, float start_radius, int kernel, 
 // its radius, work, time and unfinished queries summed; launches only with `count_launches`
 void merge_tail(tknnSolveInfo &into, const tknnSolveInfo &tail, float start_radius, bool count_launches);
 
-// dbscan.hip: out[seg[i]] = min(out[seg[i]], val[i]) for seg[i] >= 0 (tknnSegmentMin)
+// dbscan_label.hip: out[seg[i]] = min(out[seg[i]], val[i]) for seg[i] >= 0 (tknnSegmentMin)
 void db_segment_min(const int32_t *d_seg, const int64_t *d_val, int64_t n, int64_t *d_out, hipStream_t s);
 
 // test hook: the wave kernel's exact candidate thresholds for (q, r) pairs (trueknn_wave.hip)
@@ -182,7 +182,7 @@ class Engine {
   const Lbvh &halo_tree() const { return halo_; }  // meaningful while has_halo()
 
  private:
-  struct DbCall;  // dbscan.hip: one RT-DBSCAN call -- its knobs, its kernels' argument block and its launches, in steps
+  struct DbCall;  // db_call.h: one RT-DBSCAN call -- its knobs, its kernels' argument block and its launches, in steps
   void solve_lane(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s);
   // lane rounds over the queries another kernel left with done_[slot] == 0, each from next_level_[slot]
   void continue_lane(const SolveArgs &sa, int first_level, tknnSolveInfo *info, hipStream_t s);

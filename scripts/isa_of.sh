@@ -2,6 +2,7 @@
 # gfx950 assembly of ONE kernel of a .hip file (no GPU needed):
 #   scripts/isa_of.sh owlraytracing_amd/csrc/trueknn_team.hip team_kernelILb0ELi1ELb0E [out.s] [extra hipcc flags...]
 #   scripts/isa_of.sh owlraytracing_amd/csrc/trueknn_tail.hip team_walk_kernelILb0ELi1E    (trueknn_bigk.hip: bigk_walk_kernel)
+#   scripts/isa_of.sh owlraytracing_amd/csrc/dbscan_union.hip db_group_union_kernel
 # <mangled-substring> selects the function whose "Begin function" line contains it.
 set -e
 src=$(realpath "$1"); pat=$2; out=${3:-/tmp/isa_of.s}; shift 3 2>/dev/null || shift $#

@@ -2,6 +2,7 @@
 # Registers, scratch and occupancy of every kernel in one .hip file, as the compiler reports them (no GPU
 # needed):  scripts/kernel_resources.sh owlraytracing_amd/csrc/trueknn_team.hip [filter]
 # (the packet kernel; the hand-over walk and the tie pass: trueknn_tail.hip, the k > 64 walk: trueknn_bigk.hip)
+# (RT-DBSCAN's kernels by pass: dbscan_core.hip, dbscan_union.hip, dbscan_label.hip)
 # and, with ISA=1, the gfx950 assembly in /tmp/<name>.s (look for v_cmp_*_i32 + s_and_saveexec in loops:
 # wave-uniform values kept in VGPRs).
 set -e

@@ -49,6 +49,37 @@ def test_fingerprints_follow_the_split_of_the_team_kernels(tmp_path, monkeypatch
         assert {kernel for kernel in kernels if after[kernel] != before[kernel]} == own, name
 
 
+def test_fingerprints_follow_the_split_of_the_clustering_kernels(tmp_path, monkeypatch):
+    """RT-DBSCAN's kernels are three files by pass: an edit of one changes the library's fingerprint and that of the file's own
+    kernels, and leaves the other passes' and the packet kernel's as they were; an edit of the host side (dbscan.hip) or of the
+    shared device header changes every db_ kernel's and not the packet kernel's (on a copy of csrc/ and include/)."""
+    import shutil
+
+    pkg = tmp_path / "owlraytracing_amd"
+    shutil.copytree(os.path.join(_lib._HERE, "csrc"), pkg / "csrc", ignore=shutil.ignore_patterns("*.o", "diagobj"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    monkeypatch.setattr(_lib, "_HERE", str(pkg))
+    by_file = {"dbscan_core.hip": {"db_core_kernel", "db_core_pos_blocks_kernel", "db_flag_count_kernel", "db_next_core_blocks_kernel",
+                                   "db_core_from_labels_kernel", "db_noise_probe_kernel"},
+               "dbscan_union.hip": {"db_group_union_kernel", "db_union_kernel", "db_group_kernel", "db_group_list_kernel", "db_uniform_kernel"},
+               "dbscan_label.hip": {"db_label_kernel", "db_rows_from_slots_kernel", "db_rows_kernel", "db_flatten_kernel", "db_root_kernel",
+                                    "db_border_walk_kernel", "db_assign_kernel", "db_query_kernel", "db_segment_min_kernel"}}
+    every_db = set().union(*by_file.values())
+    kernels = (None, "team_kernel") + tuple(sorted(every_db))
+
+    def prints():
+        return {kernel: _lib.source_fingerprint(kernel) for kernel in kernels}
+
+    cases = [(name, {None} | own) for name, own in by_file.items()]
+    cases += [(name, {None} | every_db) for name in ("dbscan.hip", "db_device.h", "db_call.h")]
+    for name, changed in cases:
+        before = prints()
+        with open(pkg / "csrc" / name, "ab") as fh:
+            fh.write(b"\n")
+        after = prints()
+        assert {kernel for kernel in kernels if after[kernel] != before[kernel]} == changed, name
+
+
 def test_committed_records_name_the_sources_they_were_taken_on():
     recs = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
     assert recs, "profiles/hbm_traffic.json is empty"

@@ -184,6 +184,36 @@ def test_one_set_shortcut_and_side_stream_walks_change_nothing(monkeypatch):
     eng.close()
 
 
+@pytest.mark.gpu
+def test_measurement_knobs_change_nothing(monkeypatch):
+    """The host paths behind the knobs no other test sets, each alone: TKNN_DB_LABEL=scatter (the label kernel writes the rows
+    itself, no gather), TKNN_DB_SPLIT=1 (one union launch, no db_uniform_kernel), TKNN_DB_SHORT=0 (every settle the long way),
+    TKNN_DB_SCAN=0 (every probe goes to the subtree walk at once), TKNN_DB_CHUNK=1 (one packet per chunk dealt to an XCD).
+    Labels, core flags and the cluster count are the spec's.  20 003 points: not a multiple of four, so the kernels that take
+    four slots per thread run their tail branch, and 79 workgroups of 256 slots, the last one partial; the spec finds 17
+    clusters, 594 border points and 898 noise points."""
+    from owlraytracing_amd.trueknn import TrueKNN
+    xyz = datasets.gaussian_mixture3d(20_003, components=8, sigma=0.02, seed=5)
+    eps, min_pts = float(np.float32(0.01)), 4
+    ref = oracle.dbscan(xyz, eps, min_pts)
+    core = ref["core"].astype(bool)
+    assert ref["clusters"] > 1 and np.any((ref["labels"] >= 0) & ~core) and np.any(ref["labels"] < 0)
+    knobs = (("TKNN_DB_LABEL", "scatter"), ("TKNN_DB_SPLIT", "1"), ("TKNN_DB_SHORT", "0"), ("TKNN_DB_SCAN", "0"), ("TKNN_DB_CHUNK", "1"))
+    for k, _ in knobs:
+        monkeypatch.delenv(k, raising=False)
+    eng = TrueKNN()
+    eng.build(xyz)
+    for k, v in knobs:
+        monkeypatch.setenv(k, v)
+        got = eng.dbscan(eps, min_pts)
+        monkeypatch.delenv(k)
+        assert got["info"]["clusters"] == ref["clusters"], k
+        assert np.array_equal(got["labels"].cpu().numpy(), ref["labels"]), k
+        assert np.array_equal(got["core"].cpu().numpy().astype(bool), core), k
+        assert got["info"]["union_launches"] == (1 if k == "TKNN_DB_SPLIT" else 2), k
+    eng.close()
+
+
 def _gap_quadruples(eps, split=0.25, rel=(-1e-5, 1e-5), steps=81):
     """Pairs of two-point groups facing each other along ONE axis across a gap of split * eps * (1 + d), d swept over
     `rel` -- the seam between the two passes of the group-union kernel (first pass: nearest faces within split * eps,
