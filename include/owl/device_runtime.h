@@ -89,10 +89,13 @@ struct BlockState {
   uint32_t sbt_lo[OWL_RAYGEN_BLOCK], sbt_hi[OWL_RAYGEN_BLOCK];      // current program's data pointer
   uint32_t inst_id[OWL_RAYGEN_BLOCK], inst_index[OWL_RAYGEN_BLOCK];
   uint32_t hit_kind[OWL_RAYGEN_BLOCK], hit_attr[2][OWL_RAYGEN_BLOCK];
-  uint32_t flags[OWL_RAYGEN_BLOCK];  // bit 0: terminate requested, bit 1: a hit is recorded, bit 2: the any-hit program ignored the candidate
+  // bit 0: terminate requested, bit 1: a hit is recorded, bit 2: the any-hit program ignored the candidate,
+  // bits 8..11: the OPTIX_RAY_FLAG_* word of the trace in flight (RAY_FLAGS_SHIFT)
+  uint32_t flags[OWL_RAYGEN_BLOCK];
   uint32_t anyhit_lo[OWL_RAYGEN_BLOCK], anyhit_hi[OWL_RAYGEN_BLOCK];  // __anyhit__ program of the geometry whose intersection program runs (0: none)
 };
 static __shared__ BlockState owl_block_state;
+enum { RAY_FLAGS_SHIFT = 8, RAY_FLAGS_MASK = 0xfu };  // where optixTrace keeps its rayFlags in BlockState::flags
 
 }  // namespace device
 }  // namespace owl
@@ -185,7 +188,9 @@ __device__ __forceinline__ void optixIgnoreIntersection() { owl::device::state()
 // ray.  The geometry's any-hit program, if it has one for this ray type, then sees the candidate (t as the
 // ray's tmax, hit kind and attributes) and may reject it with optixIgnoreIntersection or accept it and end
 // the traversal with optixTerminateRay; an accepted candidate shortens the ray to t (closest-hit
-// semantics).  Returns whether the hit was accepted, like OptiX.
+// semantics).  Ray flags of the trace in flight: OPTIX_RAY_FLAG_DISABLE_ANYHIT skips the any-hit program (every
+// candidate is accepted), OPTIX_RAY_FLAG_TERMINATE_ON_FIRST_HIT ends the traversal at the first accepted candidate.
+// Returns whether the hit was accepted, like OptiX.
 __device__ __forceinline__ bool optixReportIntersection(float t, unsigned int kind, unsigned int a0 = 0,
                                                         unsigned int a1 = 0) {
   const uint32_t i = owl::device::tid();
@@ -198,7 +203,8 @@ __device__ __forceinline__ bool optixReportIntersection(float t, unsigned int ki
   s.hit_attr[0][i] = a0;
   s.hit_attr[1][i] = a1;
   const uint64_t any_hit = ((uint64_t)s.anyhit_hi[i] << 32) | s.anyhit_lo[i];
-  if (any_hit) {
+  const uint32_t ray_flags = (s.flags[i] >> owl::device::RAY_FLAGS_SHIFT) & owl::device::RAY_FLAGS_MASK;
+  if (any_hit && !(ray_flags & OPTIX_RAY_FLAG_DISABLE_ANYHIT)) {
     s.flags[i] &= ~4u;
     ((owl::device::ProgramFn)any_hit)();
     if (s.flags[i] & 4u) {  // ignored: as if nothing had been reported
@@ -210,7 +216,7 @@ __device__ __forceinline__ bool optixReportIntersection(float t, unsigned int ki
       return false;
     }
   }
-  s.flags[i] |= 2u;  // a hit is recorded
+  s.flags[i] |= (ray_flags & OPTIX_RAY_FLAG_TERMINATE_ON_FIRST_HIT) ? 3u : 2u;  // a hit is recorded (and the ray ends)
   return true;
 }
 
@@ -300,10 +306,13 @@ __device__ __forceinline__ void xfm_vector(const float m[12], const float v[3], 
 }  // namespace device
 }  // namespace owl
 
-// optixTrace: same parameter list as OptiX 7 (reference call site owl_device.h:161-173).
+// optixTrace: same parameter list as OptiX 7 (reference call site owl_device.h:161-173).  The visibility mask is
+// ignored (instances carry none).  rayFlags: DISABLE_ANYHIT and TERMINATE_ON_FIRST_HIT act in
+// optixReportIntersection, DISABLE_CLOSESTHIT here (the miss program still runs on a miss); ENFORCE_ANYHIT has
+// nothing to override, as no geometry flag of this backend disables any-hit programs.
 __device__ __forceinline__ void optixTrace(OptixTraversableHandle handle, float3 rayOrigin, float3 rayDirection,
                                            float tmin, float tmax, float rayTime, OptixVisibilityMask /*mask*/,
-                                           unsigned int /*rayFlags*/, unsigned int SBToffset,
+                                           unsigned int rayFlags, unsigned int SBToffset,
                                            unsigned int /*SBTstride*/, unsigned int missSBTIndex, unsigned int &p0,
                                            unsigned int &p1) {
   using namespace owl::device;
@@ -321,7 +330,7 @@ __device__ __forceinline__ void optixTrace(OptixTraversableHandle handle, float3
   s.time[i] = rayTime;
   s.payload[0][i] = p0;
   s.payload[1][i] = p1;
-  s.flags[i] = 0;
+  s.flags[i] = (rayFlags & RAY_FLAGS_MASK) << RAY_FLAGS_SHIFT;
   HitRecord hit = {0, 0, 0, 0};
   const AccelHeader *hdr = (const AccelHeader *)handle;
   if (hdr) {
@@ -362,7 +371,7 @@ __device__ __forceinline__ void optixTrace(OptixTraversableHandle handle, float3
   if (hit.geom) {
     const GeomRecord *rec = (const GeomRecord *)hit.geom;
     const uint64_t fn = rec->closest_hit[SBToffset < OWL_MAX_RAY_TYPES ? SBToffset : 0];
-    if (fn) {
+    if (fn && !(rayFlags & OPTIX_RAY_FLAG_DISABLE_CLOSESTHIT)) {
       s.prim[i] = hit.prim;
       s.inst_id[i] = hit.inst_id;
       s.inst_index[i] = hit.inst_index;

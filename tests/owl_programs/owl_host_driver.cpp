@@ -13,6 +13,9 @@
 //   owl_host_driver api    <api_programs.hsaco> <out.bin>
 //       tests/owl_programs/api_programs.cu: OWL_BUFFER / OWL_BUFFER_SIZE / OWL_DEVICE variables, host-pinned output,
 //       owlBufferUpload / Resize / Destroy, any-hit, instance transforms and ids, two OWLParams launched asynchronously.
+//   owl_host_driver rays   <ray_programs.hsaco> <scene.bin> <rays.bin> <out.bin> <pass,pass,...> <n1d> <dx> <dy>
+//       tests/owl_programs/ray_programs.cu: real rays (any direction, tmin / tmax, two ray types, ray flags) against boxes
+//       and spheres under transformed instances; one launch per named pass, every pass's per-ray records in one file.
 //   owl_host_driver errors <module.hsaco>
 //       the error conventions of SURVEY.md section 8(b); prints one PASS/FAIL line per check.
 #include <owl/owl.h>
@@ -397,6 +400,266 @@ static int run_api(int argc, char **argv) {
   return 0;
 }
 
+// tests/owl_programs/ray_programs.cu layouts
+struct PrimsGeomRec {
+  Point3 *centers;
+  float *half;
+  int tag;
+  int anyhit_mode;
+};
+struct RayRecHost {
+  float org[3], dir[3];
+  float tmin, tmax;
+  unsigned type, flags;
+};
+struct HitRecHost {
+  int prim;
+  unsigned inst_id;
+  int inst_index, kind;
+  unsigned attr0;
+  float t;
+  int geom, status, far_prim;
+  unsigned far_inst_id;
+  int far_geom;
+  float far_t;
+};
+struct RayParamsRec {
+  RayRecHost *rays;
+  HitRecHost *out;
+  unsigned *calls;
+  unsigned *idsum;
+  int n_inst;
+  int count_mode;
+};
+struct RaysRayGenRec {
+  OptixTraversableHandle world;
+  int n;
+};
+struct RayPass {
+  const char *name;
+  int count_mode;
+  int mode_boxes, mode_spheres;  // any-hit mode of every box / sphere geometry
+  int use_types;                 // 0: every ray is of type 0, 1: the ray file's type column
+  unsigned flags;                // OPTIX_RAY_FLAG_* word of every ray
+  int shape;                     // 0: 1-D launch of n1d rays, 1: dx x dy launch over all rays of the file, 2: 1-D launch of one ray
+  int refit;                     // 1: move to the scene's second set of centres / half-widths and refit first
+};
+static const RayPass kRayPasses[] = {
+    {"count", 1, 0, 0, 0, 0u, 0, 0},
+    {"closest", 0, 0, 0, 0, 0u, 0, 0},
+    {"ignore_odd", 0, 1, 1, 0, 0u, 0, 0},
+    {"ignore_near", 0, 1, 2, 0, 0u, 0, 0},
+    {"terminate", 0, 3, 3, 0, 0u, 0, 0},
+    {"types", 0, 0, 0, 1, 0u, 0, 0},
+    {"flag_disable_anyhit", 0, 1, 1, 0, 1u, 0, 0},
+    {"flag_enforce_anyhit", 0, 1, 1, 0, 2u, 0, 0},
+    {"flag_terminate_first", 0, 1, 1, 0, 4u, 0, 0},
+    {"flag_disable_closesthit", 0, 1, 1, 0, 8u, 0, 0},
+    {"flag_disable_anyhit_terminate_first", 0, 1, 1, 0, 5u, 0, 0},
+    {"launch2d", 0, 0, 0, 0, 0u, 1, 0},
+    {"launch_one", 0, 0, 0, 0, 0u, 2, 0},
+    {"refit", 0, 0, 0, 0, 0u, 0, 1},
+};
+
+// Scene file (int32 / float32, little endian), written by tests/ray_spec.py:
+//   magic, n_groups, n_instances, has_second_set
+//   per group: n_geoms; per geometry: type (0 boxes, 1 spheres), n, centers[3n], half[n] (+ centers[3n], half[n] of the second set)
+//   per instance: child group, id, how (bit 0: transform handed to owlInstanceGroupCreate, else set afterwards with
+//                 owlInstanceGroupSetTransform; bit 1: child set afterwards with owlInstanceGroupSetChild), 12 floats in OWL format
+// Ray file: n, then n RayRec.  Output: for every pass HitRec[n], calls[n * n_instances], idsum[n * n_instances].
+static int run_rays(int argc, char **argv) {
+  if (argc < 10) return 2;
+  std::vector<char> code = read_file(argv[2]);
+  std::vector<char> scene = read_file(argv[3]);
+  std::vector<char> rayfile = read_file(argv[4]);
+  const int n1d = std::atoi(argv[7]), dx2 = std::atoi(argv[8]), dy2 = std::atoi(argv[9]);
+  const char *cur = scene.data();
+  auto take = [&](size_t bytes) {
+    const char *p = cur;
+    cur += bytes;
+    if (cur > scene.data() + scene.size() - 1) {
+      std::fprintf(stderr, "scene file too short\n");
+      std::exit(2);
+    }
+    return p;
+  };
+  auto take_i = [&] { int32_t v; std::memcpy(&v, take(4), 4); return v; };
+  if (take_i() != 0x52415953) return 2;
+  const int n_groups = take_i(), n_inst = take_i(), has_second = take_i();
+  int n_rays;
+  std::memcpy(&n_rays, rayfile.data(), 4);
+  if (rayfile.size() - 1 < 4 + (size_t)n_rays * sizeof(RayRecHost)) return 2;
+  std::vector<RayRecHost> rays(n_rays);
+  std::memcpy(rays.data(), rayfile.data() + 4, (size_t)n_rays * sizeof(RayRecHost));
+  if (n1d > n_rays || (long long)dx2 * dy2 < n_rays) return 2;
+
+  OWLContext ctx = owlContextCreate(nullptr, 1);
+  owlContextSetRayTypeCount(ctx, 2);
+  OWLModule mod = owlModuleCreate(ctx, code.data());
+  OWLVarDecl geomVars[] = {{"centers", OWL_BUFPTR, OWL_OFFSETOF(PrimsGeomRec, centers)},
+                           {"half", OWL_BUFPTR, OWL_OFFSETOF(PrimsGeomRec, half)},
+                           {"tag", OWL_INT, OWL_OFFSETOF(PrimsGeomRec, tag)},
+                           {"anyhit_mode", OWL_INT, OWL_OFFSETOF(PrimsGeomRec, anyhit_mode)},
+                           {nullptr, OWL_INVALID_TYPE, 0}};
+  OWLGeomType types[2];
+  for (int t = 0; t < 2; t++) {
+    types[t] = owlGeomTypeCreate(ctx, OWL_GEOMETRY_USER, sizeof(PrimsGeomRec), geomVars, -1);
+    owlGeomTypeSetIntersectProg(types[t], 0, mod, t ? "Spheres" : "Boxes");
+    owlGeomTypeSetClosestHit(types[t], 0, mod, "Prims");
+    owlGeomTypeSetAnyHit(types[t], 0, mod, "Prims");
+    owlGeomTypeSetBoundsProg(types[t], mod, "Prims");
+  }
+  owlGeomTypeSetIntersectProg(types[1], 1, mod, "SpheresFar");  // ray type 1: spheres only, no closest-hit, no any-hit
+  OWLVarDecl noVars[] = {{nullptr, OWL_INVALID_TYPE, 0}};
+  owlMissProgCreate(ctx, mod, "miss0", 0, noVars, -1);  // the i-th created miss program serves ray type i
+  owlMissProgCreate(ctx, mod, "miss1", 0, noVars, -1);
+  owlBuildPrograms(ctx);
+
+  struct GeomState {
+    OWLGeom geom;
+    OWLBuffer centers, half;
+    int type;
+    size_t n;
+    const float *centers2, *half2;
+  };
+  std::vector<GeomState> geoms;
+  std::vector<OWLGroup> groups;
+  for (int g = 0; g < n_groups; g++) {
+    const int n_geoms = take_i();
+    std::vector<OWLGeom> members;
+    for (int k = 0; k < n_geoms; k++) {
+      GeomState st;
+      st.type = take_i();
+      st.n = (size_t)take_i();
+      const float *centers = (const float *)take(st.n * 12), *half = (const float *)take(st.n * 4);
+      st.centers2 = has_second ? (const float *)take(st.n * 12) : nullptr;
+      st.half2 = has_second ? (const float *)take(st.n * 4) : nullptr;
+      st.centers = owlDeviceBufferCreate(ctx, OWL_USER_TYPE(Point3), st.n, centers);
+      st.half = owlDeviceBufferCreate(ctx, OWL_FLOAT, st.n, half);
+      st.geom = owlGeomCreate(ctx, types[st.type]);
+      owlGeomSetPrimCount(st.geom, st.n);
+      owlGeomSetBuffer(st.geom, "centers", st.centers);
+      owlGeomSetBuffer(st.geom, "half", st.half);
+      owlGeomSet1i(st.geom, "tag", (int)geoms.size());
+      owlGeomSet1i(st.geom, "anyhit_mode", 0);
+      members.push_back(st.geom);
+      geoms.push_back(st);
+    }
+    OWLGroup grp = owlUserGeomGroupCreate(ctx, members.size(), members.data());
+    owlGroupBuildAccel(grp);
+    groups.push_back(grp);
+  }
+  std::vector<OWLGroup> children(n_inst);
+  std::vector<uint32_t> ids(n_inst);
+  std::vector<float> at_create(12 * (size_t)n_inst);
+  std::vector<int> child_of(n_inst), how(n_inst);
+  std::vector<const float *> xfm(n_inst);
+  static const float ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  for (int i = 0; i < n_inst; i++) {
+    child_of[i] = take_i();
+    ids[i] = (uint32_t)take_i();
+    how[i] = take_i();
+    xfm[i] = (const float *)take(48);
+    if (child_of[i] < 0 || child_of[i] >= n_groups) return 2;
+    children[i] = (how[i] & 2) ? nullptr : groups[child_of[i]];
+    std::memcpy(&at_create[12 * (size_t)i], (how[i] & 1) ? xfm[i] : ident, 48);
+  }
+  OWLGroup world = owlInstanceGroupCreate(ctx, n_inst, children.data(), ids.data(), at_create.data(), OWL_MATRIX_FORMAT_OWL);
+  for (int i = 0; i < n_inst; i++) {
+    if (!(how[i] & 1)) owlInstanceGroupSetTransform(world, i, xfm[i], OWL_MATRIX_FORMAT_OWL);
+    if (how[i] & 2) owlInstanceGroupSetChild(world, i, groups[child_of[i]]);
+  }
+  owlGroupBuildAccel(world);
+
+  const size_t n_slots = (size_t)n_rays * n_inst;
+  OWLBuffer ray_buf = owlDeviceBufferCreate(ctx, OWL_USER_TYPE(RayRecHost), n_rays, nullptr);
+  OWLBuffer out_buf = owlDeviceBufferCreate(ctx, OWL_USER_TYPE(HitRecHost), n_rays, nullptr);
+  OWLBuffer calls = owlDeviceBufferCreate(ctx, OWL_UINT, n_slots, nullptr), idsum = owlDeviceBufferCreate(ctx, OWL_UINT, n_slots, nullptr);
+  OWLVarDecl lpVars[] = {{"rays", OWL_BUFPTR, OWL_OFFSETOF(RayParamsRec, rays)},
+                         {"out", OWL_BUFPTR, OWL_OFFSETOF(RayParamsRec, out)},
+                         {"calls", OWL_BUFPTR, OWL_OFFSETOF(RayParamsRec, calls)},
+                         {"idsum", OWL_BUFPTR, OWL_OFFSETOF(RayParamsRec, idsum)},
+                         {"n_inst", OWL_INT, OWL_OFFSETOF(RayParamsRec, n_inst)},
+                         {"count_mode", OWL_INT, OWL_OFFSETOF(RayParamsRec, count_mode)},
+                         {nullptr, OWL_INVALID_TYPE, 0}};
+  OWLParams lp = owlParamsCreate(ctx, sizeof(RayParamsRec), lpVars, -1);
+  owlParamsSetBuffer(lp, "rays", ray_buf);
+  owlParamsSetBuffer(lp, "out", out_buf);
+  owlParamsSetBuffer(lp, "calls", calls);
+  owlParamsSetBuffer(lp, "idsum", idsum);
+  owlParamsSet1i(lp, "n_inst", n_inst);
+  OWLVarDecl rgVars[] = {{"world", OWL_GROUP, OWL_OFFSETOF(RaysRayGenRec, world)},
+                         {"n", OWL_INT, OWL_OFFSETOF(RaysRayGenRec, n)},
+                         {nullptr, OWL_INVALID_TYPE, 0}};
+  OWLRayGen rg1 = owlRayGenCreate(ctx, mod, "rays1d", sizeof(RaysRayGenRec), rgVars, -1);
+  OWLRayGen rg2 = owlRayGenCreate(ctx, mod, "rays2d", sizeof(RaysRayGenRec), rgVars, -1);
+  owlRayGenSetGroup(rg1, "world", world);
+  owlRayGenSetGroup(rg2, "world", world);
+  owlBuildPrograms(ctx);
+  owlBuildPipeline(ctx);
+
+  std::vector<char> out;
+  HitRecHost never;  // what a record reads if no thread wrote it
+  std::memset(&never, 0, sizeof never);
+  never.prim = never.inst_index = never.kind = never.geom = never.status = never.far_prim = never.far_geom = -9;
+  const std::vector<HitRecHost> blank(n_rays, never);
+  const std::vector<unsigned> zeros(n_slots, 0u);
+  std::string list = argv[6];
+  for (size_t at = 0; at < list.size();) {
+    size_t end = list.find(',', at);
+    if (end == std::string::npos) end = list.size();
+    const std::string name = list.substr(at, end - at);
+    at = end + 1;
+    const RayPass *pass = nullptr;
+    for (const RayPass &p : kRayPasses)
+      if (name == p.name) pass = &p;
+    if (!pass) {
+      std::fprintf(stderr, "unknown pass '%s'\n", name.c_str());
+      return 2;
+    }
+    if (pass->refit) {
+      if (!has_second) return 2;
+      for (GeomState &st : geoms) {
+        owlBufferUpload(st.centers, st.centers2, 0, st.n * 12);
+        owlBufferUpload(st.half, st.half2, 0, st.n * 4);
+      }
+      for (OWLGroup grp : groups) owlGroupRefitAccel(grp);
+      owlGroupRefitAccel(world);
+    }
+    for (GeomState &st : geoms) owlGeomSet1i(st.geom, "anyhit_mode", st.type ? pass->mode_spheres : pass->mode_boxes);
+    std::vector<RayRecHost> shot = rays;
+    for (RayRecHost &r : shot) {
+      if (!pass->use_types) r.type = 0;
+      r.flags = pass->flags;
+    }
+    owlBufferUpload(ray_buf, shot.data(), 0, shot.size() * sizeof(RayRecHost));
+    owlBufferUpload(out_buf, blank.data(), 0, blank.size() * sizeof(HitRecHost));
+    owlBufferUpload(calls, zeros.data(), 0, n_slots * 4);
+    owlBufferUpload(idsum, zeros.data(), 0, n_slots * 4);
+    owlParamsSet1i(lp, "count_mode", pass->count_mode);
+    OWLRayGen rg = pass->shape == 1 ? rg2 : rg1;
+    owlRayGenSet1i(rg, "n", pass->shape == 0 ? n1d : pass->shape == 1 ? n_rays : 1);
+    owlBuildSBT(ctx);
+    if (pass->shape == 1)
+      owlLaunch2D(rg, dx2, dy2, lp);
+    else
+      owlLaunch2D(rg, pass->shape == 0 ? n1d : 1, 1, lp);
+    const size_t base = out.size();
+    out.resize(base + (size_t)n_rays * sizeof(HitRecHost) + 2 * n_slots * 4);
+    char *p = out.data() + base;
+    CUDA_CHECK(cudaMemcpy(p, owlBufferGetPointer(out_buf, 0), (size_t)n_rays * sizeof(HitRecHost), cudaMemcpyDeviceToHost));
+    p += (size_t)n_rays * sizeof(HitRecHost);
+    CUDA_CHECK(cudaMemcpy(p, owlBufferGetPointer(calls, 0), n_slots * 4, cudaMemcpyDeviceToHost));
+    p += n_slots * 4;
+    CUDA_CHECK(cudaMemcpy(p, owlBufferGetPointer(idsum, 0), n_slots * 4, cudaMemcpyDeviceToHost));
+    std::printf("pass=%s\n", pass->name);
+  }
+  write_file(argv[5], out.data(), out.size());
+  std::printf("rays=%d instances=%d geometries=%zu\n", n_rays, n_inst, geoms.size());
+  owlContextDestroy(ctx);
+  return 0;
+}
+
 static int checks = 0, failures = 0;
 static void expect_throw(const char *what, const std::function<void()> &f, const char *needle = nullptr) {
   checks++;
@@ -484,6 +747,7 @@ int main(int argc, char **argv) {
     if (!std::strcmp(argv[1], "count")) return run_count(argc, argv);
     if (!std::strcmp(argv[1], "errors")) return run_errors(argc, argv);
     if (!std::strcmp(argv[1], "api")) return run_api(argc, argv);
+    if (!std::strcmp(argv[1], "rays")) return run_rays(argc, argv);
   } catch (const std::exception &e) {
     std::fprintf(stderr, "uncaught: %s\n", e.what());
     return 3;
