@@ -19,8 +19,14 @@ path shards naturally -- queries are independent -- with ONE real exchange step:
 
 One process per GPU (torch.distributed, backend "nccl" = RCCL on ROCm); with backend "gloo" the
 same code runs with host-staged messages (CPU tests, or several ranks sharing one GPU).
+
+``_Comm._exchange_capped`` is the fixed-capacity exchange; ``exchange_rows`` (rows on hand) and
+``exchange_fixed`` (messages selected in place) build its messages.  ``ShardedTrueKNN.solve`` loops over
+``_select``, ``_interior_solve``, ``_exchange``, ``_engine_step``, ``_anyone_left`` around one ``_SolveState``.
 """
+import contextlib
 import os
+import threading
 import time
 
 import numpy as np
@@ -56,6 +62,44 @@ def sample_positions(count, samples, device):
     return (steps * last) // max(samples - 1, 1)
 
 
+def _count_cells(count):
+    """A row count as the two header cells of a fixed-capacity message: low 24 bits, the rest (float32 holds integers
+    below 2**24 exactly).  TrueKNN.halo_select_fixed writes the same cells on the device."""
+    return float(count % (1 << 24)), float(count >> 24)
+
+
+def _count_of_cells(low, high):
+    """The row count two header cells carry (see _count_cells)."""
+    return int(low) + (int(high) << 24)
+
+
+_BIG = torch.iinfo(torch.int64).max  # "no label yet" in the label propagation of dbscan
+
+
+def _row_ids(rows):
+    """the global ids of 16-byte wire rows x y z id-bits"""
+    return rows[:, 3].contiguous().view(torch.int32)
+
+
+class _PhaseClock:
+    """Wall time per named phase of a solve / dbscan call.  Only with ``on`` (TKNN_SHARD_PROFILE, bench.py's instrumented
+    steps) does a lap synchronise the device and count; otherwise it costs a clock read."""
+
+    def __init__(self, names, device, on):
+        self.ms, self.device, self.on = dict.fromkeys(names, 0.0), device, on
+        self.restart()
+
+    def restart(self):
+        self.t = time.perf_counter()
+
+    def lap(self, name):
+        if self.on:
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
+            self.ms[name] += (time.perf_counter() - self.t) * 1e3
+        self.restart()
+
+
 class _Comm:
     """The three collectives the path needs, on device tensors (nccl) or host-staged (gloo)."""
 
@@ -82,6 +126,66 @@ class _Comm:
         dist.all_gather(out, w, group=self.group)
         return torch.stack(out).to(t.device)
 
+    def _recv_buffer(self, rows, width, dtype, device):
+        """where a message of ``rows`` rows lands: on the host when messages are staged, else on ``device``"""
+        return torch.empty((int(rows), width), dtype=dtype, device="cpu" if self.staged else device)
+
+    def _transfer(self, sends, recvs):
+        """ONE batched send/recv, waited for: ``sends`` {peer: tensor}, ``recvs`` {peer: buffer to fill}."""
+        ops = []
+        for p in range(self.world):
+            if p in sends:
+                ops.append(dist.P2POp(dist.isend, self._wire(sends[p]), p, group=self.group))
+            if p in recvs:
+                ops.append(dist.P2POp(dist.irecv, recvs[p], p, group=self.group))
+        if ops:  # (no ops: nothing to wait for)
+            for req in dist.batch_isend_irecv(ops):
+                req.wait()
+
+    def _exchange_exact(self, sends, expect, width, dtype, device):
+        """Exact-size messages whose sizes both ends know: ``sends`` {peer: rows}, ``expect`` {peer: rows that arrive}; an
+        empty block does not travel.  Returns {peer: the rows received, on ``device``}."""
+        recv = {p: self._recv_buffer(c, width, dtype, device) for p, c in expect.items()}
+        self._transfer({p: r.contiguous() for p, r in sends.items() if len(r)}, {p: b for p, b in recv.items() if len(b)})
+        return {p: b.to(device) for p, b in recv.items()}
+
+    def _exchange_capped(self, tag, messages, counts_out, exact_blocks, width, dtype, device):
+        """The fixed-capacity exchange under ``tag``: ``messages[p]`` (a header row with my count + cap_out[p] rows) goes to peer
+        p, cap_in[p] + 1 rows arrive from it, and ONE host read brings the counts of what arrived -- and my own, when
+        ``counts_out`` is a device tensor and not a host list.  A pair whose rows outgrew its capacity (both ends see it: the
+        sender by its count, the receiver by the header) goes through exact-size messages once more; ``exact_blocks()`` then
+        returns my exact rows per peer.  Capacities: what both ends remember of the pair's exchanges under the tag (_remember).
+        Returns (rows received per source, rows sent per destination), None at my own rank."""
+        world, me = self.world, self.rank
+        cap_in, cap_out = self._caps[(tag, "in")], self._caps[(tag, "out")]
+        peers = [p for p in range(world) if p != me]
+        recv = {p: self._recv_buffer(cap_in[p] + 1, width, dtype, device) for p in peers}
+        self._transfer({p: messages[p] for p in peers}, recv)
+        cells = [recv[p][0, :2] for p in peers]
+        if torch.is_tensor(counts_out):  # my counts join the read: first in it, as float64 like the cells then
+            cells = [counts_out.to(cells[0].device if peers else counts_out.device).double()] + [c.double() for c in cells]
+        flat = torch.cat(cells).tolist() if cells else []  # the step's one host round trip
+        if torch.is_tensor(counts_out):
+            counts_out, flat = [int(c) for c in flat[:world]], flat[world:]
+        counts_in = [0] * world
+        for j, p in enumerate(peers):
+            counts_in[p] = _count_of_cells(flat[2 * j], flat[2 * j + 1])
+        late_in = {p: counts_in[p] for p in peers if counts_in[p] > cap_in[p]}
+        late_out = [p for p in peers if counts_out[p] > cap_out[p]]
+        got, sent = [None] * world, [None] * world
+        for p in peers:
+            if p not in late_in:
+                got[p] = recv[p][1:1 + counts_in[p]].to(device)
+            sent[p] = messages[p][1:1 + min(counts_out[p], cap_out[p])]
+        if late_in or late_out:
+            exact = exact_blocks() if late_out else None
+            for p in late_out:
+                sent[p] = exact[p]
+            for p, rows in self._exchange_exact({p: exact[p] for p in late_out}, late_in, width, dtype, device).items():
+                got[p] = rows
+        self._remember(tag, counts_in, counts_out)
+        return got, sent
+
     def exchange_rows(self, rows_per_peer, width, dtype, device, tag=None, counts_in=None):
         """all-to-all-v of 2-D row blocks: rows_per_peer[p] goes to rank p; returns the list of
         blocks received (index = source rank).
@@ -89,87 +193,38 @@ class _Comm:
         Without ``tag``: counts first (an all-gather and a host round trip), then one batched
         send/recv of exactly those rows.  With ``counts_in`` (rows per source, known to the caller):
         just that send/recv.  With ``tag`` (the per-step halo exchange): ONE batched
-        send/recv of fixed-capacity messages whose first row carries the count -- the capacity of
-        every ordered pair is what both ends remember of the pair's last exchange under that tag
-        (x 1.25 + 64 rows); the first exchange under a tag, and any pair whose rows outgrow the
-        capacity (both ends see it: the sender by its rows, the receiver by the header), go
-        through exact-size messages once more.  Float32 headers hold counts < 2**24 exactly."""
+        send/recv of fixed-capacity, zero-filled messages whose first row carries the count
+        (_exchange_capped); the first exchange under a tag goes the counts-first way and teaches
+        both ends of every pair the capacity (x 1.25 + 64 rows)."""
         world, me = self.world, self.rank
         if world == 1:  # nobody to exchange with (and no count to agree on)
             return [rows_per_peer[0]]
-        if tag is not None and dtype == torch.float32 and (tag, "in") in self._caps:
-            cap_in, cap_out = self._caps[(tag, "in")], self._caps[(tag, "out")]
-            recv = [None] * world
-            ops = []
-            msgs = []
-            for p in range(world):
-                if p == me:
-                    continue
-                rows = rows_per_peer[p]
-                m = torch.zeros((cap_out[p] + 1, width), dtype=dtype, device=rows.device)
-                m[0, 0] = float(len(rows) % (1 << 24))  # (two cells: float32 holds integers below 2**24 exactly)
-                m[0, 1] = float(len(rows) >> 24)
-                take = min(len(rows), cap_out[p])
-                if take:
-                    m[1:1 + take] = rows[:take]
-                msgs.append(m)
-                ops.append(dist.P2POp(dist.isend, self._wire(m), p, group=self.group))
-                recv[p] = torch.empty((cap_in[p] + 1, width), dtype=dtype, device="cpu" if self.staged else device)
-                ops.append(dist.P2POp(dist.irecv, recv[p], p, group=self.group))
-            if ops:
-                for req in dist.batch_isend_irecv(ops):
-                    req.wait()
-            peers = [p for p in range(world) if p != me]
-            heads = torch.stack([recv[p][0, :2] for p in peers]).tolist() if peers else []  # the step's one host round trip
-            counts_in = [0] * world
-            for p, h in zip(peers, heads):
-                counts_in[p] = int(h[0]) + (int(h[1]) << 24)
-            out = [None] * world
-            again = []  # pairs whose rows did not fit: exact-size messages, both ends know
-            for p in range(world):
-                if p == me:
-                    out[p] = rows_per_peer[p]
-                    continue
-                if counts_in[p] > cap_in[p]:
-                    again.append(("in", p))
-                else:
-                    out[p] = recv[p][1:1 + counts_in[p]].to(device)
-                if len(rows_per_peer[p]) > cap_out[p]:
-                    again.append(("out", p))
-            if again:
-                ops, late = [], {}
-                for kind, p in again:
-                    if kind == "out":
-                        ops.append(dist.P2POp(dist.isend, self._wire(rows_per_peer[p].contiguous()), p, group=self.group))
-                    else:
-                        late[p] = torch.empty((counts_in[p], width), dtype=dtype, device="cpu" if self.staged else device)
-                        ops.append(dist.P2POp(dist.irecv, late[p], p, group=self.group))
-                for req in dist.batch_isend_irecv(ops):
-                    req.wait()
-                for p, t in late.items():
-                    out[p] = t.to(device)
-            self._remember(tag, counts_in, [len(r) for r in rows_per_peer])
-            return out
+        counts_out = [len(r) for r in rows_per_peer]
+        if tag is not None and dtype == torch.float32 and self.has_caps(tag):
+            cap_out = self._caps[(tag, "out")]
+            messages = [None if p == me else self._message(rows, cap_out[p], width) for p, rows in enumerate(rows_per_peer)]
+            got, _ = self._exchange_capped(tag, messages, counts_out, lambda: rows_per_peer, width, dtype, device)
+            got[me] = rows_per_peer[me]
+            return got
         if counts_in is None:
-            counts = torch.tensor([len(r) for r in rows_per_peer], dtype=torch.int64, device=device)
-            counts_in = self.all_gather(counts)[:, self.rank].tolist()  # [src] rows coming from src
+            counts = torch.tensor(counts_out, dtype=torch.int64, device=device)
+            counts_in = self.all_gather(counts)[:, me].tolist()  # [src] rows coming from src
         # (else: the caller knows what arrives -- the answers to rows it has sent, say -- and no count travels)
-        recv = [torch.empty((int(c), width), dtype=dtype, device="cpu" if self.staged else device) for c in counts_in]
-        ops = []
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            if len(rows_per_peer[p]):
-                ops.append(dist.P2POp(dist.isend, self._wire(rows_per_peer[p].contiguous()), p, group=self.group))
-            if counts_in[p]:
-                ops.append(dist.P2POp(dist.irecv, recv[p], p, group=self.group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        recv[self.rank] = rows_per_peer[self.rank]
+        got = self._exchange_exact({p: r for p, r in enumerate(rows_per_peer) if p != me},
+                                   {p: c for p, c in enumerate(counts_in) if p != me}, width, dtype, device)
         if tag is not None and dtype == torch.float32:
-            self._remember(tag, [int(c) for c in counts_in], [len(r) for r in rows_per_peer])
-        return [r.to(device) for r in recv]
+            self._remember(tag, [int(c) for c in counts_in], counts_out)
+        return [rows_per_peer[me].to(device) if p == me else got[p] for p in range(world)]
+
+    @staticmethod
+    def _message(rows, cap, width):
+        """a zero-filled fixed-capacity message: the count of ``rows`` in its header row, then the first ``cap`` of them"""
+        m = torch.zeros((cap + 1, width), dtype=rows.dtype, device=rows.device)
+        m[0, 0], m[0, 1] = _count_cells(len(rows))
+        take = min(len(rows), cap)
+        if take:
+            m[1:1 + take] = rows[:take]
+        return m
 
     def has_caps(self, tag):
         return (tag, "in") in self._caps
@@ -182,52 +237,13 @@ class _Comm:
         messages leave as they are, the headers of what arrives and my own counts come to the host in ONE read -- the step's only
         round trip before the solve (the two-pass selection had one of its own).  A pair whose rows outgrew its capacity goes
         through exact-size messages once more; ``exact_blocks()`` then returns the per-peer rows the two-pass selection gives.
+        Rows past the count in a selected message are unspecified device memory and travel as they are.
         Returns (rows received per source, rows sent per destination)."""
-        world, me = self.world, self.rank
-        cap_in, cap_out = self._caps[(tag, "in")], self._caps[(tag, "out")]
-        recv, ops = [None] * world, []
-        for p in range(world):
-            if p == me:
-                continue
-            m = messages[starts[p]: starts[p] + cap_out[p] + 1]
-            ops.append(dist.P2POp(dist.isend, self._wire(m), p, group=self.group))
-            recv[p] = torch.empty((cap_in[p] + 1, 4), dtype=torch.float32, device="cpu" if self.staged else device)
-            ops.append(dist.P2POp(dist.irecv, recv[p], p, group=self.group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        peers = [p for p in range(world) if p != me]
-        mine = counts_dev.to(recv[peers[0]].device if peers else counts_dev.device).double()
-        heads = [recv[p][0, :2].double() for p in peers]
-        flat = torch.cat([mine] + heads).tolist()  # the one host round trip: my counts, then (low, high) per source
-        counts_out = [int(c) for c in flat[:world]]
-        counts_in = [0] * world
-        for j, p in enumerate(peers):
-            counts_in[p] = int(flat[world + 2 * j]) + (int(flat[world + 2 * j + 1]) << 24)
-        sent = [messages[starts[p] + 1: starts[p] + 1 + min(counts_out[p], cap_out[p])] for p in range(world)]
-        out = [None] * world
-        again_in = [p for p in peers if counts_in[p] > cap_in[p]]
-        again_out = [p for p in peers if counts_out[p] > cap_out[p]]
-        for p in range(world):
-            if p == me:
-                out[p] = messages[:0]
-            elif p not in again_in:
-                out[p] = recv[p][1:1 + counts_in[p]].to(device)
-        if again_in or again_out:
-            exact = exact_blocks() if again_out else None
-            ops, late = [], {}
-            for p in again_out:
-                sent[p] = exact[p]
-                ops.append(dist.P2POp(dist.isend, self._wire(exact[p].contiguous()), p, group=self.group))
-            for p in again_in:
-                late[p] = torch.empty((counts_in[p], 4), dtype=torch.float32, device="cpu" if self.staged else device)
-                ops.append(dist.P2POp(dist.irecv, late[p], p, group=self.group))
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-            for p, t in late.items():
-                out[p] = t.to(device)
-        self._remember(tag, counts_in, counts_out)
-        return out, sent
+        cap_out = self._caps[(tag, "out")]
+        per_peer = [messages[s: s + cap_out[p] + 1] for p, s in enumerate(starts)]
+        got, sent = self._exchange_capped(tag, per_peer, counts_dev, exact_blocks, 4, torch.float32, device)
+        got[self.rank] = sent[self.rank] = messages[:0]
+        return got, sent
 
     def _remember(self, tag, counts_in, counts_out):
         """capacities of the next exchange under ``tag``: both ends of a pair derive the same number from the same count"""
@@ -237,6 +253,23 @@ class _Comm:
         self._caps[(tag, "out")] = [max(grow(c), old_out[p] if old_out else 0) for p, c in enumerate(counts_out)]
 
 
+class _SolveState:
+    """What one ShardedTrueKNN.solve carries from step to step."""
+
+    def __init__(self, world):
+        self.halo = None            # every foreign row received so far (the halo tree's points)
+        self.held = [None] * world  # ids of my rows each peer holds already
+        self.round_halo = []        # rows received per exchange; its length is the number of exchanges
+        self.one_pass = False       # the first exchange selected its rows straight into fixed-capacity messages
+        self.overlapped = False     # the interior queries were solved beside the first exchange
+        self.res = None             # the last engine result; None: the first step is still to come
+
+    def travelled(self, peer, rows):
+        """``rows`` of mine went to ``peer``: it holds them from now on, and a straggler round sends only what it lacks"""
+        if len(rows):
+            self.held[peer] = _row_ids(rows) if self.held[peer] is None else torch.cat([self.held[peer], _row_ids(rows)])
+
+
 class ShardedTrueKNN:
     """TrueKNN over a point set sharded across the ranks of a process group.
 
@@ -244,6 +277,9 @@ class ShardedTrueKNN:
     interface (build / set_halo / solve); the default is that class, i.e. the HIP engine.  Tests
     inject a checker-backed stand-in to run the partition / halo / validity logic on CPU ranks.
     """
+
+    CELL_LEVEL = 2   # a tile is described by the boxes of its Morton cells at this level ...
+    MAX_CELLS = 64   # ... of which there are at most 8 ** CELL_LEVEL
 
     def __init__(self, device, kernel=_lib.KERNEL_AUTO, engine_factory=None, group=None, halo_levels=None):
         self.device = torch.device(device)
@@ -349,10 +385,13 @@ class ShardedTrueKNN:
         self.tile_boxes = comm.all_gather(boxes).cpu()  # (W, MAX_CELLS, 6); empty slots are inverted boxes
         self.engine.build(self.points, self.ids)
 
-    CELL_LEVEL = 2
-    MAX_CELLS = 64
-
     # ---- per-solve exchange ---------------------------------------------------------------------
+    @staticmethod
+    def _reach(radius):
+        """How far beyond a peer's cell box a point of mine can lie and still be a box candidate of a query at ``radius``:
+        the radius and a relative 1e-5 (_widen adds an ulp-of-coordinate margin and rounds outward)."""
+        return float(radius) * (1.0 + 1e-5) + 1e-30
+
     def _halo_blocks(self, radius):
         """For each peer, the rows of my tile within `radius` (L-inf) of any of the peer's cell boxes:
         exactly the foreign points that can be box candidates of the peer's queries.
@@ -362,30 +401,21 @@ class ShardedTrueKNN:
         boxes widened in float64 (radius, a relative 1e-5, an ulp-of-coordinate margin) and rounded
         OUTWARD, so the selection can only err on the side of sending a point too many."""
         comm, dev = self.comm, self.device
-        reach = float(radius) * (1.0 + 1e-5) + 1e-30
+        rows = self._rows
         if hasattr(self.engine, "halo_select"):
             # the engine's kernels do the selection on its own Morton-sorted points: widened peer boxes
             # in, per-peer contiguous wire rows out (tknnHaloSelect)
-            boxes, owner = self._peer_boxes(reach)
+            boxes, owner = self._peer_boxes(self._reach(radius))
             if boxes is None:
-                return [self._rows[:0] for _ in range(comm.world)]
+                return [rows[:0] for _ in range(comm.world)]
             rows, counts = self.engine.halo_select(boxes, owner, comm.world)
             self._boundary_marked = True  # the count pass has marked my points inside a peer's box: my boundary queries
             return list(torch.split(rows, counts))
-        rows = self._rows
-        blocks = []
+        blocks = [rows[:0] for _ in range(comm.world)]
         mine = self.cell_boxes  # (C,6) float64, host
-        for peer in range(comm.world):
-            if peer == comm.rank:
-                blocks.append(rows[:0])
-                continue
-            pb = self.tile_boxes[peer]
-            pb = pb[pb[:, 0] <= pb[:, 3]]  # drop empty slots
-            mag = pb.abs().max(dim=1, keepdim=True).values
-            lo64, hi64 = pb[:, :3] - reach - 1e-6 * mag, pb[:, 3:] + reach + 1e-6 * mag
+        for peer, lo64, hi64, lo, hi in self._peer_cells(self._reach(radius)):
             # which of my cells meet any widened peer box (host)
             meet = ((mine[:, None, :3] <= hi64[None]) & (mine[:, None, 3:] >= lo64[None])).all(dim=2)  # (C,P)
-            lo, hi = self._widen(pb, reach)
             lo, hi = lo.to(dev), hi.to(dev)
             picked = []
             for c, (s0, s1) in enumerate(self.cell_slices):
@@ -396,37 +426,39 @@ class ShardedTrueKNN:
                 blo, bhi = lo[which.to(dev)], hi[which.to(dev)]
                 inside = ((seg[:, None, :] >= blo[None]) & (seg[:, None, :] <= bhi[None])).all(dim=2).any(dim=1)
                 picked.append(rows[s0:s1][inside])
-            blocks.append(torch.cat(picked, dim=0) if picked else rows[:0])
+            if picked:
+                blocks[peer] = torch.cat(picked, dim=0)
         return blocks
+
+    def _peer_cells(self, reach):
+        """(peer, lo64, hi64, lo, hi) for every peer that has cells: its cell boxes widened by ``reach`` in float64, and the
+        float32 boxes that contain those (_widen)"""
+        for peer in range(self.comm.world):
+            pb = self.tile_boxes[peer]
+            pb = pb[pb[:, 0] <= pb[:, 3]]  # drop empty slots
+            if peer != self.comm.rank and len(pb):
+                yield (peer,) + self._widen(pb, reach)
 
     def _peer_boxes(self, reach):
         """(boxes (m,6) float32, owner (m,) int32) of every peer's Morton cells widened by ``reach``, or (None, None)"""
-        comm = self.comm
         boxes, owner = [], []
-        for peer in range(comm.world):
-            if peer == comm.rank:
-                continue
-            pb = self.tile_boxes[peer]
-            pb = pb[pb[:, 0] <= pb[:, 3]]  # drop empty slots
-            if len(pb) == 0:
-                continue
-            lo, hi = self._widen(pb, reach)
+        for peer, _, _, lo, hi in self._peer_cells(reach):
             boxes.append(torch.cat([lo, hi], dim=1))
-            owner.append(torch.full((len(pb),), peer, dtype=torch.int32))
+            owner.append(torch.full((len(lo),), peer, dtype=torch.int32))
         if not boxes:
             return None, None
         return torch.cat(boxes), torch.cat(owner)
 
     @staticmethod
     def _widen(pb, reach):
-        """float32 boxes containing pb (float64 cell boxes) widened by `reach`, a relative 1e-6 and
-        rounded OUTWARD: the selection can only err on the side of sending a point too many."""
+        """pb (float64 cell boxes) widened by `reach` and a relative 1e-6: (lo64, hi64, lo, hi), the last two float32 boxes
+        containing the first two, rounded OUTWARD: the selection can only err on the side of sending a point too many."""
         mag = pb.abs().max(dim=1, keepdim=True).values
         lo64, hi64 = pb[:, :3] - reach - 1e-6 * mag, pb[:, 3:] + reach + 1e-6 * mag
         lo, hi = lo64.float(), hi64.float()
         lo = torch.where(lo.double() > lo64, torch.nextafter(lo, torch.full_like(lo, -float("inf"))), lo)
         hi = torch.where(hi.double() < hi64, torch.nextafter(hi, torch.full_like(hi, float("inf"))), hi)
-        return lo, hi
+        return lo64, hi64, lo, hi
 
     @staticmethod
     def _merge_infos(a, b, levels_counted_twice):
@@ -444,169 +476,168 @@ class ShardedTrueKNN:
                                         / max(merged["dominant_kernel_launches"], 1))
         return merged
 
-    def solve(self, k, start_radius, max_rounds=64, want_fb=False):
-        comm, dev = self.comm, self.device
-        r0 = np.float32(start_radius)
-        level_cap = self.halo_levels
-        if level_cap is None:
-            ext = [float(e) for e in self.extent if float(e) > 0]
-            measure = float(np.prod(ext)) if ext else 0.0
-            level_cap = 0
-            if measure > 0:
-                density = self.n_total / measure
-                while level_cap < 6 and density * (2.0 * float(r0) * 2 ** level_cap) ** len(ext) < 32.0 * k:
-                    level_cap += 1
-        exchanges, halo_points = 0, 0
-        phase = {"select": 0.0, "exchange": 0.0, "halo_build": 0.0, "solve": 0.0, "reduce": 0.0}
-        profile = self.profile
+    def _first_halo_level(self, k, r0):
+        """The radius level the first halo covers: ``halo_levels``, or the level (<= 6) the density of the set suggests."""
+        if self.halo_levels is not None:
+            return self.halo_levels
+        ext = [float(e) for e in self.extent if float(e) > 0]
+        measure = float(np.prod(ext)) if ext else 0.0
+        level = 0
+        if measure > 0:
+            density = self.n_total / measure
+            while level < 6 and density * (2.0 * float(r0) * 2 ** level) ** len(ext) < 32.0 * k:
+                level += 1
+        return level
 
-        def lap(name, t0):
-            if profile:
-                if dev.type == "cuda":
-                    torch.cuda.synchronize(dev)
-                phase[name] += (time.perf_counter() - t0) * 1e3
-            return time.perf_counter()
+    @staticmethod
+    def _halo_radius(r0, level):
+        """The engine's radius at ``level``: r0 doubled ``level`` times in float32, bit for bit what its rounds use."""
+        radius = np.float32(r0)
+        for _ in range(level):
+            radius = np.float32(radius * np.float32(2))
+        return radius
 
-        first = True
-        one_pass = False  # the first exchange of this solve selected its rows straight into fixed-capacity messages
-        overlapped = False
-        halo = None                         # every foreign row received so far (the halo tree's points)
-        sent = [None] * comm.world          # ids of my rows each peer holds already
-        round_halo = []                     # rows received per exchange
-        res = None
-        while True:
-            halo_radius = np.float32(r0)
-            for _ in range(level_cap):
-                halo_radius = np.float32(halo_radius * np.float32(2))
-            t = time.perf_counter()
-            self._boundary_marked = False
-            tag = ("halo", level_cap, first)
-            # The step's usual form (round 4): both ends of every pair remember how much travelled under this tag, so the rows are
-            # selected straight into messages of that capacity (one pass, no count pass, no host round trip of its own) and the
-            # exchange's one read of the headers also brings my own counts.  The first exchange under a tag, the straggler rounds
-            # (shells) and engines without the one-pass selection go the two-pass way below.
-            fixed = (first and comm.world > 1 and comm.has_caps(tag) and hasattr(self.engine, "halo_select_fixed")
-                     and not (self.overlap and getattr(self.engine, "supports_phases", False)))
-            fixed_sel = None
-            if fixed:
-                reach = float(halo_radius) * (1.0 + 1e-5) + 1e-30
-                boxes, owner = self._peer_boxes(reach)
-                if boxes is None:
-                    fixed = False
-                else:
-                    fixed_sel = self.engine.halo_select_fixed(boxes, owner, comm.world, [0 if p == comm.rank else c for p, c in enumerate(comm.caps_out(tag))])
-                    self._boundary_marked = True
-                    one_pass = True
-            blocks = self._halo_blocks(halo_radius) if not fixed else None
-            if not first:
-                # a straggler round: the peers hold what the smaller radius selected -- only the SHELL between the two
-                # radii travels ("only the incremental shell (r_{t-1}, r_t] need be sent after round 1")
-                for p in range(comm.world):
-                    if p != comm.rank and len(blocks[p]) and sent[p] is not None and len(sent[p]):
-                        ids_p = blocks[p][:, 3].contiguous().view(torch.int32)
-                        blocks[p] = blocks[p][~torch.isin(ids_p, sent[p])]
-            if not fixed:
-                for p in range(comm.world):
-                    if p != comm.rank and len(blocks[p]):
-                        ids_p = blocks[p][:, 3].contiguous().view(torch.int32)
-                        sent[p] = ids_p if sent[p] is None else torch.cat([sent[p], ids_p])
-            t = lap("select", t)
-            two_phases = (first and self.overlap and self._boundary_marked and getattr(self.engine, "supports_phases", False)
-                          and dev.type == "cuda" and k <= 64 and self.kernel in (_lib.KERNEL_AUTO, _lib.KERNEL_TEAM))
-            solve_kw = dict(kernel=self.kernel, max_rounds=level_cap + 1, want_fb=want_fb, want_levels=True, allow_unfinished=True)
-            interior = {}
-            worker = None
-            overlapped = overlapped or two_phases
-            if two_phases:
-                # interior queries: own tree only, on a stream and a host thread of their own (the call returns when
-                # its kernels are done, so it cannot be issued from the thread that drives the exchange)
-                import threading
+    def _select(self, st, tag, halo_radius):
+        """My rows for every peer at ``halo_radius``: (None, fixed selection) in a step's usual form (round 4) -- both ends of
+        every pair remember how much travelled under ``tag``, so the rows are selected straight into messages of that capacity,
+        one pass and no host round trip of its own --, else (per-peer blocks, None): the first exchange under a tag, engines
+        without the one-pass selection, and the straggler rounds, whose blocks hold only the SHELL a peer does not hold yet
+        (SURVEY 8e).  ``_boundary_marked`` says afterwards whether the engine has marked my boundary queries."""
+        comm, first = self.comm, st.res is None
+        self._boundary_marked = False
+        if (first and comm.world > 1 and comm.has_caps(tag) and hasattr(self.engine, "halo_select_fixed")
+                and not (self.overlap and getattr(self.engine, "supports_phases", False))):
+            boxes, owner = self._peer_boxes(self._reach(halo_radius))
+            if boxes is not None:
+                caps = [0 if p == comm.rank else c for p, c in enumerate(comm.caps_out(tag))]
+                selection = self.engine.halo_select_fixed(boxes, owner, comm.world, caps)
+                self._boundary_marked = st.one_pass = True
+                return None, selection
+        blocks = self._halo_blocks(halo_radius)
+        for p in range(comm.world):
+            if p == comm.rank or not len(blocks[p]):
+                continue
+            if not first and st.held[p] is not None:
+                blocks[p] = blocks[p][~torch.isin(_row_ids(blocks[p]), st.held[p])]
+            st.travelled(p, blocks[p])
+        return blocks, None
 
-                n_own = len(self.points)
-                if self._out.get("idx") is None or tuple(self._out["idx"].shape) != (n_own, k):
-                    self._out = {"idx": torch.empty((n_own, k), dtype=torch.int32, device=dev),
-                                 "dist": torch.empty((n_own, k), dtype=torch.float32, device=dev),
-                                 "intersections": torch.empty((n_own,), dtype=torch.int64, device=dev),
-                                 "levels": torch.empty((n_own,), dtype=torch.int32, device=dev)}
-                if want_fb and self._out.get("fb") is None:
-                    self._out["fb"] = torch.empty((n_own * k * 24,), dtype=torch.uint8, device=dev)
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                self.engine.set_halo(None, None)
+    @contextlib.contextmanager
+    def _interior_solve(self, st, k, r0, want_fb, solve_kw):
+        """Around the first exchange, with TKNN_SHARD_OVERLAP=1: the interior queries (own tree only) are solved on a stream
+        and a host thread of their own -- the engine call returns when its kernels are done, so the thread that drives the
+        exchange cannot issue it.  Yields None without an interior solve, else a dict that holds ``res`` and ``ms`` once the
+        block is left.  The worker uses self.engine: it is joined whatever the block raises, and what it raised
+        itself is raised again on the driving thread."""
+        dev = self.device
+        if not (st.res is None and self.overlap and self._boundary_marked and getattr(self.engine, "supports_phases", False)
+                and dev.type == "cuda" and k <= 64 and self.kernel in (_lib.KERNEL_AUTO, _lib.KERNEL_TEAM)):
+            yield None
+            return
+        st.overlapped = True
+        n_own = len(self.points)
+        if self._out.get("idx") is None or tuple(self._out["idx"].shape) != (n_own, k):
+            self._out = {"idx": torch.empty((n_own, k), dtype=torch.int32, device=dev),
+                         "dist": torch.empty((n_own, k), dtype=torch.float32, device=dev),
+                         "intersections": torch.empty((n_own,), dtype=torch.int64, device=dev),
+                         "levels": torch.empty((n_own,), dtype=torch.int32, device=dev)}
+        if want_fb and self._out.get("fb") is None:
+            self._out["fb"] = torch.empty((n_own * k * 24,), dtype=torch.uint8, device=dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        self.engine.set_halo(None, None)
+        interior = {}
 
-                def run_interior():
-                    try:
-                        interior["res"] = self.engine.solve(k, float(r0), out=self._out, phase=1, stream=side, **solve_kw)
-                    except BaseException as e:  # re-raised on the driving thread
-                        interior["error"] = e
-
-                worker = threading.Thread(target=run_interior, name="tknn-interior")
-                t_int = time.perf_counter()
-                worker.start()
+        def run_interior():
             try:
-                # (tagged: fixed-capacity messages with the count in their first row -- one exchange, one host round
-                # trip -- once a first exchange at this radius level has told both ends of every pair how much travels)
-                if fixed:
-                    got, went = comm.exchange_fixed(fixed_sel[0], fixed_sel[1], fixed_sel[2], tag, dev, lambda: self._halo_blocks(halo_radius))
-                    for p in range(comm.world):  # what each peer holds of mine now (the straggler rounds send shells)
-                        if p != comm.rank and len(went[p]):
-                            sent[p] = went[p][:, 3].contiguous().view(torch.int32)
-                else:
-                    got = comm.exchange_rows(blocks, 4, torch.float32, dev, tag=tag)
-                got[comm.rank] = got[comm.rank][:0]
-                new_rows = torch.cat(got, dim=0)
-                t = lap("exchange", t)
-                exchanges += 1
-                round_halo.append(int(len(new_rows)))
-                halo = new_rows if halo is None else torch.cat([halo, new_rows], dim=0)
-                halo_points = len(halo)
-                self.engine.set_halo(halo[:, :3].contiguous(), halo[:, 3].contiguous().view(torch.int32))
-                t = lap("halo_build", t)
-            finally:
-                # the interior solve uses self.engine on its own stream: never unwind past it
-                if worker is not None:
-                    worker.join()
-            if worker is not None:
-                if "error" in interior:
-                    raise interior["error"]
-                phase["interior_solve_overlapped"] = phase.get("interior_solve_overlapped", 0.0) + (time.perf_counter() - t_int) * 1e3
-                t = time.perf_counter()
-                # boundary queries: own + halo tree, rows and levels of the interior queries stay
-                res = self.engine.solve(k, float(r0), out={kk: v for kk, v in interior["res"].items() if kk != "info"}, phase=2, **solve_kw)
-                res["info"] = self._merge_infos(interior["res"]["info"], res["info"], 0)
-            elif first:
-                # levels 0..level_cap are exact with this halo; stop there and see who is left
-                res = self.engine.solve(k, float(r0), **solve_kw)
-            else:
-                # only the queries the rounds so far left unfinished, over own + widened halo tree; every other row stays
-                before = res["info"]
-                res = self.engine.solve(k, float(r0), out={kk: v for kk, v in res.items() if kk != "info"}, phase=3, **solve_kw)
-                res["info"] = self._merge_infos(before, res["info"], int(before["unfinished"]) * level_cap)
-            t = lap("solve", t)
-            first = False
-            # ONE all-reduce per solve step: is anybody left (a maximum says so as well as a sum), and the rounds the ranks took
-            left = torch.tensor([int(res["info"]["unfinished"]), int(res["info"]["rounds"])], dtype=torch.int64, device=dev)
-            comm.all_reduce(left, dist.ReduceOp.MAX)
-            left_host = left.tolist()
-            done = int(left_host[0]) == 0
-            rounds_all = int(left_host[1])
-            t = lap("reduce", t)
+                interior["res"] = self.engine.solve(k, float(r0), out=self._out, phase=1, stream=side, **solve_kw)
+            except BaseException as e:  # re-raised on the driving thread
+                interior["error"] = e
+
+        worker = threading.Thread(target=run_interior, name="tknn-interior")
+        t0 = time.perf_counter()
+        worker.start()
+        try:
+            yield interior
+        finally:
+            worker.join()
+        if "error" in interior:
+            raise interior["error"]
+        interior["ms"] = (time.perf_counter() - t0) * 1e3
+
+    def _exchange(self, st, tag, blocks, selection, halo_radius, clock):
+        """One point-to-point exchange of what _select chose (tagged: one host round trip once a first exchange at this
+        radius level has taught the capacities), then the halo tree over every foreign row received so far."""
+        comm, dev = self.comm, self.device
+        if selection is not None:
+            got, went = comm.exchange_fixed(*selection, tag, dev, lambda: self._halo_blocks(halo_radius))
+            for p in range(comm.world):
+                if p != comm.rank:
+                    st.travelled(p, went[p])
+        else:
+            got = comm.exchange_rows(blocks, 4, torch.float32, dev, tag=tag)
+        got[comm.rank] = got[comm.rank][:0]
+        new_rows = torch.cat(got, dim=0)
+        clock.lap("exchange")
+        st.round_halo.append(int(len(new_rows)))
+        st.halo = new_rows if st.halo is None else torch.cat([st.halo, new_rows], dim=0)
+        self.engine.set_halo(st.halo[:, :3].contiguous(), _row_ids(st.halo))
+        clock.lap("halo_build")
+
+    def _engine_step(self, st, k, r0, level, interior, solve_kw):
+        """The engine call of a step; ``st.res`` then holds every row and the info of the whole solve so far.  After an
+        interior solve: the boundary queries; a first step: every query (levels 0..``level`` are exact with this halo); a
+        straggler round: only the queries left unfinished, over own + widened halo tree.  Every other row stays."""
+        rows_of = lambda res: {kk: v for kk, v in res.items() if kk != "info"}  # noqa: E731
+        if interior is not None:
+            res = self.engine.solve(k, float(r0), out=rows_of(interior["res"]), phase=2, **solve_kw)
+            res["info"] = self._merge_infos(interior["res"]["info"], res["info"], 0)
+        elif st.res is None:
+            res = self.engine.solve(k, float(r0), **solve_kw)
+        else:
+            before = st.res["info"]
+            res = self.engine.solve(k, float(r0), out=rows_of(st.res), phase=3, **solve_kw)
+            res["info"] = self._merge_infos(before, res["info"], int(before["unfinished"]) * level)
+        st.res = res
+
+    def _anyone_left(self, info):
+        """ONE all-reduce per step: (no rank has unfinished queries -- a maximum says so as well as a sum --, most rounds)"""
+        left = torch.tensor([int(info["unfinished"]), int(info["rounds"])], dtype=torch.int64, device=self.device)
+        unfinished, rounds = self.comm.all_reduce(left, dist.ReduceOp.MAX).tolist()
+        return int(unfinished) == 0, int(rounds)
+
+    def solve(self, k, start_radius, max_rounds=64, want_fb=False):
+        r0 = np.float32(start_radius)
+        level = self._first_halo_level(k, r0)
+        clock = _PhaseClock(("select", "exchange", "halo_build", "solve", "reduce"), self.device, self.profile)
+        st = _SolveState(self.comm.world)
+        while True:
+            tag = ("halo", level, st.res is None)
+            halo_radius = self._halo_radius(r0, level)
+            solve_kw = dict(kernel=self.kernel, max_rounds=level + 1, want_fb=want_fb, want_levels=True, allow_unfinished=True)
+            clock.restart()
+            blocks, selection = self._select(st, tag, halo_radius)
+            clock.lap("select")
+            with self._interior_solve(st, k, r0, want_fb, solve_kw) as interior:
+                self._exchange(st, tag, blocks, selection, halo_radius, clock)
+            if interior is not None:
+                clock.ms["interior_solve_overlapped"] = interior["ms"]  # (a first step's: once per solve)
+                clock.restart()
+            self._engine_step(st, k, r0, level, interior, solve_kw)
+            clock.lap("solve")
+            done, rounds_all = self._anyone_left(st.res["info"])
+            clock.lap("reduce")
             if done:
                 break
-            if level_cap + 1 >= max_rounds:
+            if level + 1 >= max_rounds:
                 raise _lib.TknnError(-4, "max_rounds reached with unfinished queries")
-            level_cap += 1  # stragglers need the next radius level: widen the halo by its shell and solve them again
-        info = dict(res["info"])
-        info["rounds"] = rounds_all
-        info["halo_exchanges"] = exchanges
-        info["halo_points"] = halo_points
-        info["halo_points_by_exchange"] = round_halo  # the first exchange's halo, then the shells of the straggler rounds
-        info["halo_levels"] = level_cap
-        info["overlapped"] = bool(overlapped)
-        info["halo_select_one_pass"] = bool(one_pass)
-        if profile:
-            info["phase_ms"] = phase
-        self.last = res
+            level += 1  # stragglers need the next radius level: widen the halo by its shell and solve them again
+        # (halo_points_by_exchange: the first exchange's halo, then the shells of the straggler rounds)
+        info = dict(st.res["info"], rounds=rounds_all, halo_exchanges=len(st.round_halo), halo_points=len(st.halo),
+                    halo_points_by_exchange=st.round_halo, halo_levels=level, overlapped=st.overlapped, halo_select_one_pass=st.one_pass)
+        if self.profile:
+            info["phase_ms"] = clock.ms
+        self.last = st.res
         self.last["info"] = info
         return info
 
@@ -623,26 +654,13 @@ class ShardedTrueKNN:
         propagation: label = smallest core id known for the component; a round takes the minimum
         over each local component, sends the labels of halo copies back to their owners (minimum) and
         the owners' labels out to the copies again, until nothing changes anywhere."""
-        comm, dev = self.comm, self.device
-        eps32 = float(np.float32(eps))
-        m = len(self.points)
-        phase = {"setup": 0.0, "cluster": 0.0, "propagate": 0.0, "number": 0.0, "assign": 0.0}
-        profile = self.profile
-
-        def lap(name, t0):  # (TKNN_SHARD_PROFILE / bench.py's instrumented steps: a device synchronisation per phase)
-            if profile:
-                if dev.type == "cuda":
-                    torch.cuda.synchronize(dev)
-                phase[name] += (time.perf_counter() - t0) * 1e3
-            return time.perf_counter()
-
-        t = time.perf_counter()
+        dev, eps32, m = self.device, float(np.float32(eps)), len(self.points)
+        clock = _PhaseClock(("setup", "cluster", "propagate", "number", "assign"), dev, self.profile)
         halo, counts_in, sent_local, ids = self._db_setup(eps32, reuse=_reuse_setup)
-        t = lap("setup", t)
+        clock.lap("setup")
         local = self.db_engine.dbscan(eps32, min_pts)
-        t = lap("cluster", t)
+        clock.lap("cluster")
         core = local["core"].to(dev).bool()
-        big = torch.iinfo(torch.int64).max
         # Label propagation works on CLUSTERS, not points (round 4; the per-point form spent 160 ms of a 174 ms step in
         # scatter-reduces of ten million values onto 83 addresses): lab_comp[c] = the smallest global core id known for local
         # cluster c.  Per point there is one step before the rounds (the clusters' own minima: tknnSegmentMin) and one gather
@@ -652,15 +670,39 @@ class ShardedTrueKNN:
         if ncomp < 0:  # (an engine that does not say)
             ncomp = int(seg.max().item()) + 1 if len(seg) else 0
         ncomp = max(ncomp, 0)
-        lab_comp = torch.full((max(ncomp, 1),), big, dtype=torch.int64, device=dev)
+        lab_comp = torch.full((max(ncomp, 1),), _BIG, dtype=torch.int64, device=dev)
         self._seg_min(seg, ids.long(), lab_comp)
+        rounds = self._propagate_labels(lab_comp, seg, m, counts_in, sent_local)
+        clock.lap("propagate")
+        clusters, core_label = self._number_clusters(lab_comp, seg, ids, m)
+        clock.lap("number")
+        labels = self.db_engine.dbscan_assign(eps32, core_label)
+        clock.lap("assign")
+        info = {"clusters": clusters, "rounds": rounds, "label_rounds": rounds, "halo_points": int(len(halo)), "halo_exchanges": 1}
+        # the tile's own clustering as its engine reports it (device times of the three traversal kernels, work counters)
+        eng_info = dict(local.get("info") or {})
+        eng_info["n_clustered"] = int(len(ids))
+        info["engine"] = eng_info
+        if self.profile:
+            info["phase_ms"] = clock.ms
+        return {"labels": labels[:m].to(dev), "core": core[:m], "info": info}
+
+    def _propagate_labels(self, lab_comp, seg, m, counts_in, sent_local):
+        """Label propagation between the ranks, in place on ``lab_comp`` (per local cluster, the smallest global core id
+        known): a round sends the labels of the halo copies back to their owners (minimum) and the owners' labels out to
+        the copies again, until a round changes nothing on any rank.  Returns the number of rounds."""
+        comm, dev = self.comm, self.device
         seg_halo = seg[m:]
         seg_sent = [seg[:m][sent_local[p]] if len(sent_local[p]) else seg[:0] for p in range(comm.world)]
         offs = np.concatenate([[0], np.cumsum(counts_in)])
-        big_row = torch.full((1,), big, dtype=torch.int64, device=dev)
+        big_row = torch.full((1,), _BIG, dtype=torch.int64, device=dev)
 
         def of_clusters(which):  # the clusters' labels for a list of rows (a row that is not core: nothing to say)
             return torch.where(which >= 0, lab_comp[which.clamp(min=0).long()], big_row).reshape(-1, 1).contiguous()
+
+        def answer(blocks, expect):  # (both directions answer rows that travelled before: every count is known at both ends)
+            expect = [int(len(blocks[p])) if p == comm.rank else int(c) for p, c in enumerate(expect)]
+            return comm.exchange_rows(blocks, 1, torch.int64, dev, counts_in=expect)
 
         rounds = 0
         while True:
@@ -668,48 +710,35 @@ class ShardedTrueKNN:
             before = lab_comp.clone()
             # copies -> owners (minimum)
             back = [of_clusters(seg_halo[int(offs[s_]): int(offs[s_ + 1])]) for s_ in range(comm.world)]
-            # (both directions answer rows that travelled before: every count is known at both ends, none is exchanged)
-            expect_back = [int(len(sent_local[p])) for p in range(comm.world)]
-            expect_back[comm.rank] = int(len(back[comm.rank]))
-            for p, vals in enumerate(comm.exchange_rows(back, 1, torch.int64, dev, counts_in=expect_back)):
+            for p, vals in enumerate(answer(back, [len(s_) for s_ in sent_local])):
                 if p != comm.rank and len(vals):
                     self._seg_min(seg_sent[p], vals.flatten(), lab_comp)
             # owners -> copies
-            fwd = [of_clusters(seg_sent[p]) for p in range(comm.world)]
-            expect_fwd = [int(c) for c in counts_in]
-            expect_fwd[comm.rank] = int(len(fwd[comm.rank]))
-            new = comm.exchange_rows(fwd, 1, torch.int64, dev, counts_in=expect_fwd)
+            new = answer([of_clusters(seg_sent[p]) for p in range(comm.world)], counts_in)
             new[comm.rank] = new[comm.rank][:0]
-            if len(halo):
+            if len(seg_halo):
                 self._seg_min(seg_halo, torch.cat(new, dim=0).flatten(), lab_comp)
             changed = torch.tensor([int(bool((lab_comp != before).any()))], dtype=torch.int64, device=dev)
             comm.all_reduce(changed, dist.ReduceOp.MAX)
             if int(changed.item()) == 0:
-                break
-        t = lap("propagate", t)
-        # cluster numbers: ascending smallest core id over ALL ranks (of the clusters that have a core point of MINE)
-        own_min = torch.full_like(lab_comp, big)
+                return rounds
+
+    def _number_clusters(self, lab_comp, seg, ids, m):
+        """Global cluster numbers: ascending smallest core id over ALL ranks (a rank contributes the clusters that have a
+        core point of its OWN).  Returns (number of clusters, per row of ``seg`` the number of its cluster or -1)."""
+        comm, dev = self.comm, self.device
+        own_min = torch.full_like(lab_comp, _BIG)
         self._seg_min(seg[:m], ids[:m].long(), own_min)
-        mine = torch.unique(lab_comp[own_min != big])
+        mine = torch.unique(lab_comp[own_min != _BIG])
         width = torch.tensor([len(mine)], dtype=torch.int64, device=dev)
         comm.all_reduce(width, dist.ReduceOp.MAX)
-        padded = torch.full((max(int(width.item()), 1),), big, dtype=torch.int64, device=dev)
+        padded = torch.full((max(int(width.item()), 1),), _BIG, dtype=torch.int64, device=dev)
         padded[: len(mine)] = mine
         everyone = torch.unique(comm.all_gather(padded).flatten())
-        everyone = everyone[everyone != big]
+        everyone = everyone[everyone != _BIG]
         number_comp = torch.searchsorted(everyone, lab_comp.clamp(max=int(everyone[-1].item()) if len(everyone) else 0)).int()
         core_label = torch.where(seg >= 0, number_comp[seg.clamp(min=0).long()], torch.full_like(seg, -1))
-        t = lap("number", t)
-        labels = self.db_engine.dbscan_assign(eps32, core_label)
-        t = lap("assign", t)
-        info = {"clusters": int(len(everyone)), "rounds": rounds, "label_rounds": rounds, "halo_points": int(len(halo)), "halo_exchanges": 1}
-        # the tile's own clustering as its engine reports it (device times of the three traversal kernels, work counters)
-        eng_info = dict(local.get("info") or {})
-        eng_info["n_clustered"] = int(len(ids))
-        info["engine"] = eng_info
-        if profile:
-            info["phase_ms"] = phase
-        return {"labels": labels[:m].to(dev), "core": core[:m], "info": info}
+        return int(len(everyone)), core_label
 
     def _seg_min(self, seg, val, out):
         """out[seg[i]] = min(out[seg[i]], val[i]) for seg[i] >= 0: the engine's kernel (tknnSegmentMin) if it has one, else torch"""

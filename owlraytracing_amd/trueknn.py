@@ -147,6 +147,7 @@ class TrueKNN:
                                                      int(npeers), ctypes.c_void_p(caps_dev.data_ptr()), ctypes.c_void_p(offsets.data_ptr()),
                                                      ctypes.c_void_p(messages.data_ptr()), ctypes.c_void_p(counts.data_ptr()), self._stream()))
             heads = torch.tensor(starts, dtype=torch.int64, device=dev)
+            # (the header cells distributed._count_cells writes on the host; distributed._count_of_cells reads them)
             messages[heads, 0] = (counts % (1 << 24)).float()
             messages[heads, 1] = (counts >> 24).float()
             return messages, starts, counts

@@ -108,6 +108,31 @@ def make_points(name, n):
     raise ValueError(name)
 
 
+class _CountCollectives:
+    """Calls of dist.batch_isend_irecv / all_reduce / all_gather inside the block (the driver reaches them through the module)."""
+    NAMES = ("batch_isend_irecv", "all_reduce", "all_gather")
+
+    def __enter__(self):
+        self.calls = dict.fromkeys(self.NAMES, 0)
+        self._real = {name: getattr(dist, name) for name in self.NAMES}
+        for name in self.NAMES:
+            setattr(dist, name, self._counting(name))
+        return self
+
+    def _counting(self, name):
+        def call(*args, **kwargs):
+            self.calls[name] += 1
+            return self._real[name](*args, **kwargs)
+        return call
+
+    def __exit__(self, *exc):
+        for name in self.NAMES:
+            setattr(dist, name, self._real[name])
+
+    def triple(self):
+        return [self.calls[name] for name in self.NAMES]
+
+
 def main():
     engine, n, k, name, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4], sys.argv[5]
     use_gpu = engine == "hip"
@@ -159,11 +184,13 @@ def main():
     r0 = float(os.environ.get("START_RADIUS", datasets.start_radius(n, k)))
     import time
     t0 = time.perf_counter()
-    info = solver.solve(k, r0)
+    with _CountCollectives() as first_calls:
+        first_info = solver.solve(k, r0)
     if use_gpu:
         torch.cuda.synchronize()
     t1 = time.perf_counter()
-    info = solver.solve(k, r0)
+    with _CountCollectives() as second_calls:
+        info = solver.solve(k, r0)
     if use_gpu:
         torch.cuda.synchronize()
     print('rank %d tile=%d halo=%d exchanges=%d solve_s first=%.4f second=%.4f kernel_ms=%.2f' % (rank, len(solver.points), info['halo_points'], info['halo_exchanges'], t1 - t0, time.perf_counter() - t1, info['dominant_kernel_ms']), flush=True)
@@ -183,7 +210,9 @@ def main():
         np.savez(out, gids=gids, idx=idx, dist=dst, isect=isect, rounds=info["rounds"],
                  exchanges=info["halo_exchanges"], halo_points=info["halo_points"], tile=len(solver.points),
                  halo_by_exchange=np.asarray(info["halo_points_by_exchange"], np.int64), total_isect=info["total_intersections"],
-                 one_pass=bool(info.get("halo_select_one_pass", False)))
+                 one_pass=bool(info.get("halo_select_one_pass", False)),
+                 collectives=np.asarray([first_calls.triple(), second_calls.triple()], np.int64),
+                 exchanges_by_solve=np.asarray([first_info["halo_exchanges"], info["halo_exchanges"]], np.int64))
     dist.barrier()
     dist.destroy_process_group()
 

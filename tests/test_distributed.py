@@ -37,6 +37,15 @@ def _check(got, name, n, k, r0=None):
     assert int(got["rounds"]) == ref["rounds"]
 
 
+def _check_collectives(got, second_only=False):
+    """One point-to-point batch and one all-reduce per exchange; the first exchange under a tag also agrees on the counts
+    (an all-gather), a solve that finds the capacities known does not.  (batch_isend_irecv, all_reduce, all_gather) of rank 0."""
+    first, second = (int(e) for e in got["exchanges_by_solve"])
+    if not second_only:
+        assert got["collectives"][0].tolist() == [first, first, first]
+    assert got["collectives"][1].tolist() == [second, second, 0]
+
+
 @pytest.mark.parametrize("count", [1, 2, 1023, 1024, 1025, (1 << 24) + 1, 33_554_436, 50_000_000, (1 << 31) + 7])
 def test_splitter_sample_positions_stay_inside_large_tiles(count):
     """The splitter sample of load_points indexes the rank's sorted codes: positions must be exact
@@ -60,6 +69,7 @@ def test_tiles_and_halo_exchange_reproduce_the_single_process_result(tmp_path, w
     got = _run("checker", world, n, k, name, tmp_path, 29611 + world)
     _check(got, name, n, k)
     assert int(got["halo_points"]) > 0
+    _check_collectives(got)
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -90,6 +100,7 @@ def test_straggler_rounds_send_the_shell_and_solve_only_the_stragglers(tmp_path)
     _check(got, "clustered", n, k, r0=0.01)
     by = got["halo_by_exchange"]
     assert int(got["exchanges"]) == len(by) >= 3
+    _check_collectives(got)
     assert int(by.sum()) == int(got["halo_points"])  # rank 0's halo tree = the first halo + the shells, nothing twice
     # a whole re-send would carry at least the previous halo again: every shell is smaller than what is held already
     assert all(int(by[j]) < int(by[:j].sum()) for j in range(2, len(by)))
@@ -135,6 +146,79 @@ dist.destroy_process_group()
     assert r.stdout.count(" ok caps ") == 2
 
 
+def test_fixed_capacity_exchange_of_selected_messages_without_an_engine(tmp_path):
+    """_Comm.exchange_fixed, the form real multi-GPU steps take, on two gloo ranks with hand-built messages: after a tagged
+    exchange_rows has taught the capacities, every step lays out a header row (count in two float32 cells), the rows up to the
+    capacity and NaN in every cell past the count (a decoder that reads them shows up), and passes the counts as an int64
+    tensor.  Blocks arrive bit for bit, ``sent`` is the whole block, ``exact_blocks`` is asked iff MY rows outgrew their
+    capacity, a step is one batched send/recv (two when a pair outgrew), and capacities grow to max(old, c + c // 4 + 64)."""
+    script = tmp_path / "xfix.py"
+    script.write_text("""
+import sys, torch, torch.distributed as dist
+sys.path.insert(0, %r)
+from owlraytracing_amd.distributed import _Comm
+dist.init_process_group("gloo")
+c = _Comm()
+r, w = c.rank, c.world
+peer = 1 - r
+dev = torch.device("cpu")
+batches = [0]
+real_batch = dist.batch_isend_irecv
+def counted_batch(ops):
+    batches[0] += 1
+    return real_batch(ops)
+dist.batch_isend_irecv = counted_batch
+def block(src, dst, m, step):
+    return (torch.arange(m * 4, dtype=torch.float32).reshape(m, 4) + 1000.0 * src + 10.0 * dst + 0.25 * step)
+grow = lambda n: n + n // 4 + 64
+# rows 0 -> 1, rows 1 -> 0 per step: same, shrinking, growing within capacity, empty, both pairs outgrowing, one side at rest
+sizes = [(5, 7), (5, 7), (6, 3), (40, 2), (0, 0), (300, 300), (1, 374)]
+calls = []
+for step, (a, b) in enumerate(sizes):
+    m_out, m_in = (a, b) if r == 0 else (b, a)
+    mine, want = block(r, peer, m_out, step), block(peer, r, m_in, step)
+    batches[0] = 0
+    if step == 0:
+        got = c.exchange_rows([mine if p == peer else mine[:0] for p in range(w)], 4, torch.float32, dev, tag="t")
+        assert c.has_caps("t")
+        cap_in, cap_out = list(c._caps[("t", "in")]), c.caps_out("t")
+        assert cap_in[peer] == grow(m_in) and cap_out[peer] == grow(m_out)
+    else:
+        caps = [0 if p == r else cap for p, cap in enumerate(c.caps_out("t"))]
+        starts = [sum(caps[:p]) + p for p in range(w)]
+        messages = torch.full((sum(caps) + w, 4), float("nan"))
+        messages[starts[r], :2] = 0.0
+        messages[starts[peer], 0], messages[starts[peer], 1] = float(m_out %% (1 << 24)), float(m_out >> 24)
+        take = min(m_out, caps[peer])
+        messages[starts[peer] + 1: starts[peer] + 1 + take] = mine[:take]
+        counts = torch.tensor([m_out if p == peer else 0 for p in range(w)], dtype=torch.int64)
+        asked = []
+        def exact_blocks():
+            asked.append(step)
+            return [mine if p == peer else mine[:0] for p in range(w)]
+        got, sent = c.exchange_fixed(messages, starts, counts, "t", dev, exact_blocks)
+        assert sent[peer].shape == mine.shape and torch.equal(sent[peer], mine), (step, r, sent[peer].shape)
+        assert len(sent[r]) == 0 and len(got[r]) == 0
+        assert bool(asked) == (m_out > cap_out[peer]), (step, r, asked, m_out, cap_out[peer])
+        assert batches[0] == (2 if (a, b) == (300, 300) else 1), (step, r, batches[0])
+        cap_in[peer], cap_out[peer] = max(cap_in[peer], grow(m_in)), max(cap_out[peer], grow(m_out))
+        assert c._caps[("t", "in")][peer] == cap_in[peer] and c.caps_out("t")[peer] == cap_out[peer], (step, r, c._caps)
+    calls.append(batches[0])
+    assert got[peer].shape == want.shape and torch.equal(got[peer], want), (step, r, got[peer].shape, want.shape)
+if r == 0:
+    assert c._caps[("t", "in")] == [64, 531] and c._caps[("t", "out")] == [64, 439], c._caps
+assert calls == [1, 1, 1, 1, 1, 2, 1], calls
+print("rank %%d ok calls %%s" %% (r, calls))
+dist.destroy_process_group()
+""" % ROOT)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29638", str(script)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert r.stdout.count(" ok calls ") == 2
+
+
 @pytest.mark.gpu
 def test_straggler_rounds_with_the_hip_engine(tmp_path):
     """The same with the real engine (tknnSolveOptions.phase = 3 over own + widened halo tree), three ranks sharing the GPU."""
@@ -155,6 +239,7 @@ def test_two_ranks_sharing_one_gpu_with_the_hip_engine(tmp_path):
     # the worker solves twice and reports the second solve: its halo rows were selected in ONE pass straight into messages of
     # the capacity the first exchange taught both ends (tknnHaloSelectFixed), counts read with the headers
     assert bool(got["one_pass"])
+    _check_collectives(got, second_only=True)
 
 
 @pytest.mark.gpu
