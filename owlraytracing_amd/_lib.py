@@ -21,7 +21,15 @@ class TknnError(RuntimeError):
         self.code = code
 
 
-class SolveInfo(ctypes.Structure):
+class _Record(ctypes.Structure):
+    """A record of include/owlknn.h."""
+
+    def as_dict(self):
+        """The record's fields by name, without its reserved_ and pad_ words."""
+        return {name: getattr(self, name) for name, _ in self._fields_ if name not in ("reserved_", "pad_")}
+
+
+class SolveInfo(_Record):
     _fields_ = [
         ("rounds", ctypes.c_int32),
         ("final_radius", ctypes.c_float),
@@ -41,11 +49,8 @@ class SolveInfo(ctypes.Structure):
         ("reserved_", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
-
-class SolveOptions(ctypes.Structure):
+class SolveOptions(_Record):
     _fields_ = [
         ("k", ctypes.c_int32),
         ("start_radius", ctypes.c_float),
@@ -62,7 +67,7 @@ class SolveOptions(ctypes.Structure):
     ]
 
 
-class QueryOptions(ctypes.Structure):
+class QueryOptions(_Record):
     _fields_ = [
         ("d_queries", ctypes.c_void_p),
         ("m", ctypes.c_int64),
@@ -79,7 +84,7 @@ class QueryOptions(ctypes.Structure):
     ]
 
 
-class DbscanQueryOptions(ctypes.Structure):
+class DbscanQueryOptions(_Record):
     _fields_ = [
         ("d_queries", ctypes.c_void_p),
         ("m", ctypes.c_int64),
@@ -91,7 +96,7 @@ class DbscanQueryOptions(ctypes.Structure):
     ]
 
 
-class RadiusOptions(ctypes.Structure):
+class RadiusOptions(_Record):
     _fields_ = [
         ("d_queries", ctypes.c_void_p),
         ("m", ctypes.c_int64),
@@ -104,16 +109,13 @@ class RadiusOptions(ctypes.Structure):
     ]
 
 
-class RadiusInfo(ctypes.Structure):
+class RadiusInfo(_Record):
     _fields_ = [("total", ctypes.c_int64), ("max_row", ctypes.c_int64), ("mismatched", ctypes.c_int64),
                 ("node_tests", ctypes.c_int64), ("point_tests", ctypes.c_int64), ("solve_ms", ctypes.c_float),
                 ("order_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("sort_ms", ctypes.c_float)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
-
-class RadiusKnnOptions(ctypes.Structure):
+class RadiusKnnOptions(_Record):
     _fields_ = [
         ("d_queries", ctypes.c_void_p),
         ("m", ctypes.c_int64),
@@ -127,27 +129,21 @@ class RadiusKnnOptions(ctypes.Structure):
     ]
 
 
-class RadiusKnnInfo(ctypes.Structure):
+class RadiusKnnInfo(_Record):
     _fields_ = [("total", ctypes.c_int64), ("full_rows", ctypes.c_int64), ("node_tests", ctypes.c_int64),
                 ("point_tests", ctypes.c_int64), ("lane_rows", ctypes.c_int64), ("solve_ms", ctypes.c_float),
                 ("order_ms", ctypes.c_float), ("walk_ms", ctypes.c_float), ("reserved_", ctypes.c_int32)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved_"}
 
-
-class DbscanInfo(ctypes.Structure):
+class DbscanInfo(_Record):
     _fields_ = [("clusters", ctypes.c_int32), ("solve_ms", ctypes.c_float), ("core_ms", ctypes.c_float),
                 ("union_ms", ctypes.c_float), ("label_ms", ctypes.c_float), ("union_launches", ctypes.c_int32),
                 ("node_tests", ctypes.c_int64), ("point_tests", ctypes.c_int64), ("core_point_tests", ctypes.c_int64),
                 ("union_point_tests", ctypes.c_int64), ("label_point_tests", ctypes.c_int64),
                 ("union_node_tests", ctypes.c_int64), ("groups", ctypes.c_int64)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "pad_"}
 
-
-class DbscanAutoInfo(ctypes.Structure):
+class DbscanAutoInfo(_Record):
     _fields_ = [("last", DbscanInfo), ("rounds", ctypes.c_int32), ("eps", ctypes.c_float), ("noise", ctypes.c_int64),
                 ("probe_ms", ctypes.c_float), ("pad_", ctypes.c_int32)]
 
@@ -157,14 +153,11 @@ class DbscanAutoInfo(ctypes.Structure):
         return d
 
 
-class BuildInfo(ctypes.Structure):
+class BuildInfo(_Record):
     _fields_ = [("build_ms", ctypes.c_float), ("device_bytes", ctypes.c_int64), ("n", ctypes.c_int32)]
 
-    def as_dict(self):
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
-
-class TreeExport(ctypes.Structure):
+class TreeExport(_Record):
     _fields_ = [("which", ctypes.c_int32), ("curve", ctypes.c_int32), ("n", ctypes.c_int64), ("nan_count", ctypes.c_int32),
                 ("wide_levels", ctypes.c_int32), ("wide_count", ctypes.c_int32 * 6), ("scene", ctypes.c_float * 6),
                 ("wide_capacity", ctypes.c_int64), ("keys", ctypes.c_void_p), ("points", ctypes.c_void_p),
@@ -223,7 +216,12 @@ _lib = None
 
 
 def load():
-    """Load the shared library (no GPU needed for loading itself)."""
+    """Load the shared library (no GPU needed for loading itself).
+
+    Order matters in a process that also uses torch: torch brings a HIP runtime of its own, the library is linked against the
+    system's.  With torch imported first the library binds to torch's runtime and both see the GPU; with the library loaded
+    first the process holds two runtimes, and the one that starts second reports "no ROCm-capable device is detected"
+    (tknnCreate then returns TKNN_E_HIP).  Import torch before the first call of load()."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -246,12 +244,13 @@ def check(rc):
 
 # native sources a kernel's code does NOT depend on, by kernel-name prefix (the FIRST matching prefix counts: team_walk_ stands
 # before team_): a committed profile of the packet kernel stays valid when only the tie pass, the k > 64 walk or the
-# clustering kernels change, and the other way round; one of the label pass when only the union pass changes
+# clustering kernels change, and the other way round; one of the label pass when only the union pass changes; every one when
+# only the C ABI's argument checks and messages (tknn_api.hip, which holds no kernel) change
 _NOT_TEAM = ("dbscan.hip", "dbscan_core.hip", "dbscan_union.hip", "dbscan_label.hip", "db_device.h", "db_call.h", "halo_select.hip", "radius_query.hip",
-             "radius_knn.hip", "owl_runtime.cpp")
+             "radius_knn.hip", "tknn_api.hip", "owl_runtime.cpp")
 # RT-DBSCAN's kernels are in three files by pass; dbscan.hip, the host side that decides their grids and arguments, counts for all
 _NOT_DB = ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip",
-           "owl_runtime.cpp")
+           "tknn_api.hip", "owl_runtime.cpp")
 _NOT_DB_CORE, _NOT_DB_UNION = _NOT_DB + ("dbscan_union.hip", "dbscan_label.hip"), _NOT_DB + ("dbscan_core.hip", "dbscan_label.hip")
 _NOT_IN = {
     "team_walk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),  # trueknn_tail.hip

@@ -258,8 +258,8 @@ const RknnWalkEntry kRknnWalks[4] = {radius_knn_walk_kernel<1>, radius_knn_walk_
 
 }  // namespace
 
-void Engine::radius_knn(const RadiusKnnArgs &ra, tknnRadiusKnnInfo *info, hipStream_t s) {
-  const int64_t m = ra.m;
+void Engine::radius_knn(const tknnRadiusKnnOptions &o, tknnRadiusKnnInfo *info, hipStream_t s) {
+  const int64_t m = o.m;
   // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | sort space
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t sort_bytes = query_order_sort_bytes(m, s);
@@ -275,23 +275,23 @@ void Engine::radius_knn(const RadiusKnnArgs &ra, tknnRadiusKnnInfo *info, hipStr
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
   a.wide = bvh_.wide_view();
-  a.queries = ra.d_queries;
+  a.queries = o.d_queries;
   a.order = order;
   a.m = (int32_t)m;
-  a.k = ra.k;
-  a.radius = ra.radius;
-  a.radii = ra.d_radii;
-  a.skip_ids = ra.d_skip_ids;
+  a.k = o.k;
+  a.radius = o.radius;
+  a.radii = o.d_radii;
+  a.skip_ids = o.d_skip_ids;
   if (const char *e = getenv("TKNN_RADIUS_KNN_FORCE_FALLBACK")) a.force_redo = atoi(e) != 0;
-  a.out_idx = ra.d_idx;
-  a.out_dist = ra.d_dist;
-  a.out_counts = ra.d_counts;
+  a.out_idx = o.d_idx;
+  a.out_dist = o.d_dist;
+  a.out_counts = o.d_counts;
   a.redo = redo;
   a.ws = d_words;
 
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   OWLMI_HIP(hipMemsetAsync(d_words, 0, kWsWords * sizeof(unsigned long long), s));
-  query_order(ra.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
+  query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   // the walk, then the lane kernel for what the walk left
   const int blocks = (int)std::min<int64_t>((m + 3) / 4, (int64_t)cu_count_ * kRknnBlocksPerCu);

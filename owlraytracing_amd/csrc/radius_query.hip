@@ -298,18 +298,18 @@ inline float radius_inside2(float r) {
 
 }  // namespace
 
-void Engine::radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_t s) {
-  const int64_t m = ra.m;
-  const bool fill = ra.d_idx != nullptr, sorted = fill && ra.sort;
+void Engine::radius_query(const tknnRadiusOptions &o, tknnRadiusInfo *info, hipStream_t s) {
+  const int64_t m = o.m;
+  const bool fill = o.d_idx != nullptr, sorted = fill && o.sort != 0;
   int64_t total = 0;
   if (fill) {
     // the one look at the caller's offsets: the fill pass's size
     int64_t *h_total = (int64_t *)(h_counters_ + kWsWords);
-    OWLMI_HIP(hipMemcpyAsync(h_total, ra.d_offsets + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    OWLMI_HIP(hipMemcpyAsync(h_total, o.d_offsets + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     OWLMI_HIP(hipStreamSynchronize(s));
     total = *h_total;
-    if (total < 0 || total > ra.capacity)
-      throw ArgError{TKNN_E_ARG, "tknnRadiusQuery: d_offsets[m] = " + std::to_string(total) + " neighbours do not fit the capacity of " + std::to_string(ra.capacity)};
+    if (total < 0 || total > o.capacity)
+      throw ArgError{TKNN_E_ARG, "tknnRadiusQuery: d_offsets[m] = " + std::to_string(total) + " neighbours do not fit the capacity of " + std::to_string(o.capacity)};
     if (total >= 0x80000000LL) throw ArgError{TKNN_E_UNSUPPORTED, "tknnRadiusQuery: 2^31 or more neighbours in one call: split the queries"};
   }
   // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | row lengths | keys, sorted keys | scan / sort space
@@ -322,7 +322,7 @@ void Engine::radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_
   if (!fill) OWLMI_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, null_u32, null_i64, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), s));
   const bool sorting = sorted && total > 0;
   if (sorting)
-    OWLMI_HIP(rocprim::segmented_radix_sort_keys(nullptr, seg_bytes, null_key, null_key, (unsigned int)total, (unsigned int)m, ra.d_offsets, ra.d_offsets + 1, 0, 64, s));
+    OWLMI_HIP(rocprim::segmented_radix_sort_keys(nullptr, seg_bytes, null_key, null_key, (unsigned int)total, (unsigned int)m, o.d_offsets, o.d_offsets + 1, 0, 64, s));
   const size_t words_b = align(kWsWords * sizeof(unsigned long long)), col_b = align(((size_t)m + 1) * sizeof(uint32_t)),
                keys_b = sorting ? align((size_t)total * sizeof(unsigned long long)) : 0, tmp_b = align(std::max(order_bytes, std::max(scan_bytes, seg_bytes)));
   char *ws = (char *)workspace(words_b + 6 * col_b + 2 * keys_b + tmp_b);
@@ -338,26 +338,26 @@ void Engine::radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
   a.wide = bvh_.wide_view();
-  a.queries = ra.d_queries;
+  a.queries = o.d_queries;
   a.order = order;
   a.m = (int32_t)m;
-  a.radius = ra.radius;
-  a.radius_wide = ra.radius * 1.000001f;
-  a.radius_in2 = radius_inside2(ra.radius);
+  a.radius = o.radius;
+  a.radius_wide = o.radius * 1.000001f;
+  a.radius_in2 = radius_inside2(o.radius);
   if (const char *e = getenv("TKNN_RADIUS_FORCE_FALLBACK")) a.force_redo = atoi(e) != 0;
   a.counts = counts;
-  a.offsets = ra.d_offsets;
+  a.offsets = o.d_offsets;
   a.total = total;
   a.keys = sorting ? keys : nullptr;
-  a.out_idx = ra.d_idx;
-  a.out_dist = ra.d_dist;
+  a.out_idx = o.d_idx;
+  a.out_dist = o.d_dist;
   a.redo = redo;
   a.ws = d_words;
 
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   OWLMI_HIP(hipMemsetAsync(d_words, 0, kWsWords * sizeof(unsigned long long), s));
   if (!fill) OWLMI_HIP(hipMemsetAsync(counts + m, 0, sizeof(uint32_t), s));  // the scan runs over m + 1 lengths: offsets[m] is the total
-  query_order(ra.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, tmp, order_bytes, s);
+  query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, tmp, order_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   // the walk, then the lane kernel for what the walk left
   const int blocks = (int)std::min<int64_t>((m + 3) / 4, (int64_t)cu_count_ * kRadiusBlocksPerCu);
@@ -382,11 +382,11 @@ void Engine::radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_
   OWLMI_HIP(hipStreamSynchronize(s));
   const bool mismatch = fill && h_words[kWsMismatched] != 0;
   if (!fill) {
-    OWLMI_HIP(rocprim::exclusive_scan(tmp, scan_bytes, counts, ra.d_offsets, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), s));
+    OWLMI_HIP(rocprim::exclusive_scan(tmp, scan_bytes, counts, o.d_offsets, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), s));
   } else if (sorting && !mismatch) {
-    OWLMI_HIP(rocprim::segmented_radix_sort_keys(tmp, seg_bytes, keys, keys_sorted, (unsigned int)total, (unsigned int)m, ra.d_offsets, ra.d_offsets + 1, 0, 64, s));
-    hipLaunchKernelGGL(radius_split_kernel, dim3((unsigned)((total + kSplitBlock - 1) / kSplitBlock)), dim3(kSplitBlock), 0, s, keys_sorted, total, ra.d_idx,
-                       ra.d_dist);
+    OWLMI_HIP(rocprim::segmented_radix_sort_keys(tmp, seg_bytes, keys, keys_sorted, (unsigned int)total, (unsigned int)m, o.d_offsets, o.d_offsets + 1, 0, 64, s));
+    hipLaunchKernelGGL(radius_split_kernel, dim3((unsigned)((total + kSplitBlock - 1) / kSplitBlock)), dim3(kSplitBlock), 0, s, keys_sorted, total, o.d_idx,
+                       o.d_dist);
     OWLMI_HIP(hipGetLastError());
   }
   OWLMI_HIP(hipEventRecord(ev_d_, s));

@@ -1,0 +1,430 @@
+// tknn_api.hip -- the C ABI of include/owlknn.h and nothing else: every entry point checks its arguments and hands over to
+// the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
+//
+// What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
+// current (a failure of that is TKNN_E_HIP, whatever else is wrong with the call), required pointers are checked, then the
+// engine's state (TKNN_E_STATE before tknnBuild), then values; a refused call has written nothing, its info included (info is zeroed once the arguments are
+// accepted); a message starts with the function's name and names the argument or the constraint.
+#include "trueknn_engine.h"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+using owlmi::Engine;
+
+static thread_local std::string g_last_error;
+
+struct tknnEngine_t {
+  Engine impl;
+};
+
+namespace {
+
+// Every engine call runs on the device the engine was created on (the caller's current device at
+// tknnCreate), whatever device is current in the calling thread now; the caller's choice is restored.
+struct DeviceScope {
+  int prev = -1, want;
+  explicit DeviceScope(int device) : want(device) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != want && hipSetDevice(want) != hipSuccess) throw owlmi::HipError{"hipSetDevice(engine's device) failed"};
+  }
+  ~DeviceScope() {
+    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
+  }
+};
+
+// The checks of one call: each throws the refusal, said in the function's name.
+struct Call {
+  const char *fn;
+  tknnEngine e;
+  [[noreturn]] void refuse(int code, const std::string &why) const { throw owlmi::ArgError{code, std::string(fn) + ": " + why}; }
+  void require(bool ok, const char *why) const {
+    if (!ok) refuse(TKNN_E_ARG, why);
+  }
+  void need(const void *p, const char *name) const {
+    if (!p) refuse(TKNN_E_ARG, std::string(name) + " is NULL");
+  }
+  template <typename T>
+  const T &record(const T *options) const {
+    need(options, "options");
+    return *options;
+  }
+  void built() const {
+    if (!e->impl.built()) refuse(TKNN_E_STATE, "call tknnBuild first");
+  }
+  void positive(float x, const char *name) const {
+    if (!(x > 0.f) || !std::isfinite(x)) refuse(TKNN_E_ARG, std::string(name) + " must be finite and > 0");
+  }
+  void count(int64_t m, const char *name, int64_t least = 0) const {
+    if (m < least || m >= 0x7fffffffLL) refuse(TKNN_E_ARG, "need " + std::to_string(least) + " <= " + name + " < 2^31-1");
+  }
+  // 1 <= k <= limit; above the limit with `code_above` (TKNN_E_UNSUPPORTED where another call or kernel serves that k)
+  void k_up_to(int k, int limit, int code_above) const {
+    if (k < 1) refuse(TKNN_E_ARG, "k must be positive");
+    if (k > limit) refuse(code_above, "k out of range (1 .. " + std::to_string(limit) + ")");
+  }
+};
+
+int failed(int code, const std::string &what) {
+  g_last_error = what;
+  return code;
+}
+
+// runs f; what it throws becomes the call's code and tknnLastError()
+template <typename F>
+int guarded(F &&f) {
+  try {
+    f();
+    return TKNN_OK;
+  } catch (const owlmi::LbvhStateError &e) {
+    return failed(TKNN_E_STATE, e.what);
+  } catch (const owlmi::HipError &e) {
+    return failed(TKNN_E_HIP, e.what);
+  } catch (const owlmi::RoundsExceeded &) {
+    return failed(TKNN_E_ROUNDS, "max_rounds reached with unfinished queries (the reference loops forever here, e.g. n <= k)");
+  } catch (const owlmi::ArgError &e) {
+    return failed(e.code, e.what);
+  } catch (const std::exception &e) {
+    return failed(TKNN_E_HIP, e.what());
+  }
+}
+
+// One call on an engine: a NULL engine is refused before any device is touched, `f(call)` runs on the engine's device.
+template <typename F>
+int api(const char *fn, tknnEngine e, F &&f) {
+  return guarded([&] {
+    const Call c{fn, e};
+    c.need(e, "the engine");
+    DeviceScope scope(e->impl.device());
+    f(c);
+  });
+}
+
+template <typename T>
+void zero(T *info) {
+  if (info) std::memset(info, 0, sizeof(*info));
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *tknnLastError(void) { return g_last_error.c_str(); }
+
+int tknnDeviceCount(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+int tknnCreate(tknnEngine *out) {
+  return guarded([&] {
+    Call{"tknnCreate", nullptr}.need(out, "out");
+    *out = nullptr;
+    int n = 0;
+    OWLMI_HIP(hipGetDeviceCount(&n));
+    if (n <= 0) throw owlmi::HipError{"no HIP device visible: the TrueKNN engine has no CPU fallback"};
+    *out = new tknnEngine_t();
+  });
+}
+
+void tknnDestroy(tknnEngine e) {
+  if (!e) return;
+  try {
+    DeviceScope scope(e->impl.device());
+    delete e;
+  } catch (...) {
+    delete e;
+  }
+}
+
+int tknnBuildIds(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, void *stream) {
+  return api("tknnBuild", e, [&](const Call &c) {
+    c.need(d_xyz, "d_xyz");
+    c.count(n, "n", 1);
+    e->impl.build(d_xyz, d_ids, n, info, (hipStream_t)stream);
+  });
+}
+
+int tknnBuild(tknnEngine e, const float *d_xyz, int64_t n, tknnBuildInfo *info, void *stream) {
+  return tknnBuildIds(e, d_xyz, nullptr, n, info, stream);
+}
+
+int tknnSetHalo(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t m, void *stream) {
+  return api("tknnSetHalo", e, [&](const Call &c) {
+    c.count(m, "m");
+    if (m > 0) c.need(d_xyz, "d_xyz"), c.need(d_ids, "d_ids");
+    c.built();
+    e->impl.set_halo(d_xyz, d_ids, m, (hipStream_t)stream);
+  });
+}
+
+// the boxes of both forms of tknnHaloSelect
+static void need_boxes(const Call &c, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes) {
+  c.require(nboxes >= 0, "nboxes must not be negative");
+  if (nboxes > 0) c.need(d_boxes, "d_boxes"), c.need(d_box_peer, "d_box_peer");
+}
+
+int tknnHaloSelect(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
+                   int64_t *d_counts, const int64_t *d_offsets, float *d_rows, void *stream) {
+  return api("tknnHaloSelect", e, [&](const Call &c) {
+    need_boxes(c, d_boxes, d_box_peer, nboxes);
+    c.require(d_rows || d_counts, "need d_counts (count pass) or d_offsets + d_rows (write pass)");
+    if (d_rows) c.need(d_offsets, "d_offsets");
+    c.built();
+    e->impl.halo_select(d_boxes, d_box_peer, nboxes, npeers, d_counts, d_offsets, d_rows, (hipStream_t)stream);
+  });
+}
+
+int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
+                        const int64_t *d_caps, const int64_t *d_offsets, float *d_rows, int64_t *d_counts, void *stream) {
+  return api("tknnHaloSelectFixed", e, [&](const Call &c) {
+    need_boxes(c, d_boxes, d_box_peer, nboxes);
+    c.need(d_caps, "d_caps"), c.need(d_offsets, "d_offsets"), c.need(d_rows, "d_rows"), c.need(d_counts, "d_counts");
+    c.built();
+    e->impl.halo_select(d_boxes, d_box_peer, nboxes, npeers, d_counts, d_offsets, d_rows, (hipStream_t)stream, d_caps);
+  });
+}
+
+int tknnSolve(tknnEngine e, int k, float start_radius, int kernel, int max_rounds, int32_t *d_idx,
+              float *d_dist, int64_t *d_intersections, tknnNeigh *d_fb, tknnSolveInfo *info, void *stream) {
+  tknnSolveOptions o = {};
+  o.k = k;
+  o.start_radius = start_radius;
+  o.kernel = kernel;
+  o.max_rounds = max_rounds;
+  o.d_idx = d_idx;
+  o.d_dist = d_dist;
+  o.d_intersections = d_intersections;
+  o.d_fb = d_fb;
+  return tknnSolveEx(e, &o, info, stream);
+}
+
+int tknnSolveEx(tknnEngine e, const tknnSolveOptions *options, tknnSolveInfo *info, void *stream) {
+  return api("tknnSolve", e, [&](const Call &c) {
+    const tknnSolveOptions &o = c.record(options);
+    c.built();
+    c.k_up_to(o.k, TKNN_MAX_K, TKNN_E_UNSUPPORTED);
+    c.require((int64_t)o.k < e->impl.size() || o.allow_unfinished, "need n > k (the reference never terminates otherwise)");
+    c.positive(o.start_radius, "start_radius");
+    c.require(o.kernel == TKNN_KERNEL_AUTO || o.kernel == TKNN_KERNEL_LANE || o.kernel == TKNN_KERNEL_WAVE || o.kernel == TKNN_KERNEL_TEAM,
+              "unknown kernel selector");
+    c.require(o.phase >= 0 && o.phase <= 3, "phase must be 0 (all), 1 (interior), 2 (boundary) or 3 (unfinished)");
+    owlmi::SolveArgs sa;
+    sa.k = o.k;
+    sa.start_radius = o.start_radius;
+    sa.max_rounds = owlmi::resolve_max_rounds(o.max_rounds);
+    sa.d_idx = o.d_idx;
+    sa.d_dist = o.d_dist;
+    sa.d_isect = o.d_intersections;
+    sa.d_fb = o.d_fb;
+    sa.d_levels = o.d_levels;
+    sa.allow_unfinished = o.allow_unfinished != 0;
+    sa.phase = o.phase;
+    sa.d_start_radii = o.d_start_radii;
+    zero(info);
+    e->impl.solve(sa, o.kernel, info, (hipStream_t)stream);
+  });
+}
+
+int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_levels, int32_t *d_idx,
+                    float *d_dist, int64_t *repaired, void *stream) {
+  return api("tknnRepairExact", e, [&](const Call &c) {
+    c.need(d_levels, "d_levels"), c.need(d_idx, "d_idx"), c.need(d_dist, "d_dist");
+    c.built();
+    c.k_up_to(k, TKNN_MAX_K_REGISTERS, TKNN_E_ARG);  // (the repair pass keeps its lists in registers)
+    c.positive(start_radius, "start_radius");
+    const int64_t n = e->impl.repair_exact(k, d_levels, d_idx, d_dist, (hipStream_t)stream);
+    if (repaired) *repaired = n;
+  });
+}
+
+int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info, void *stream) {
+  return api("tknnQuery", e, [&](const Call &c) {
+    const tknnQueryOptions &o = c.record(options);
+    if (o.m > 0) c.need(o.d_queries, "d_queries");
+    c.built();
+    c.require(o.k >= 1, "k must be positive");
+    c.require((int64_t)o.k <= e->impl.size(), "need n >= k (no query can finish otherwise)");
+    c.positive(o.start_radius, "start_radius");
+    c.count(o.m, "m");
+    c.require(!o.allow_unfinished || o.d_levels, "allow_unfinished needs d_levels (they say which rows were written)");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the query kernels keep their lists in registers)
+    if (e->impl.has_halo()) c.refuse(TKNN_E_UNSUPPORTED, "a halo tree is set (queries over tiles are not served yet)");
+    zero(info);
+    if (o.m > 0) e->impl.query(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
+               tknnDbscanInfo *info, void *stream) {
+  return api("tknnDbscan", e, [&](const Call &c) {
+    c.need(d_labels, "d_labels");
+    c.built();
+    c.positive(eps, "eps");
+    c.require(min_pts >= 1, "min_pts must be >= 1");
+    e->impl.dbscan(eps, min_pts, d_labels, d_core, d_counts, info, (hipStream_t)stream);
+  });
+}
+
+int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32_t *d_labels, tknnDbscanInfo *info,
+                     void *stream) {
+  return api("tknnDbscanAssign", e, [&](const Call &c) {
+    c.need(d_labels, "d_labels"), c.need(d_core_label, "d_core_label");
+    c.built();
+    c.positive(eps, "eps");
+    e->impl.dbscan(eps, 1, d_labels, nullptr, nullptr, info, (hipStream_t)stream, d_core_label);
+  });
+}
+
+int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream) {
+  return api("tknnDbscanQuery", e, [&](const Call &c) {
+    const tknnDbscanQueryOptions &o = c.record(options);
+    c.need(o.d_core_label, "d_core_label"), c.need(o.d_labels, "d_labels");
+    if (o.m > 0) c.need(o.d_queries, "d_queries");
+    c.built();
+    c.positive(o.eps, "eps");
+    c.count(o.m, "m");
+    zero(info);
+    if (o.m > 0) e->impl.dbscan_query(o.eps, o.d_queries, o.m, o.d_core_label, o.d_labels, o.d_counts, info, (hipStream_t)stream);
+  });
+}
+
+int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusInfo *info, void *stream) {
+  return api("tknnRadiusQuery", e, [&](const Call &c) {
+    const tknnRadiusOptions &o = c.record(options);
+    c.need(o.d_offsets, "d_offsets");
+    if (o.m > 0) c.need(o.d_queries, "d_queries");
+    c.built();
+    c.positive(o.radius, "radius");
+    c.count(o.m, "m");
+    c.require(!o.d_dist || o.d_idx, "d_dist needs d_idx (both NULL: the count pass)");
+    c.require(o.capacity >= 0, "capacity must not be negative");
+    zero(info);
+    if (o.m > 0) {
+      e->impl.radius_query(o, info, (hipStream_t)stream);
+    } else if (!o.d_idx) {  // the count pass of no queries: the one offset
+      OWLMI_HIP(hipMemsetAsync(o.d_offsets, 0, sizeof(int64_t), (hipStream_t)stream));
+      OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+  });
+}
+
+int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusKnnInfo *info, void *stream) {
+  return api("tknnRadiusKnn", e, [&](const Call &c) {
+    const tknnRadiusKnnOptions &o = c.record(options);
+    c.need(o.d_idx, "d_idx");
+    if (o.m > 0) c.need(o.d_queries, "d_queries");
+    c.built();
+    c.require(o.k >= 1, "k must be positive");
+    c.count(o.m, "m");
+    if (!o.d_radii) c.positive(o.radius, "radius (or give d_radii)");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
+    zero(info);
+    if (o.m > 0) e->impl.radius_knn(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
+                   tknnDbscanAutoInfo *info, void *stream) {
+  const int rc = api("tknnDbscanAuto", e, [&](const Call &c) {
+    c.need(d_labels, "d_labels");
+    c.built();
+    c.positive(eps0, "eps0");
+    c.require(min_pts >= 1, "min_pts must be >= 1");
+    c.require(max_noise >= 0.0 && max_noise <= 1.0, "max_noise is a share of the points, 0 .. 1");
+    c.require(max_rounds >= 1, "max_rounds must be >= 1");
+    e->impl.dbscan_auto(eps0, min_pts, max_noise, max_rounds, d_labels, d_core, info, (hipStream_t)stream);
+  });
+  if (rc == TKNN_E_ROUNDS) g_last_error = "tknnDbscanAuto: max_rounds doublings of eps did not bring the noise under the bound";
+  return rc;
+}
+
+int tknnDbscanNoise(tknnEngine e, float eps, int min_pts, uint8_t *d_noise, int64_t *noise_count, void *stream) {
+  return api("tknnDbscanNoise", e, [&](const Call &c) {
+    c.need(d_noise, "d_noise");
+    c.built();
+    c.positive(eps, "eps");
+    c.require(min_pts >= 1, "min_pts must be >= 1");
+    const int64_t count = e->impl.dbscan_noise(eps, min_pts, d_noise, (hipStream_t)stream);
+    if (noise_count) *noise_count = count;
+  });
+}
+
+int tknnSegmentMin(tknnEngine e, const int32_t *d_segment, const int64_t *d_value, int64_t n, int64_t *d_out, void *stream) {
+  return api("tknnSegmentMin", e, [&](const Call &c) {
+    c.require(n >= 0, "n must not be negative");
+    if (n > 0) c.need(d_segment, "d_segment"), c.need(d_value, "d_value"), c.need(d_out, "d_out");
+    owlmi::db_segment_min(d_segment, d_value, n, d_out, (hipStream_t)stream);
+  });
+}
+
+int tknnExportTree(tknnEngine e, void *nodes, int32_t *rope_node, int32_t *rope_leaf, int32_t *prim_id,
+                   void *stream) {
+  return api("tknnExportTree", e, [&](const Call &c) {
+    c.built();
+    e->impl.tree().download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, (hipStream_t)stream);
+  });
+}
+
+int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_paths, void *stream) {
+  return api("tknnExportTreeTables", e, [&](const Call &c) {
+    c.built();
+    e->impl.tree().download_tables(split_owner, block_paths, (hipStream_t)stream);
+  });
+}
+
+int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream) {
+  return api("tknnExportTreeEx", e, [&](const Call &c) {
+    c.need(x, "the export record");
+    c.require(x->which == 0 || x->which == 1, "which must be 0 (own tree) or 1 (halo tree)");
+    c.require(!x->wide_boxes || x->wide_capacity >= 0, "wide_capacity must not be negative");
+    c.built();
+    if (x->which == 1 && !(e->impl.has_halo() && e->impl.halo_tree().built())) c.refuse(TKNN_E_STATE, "no halo tree is set");
+    const owlmi::Lbvh &t = x->which == 1 ? e->impl.halo_tree() : e->impl.tree();
+    static_assert(sizeof(x->wide_count) == sizeof(owlmi::Lbvh::DebugInfo::wide_count), "wide levels");
+    owlmi::Lbvh::DebugInfo d;
+    t.download_debug(&d, x->keys, (LbvhPoint *)x->points, x->row_slot, (LbvhBox *)x->wide_boxes, x->wide_capacity, (hipStream_t)stream);
+    t.download((LbvhNode *)x->nodes, x->rope_node, x->rope_leaf, x->prim_id, (hipStream_t)stream);
+    t.download_tables(x->split_owner, nullptr, (hipStream_t)stream);
+    x->n = t.size();
+    x->curve = d.curve;
+    x->nan_count = d.nan_count;
+    x->wide_levels = d.wide_levels;
+    for (int l = 0; l < LBVH_WIDE_LEVELS; l++) x->wide_count[l] = d.wide_count[l];
+    for (int a = 0; a < 6; a++) x->scene[a] = d.scene[a];
+  });
+}
+
+// the debug entry points need no engine
+
+int tknnDebugBoxTree(const float *d_boxes, int64_t n, const float *d_boxes_refit, int mode, void *nodes, int32_t *rope_node,
+                     int32_t *rope_leaf, int32_t *prim_id, float *sorted_boxes, void *stream) {
+  return guarded([&] {
+    const Call c{"tknnDebugBoxTree", nullptr};
+    c.need(d_boxes, "d_boxes");
+    c.count(n, "n", 1);
+    c.require(mode >= 0 && mode <= 2, "mode must be 0, 1 or 2");
+    const hipStream_t s = (hipStream_t)stream;
+    owlmi::Lbvh tree;
+    if (mode == 0) tree.build_from_boxes((const LbvhBox *)d_boxes, n, s);
+    if (mode == 2) tree.build_from_points(d_boxes, 2 * n, s);
+    if (d_boxes_refit || mode != 0) tree.refit_boxes((const LbvhBox *)(d_boxes_refit ? d_boxes_refit : d_boxes), s);
+    tree.download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, s);
+    if (sorted_boxes) tree.download_boxes((LbvhBox *)sorted_boxes, s);
+    OWLMI_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int tknnDebugThresholds(const float *d_q, const float *d_r, int64_t n, float *d_lo, float *d_hi, void *stream) {
+  return guarded([&] {
+    const Call c{"tknnDebugThresholds", nullptr};
+    c.need(d_q, "d_q"), c.need(d_r, "d_r"), c.need(d_lo, "d_lo"), c.need(d_hi, "d_hi");
+    c.require(n >= 0, "n must not be negative");
+    owlmi::debug_thresholds(d_q, d_r, n, d_lo, d_hi, (hipStream_t)stream);
+    OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
+}  // extern "C"

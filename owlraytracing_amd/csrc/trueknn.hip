@@ -1,6 +1,6 @@
 // trueknn.hip -- the TrueKNN engine behind include/owlknn.h: LBVH build, the per-round "lane"
 // kernel and the exact repair (one query per lane, the stackless rope traversal of lane_walk.h) and
-// the result writers.  The persistent wave-packet kernel lives in trueknn_wave.hip.
+// the result writers.  The persistent wave-packet kernel lives in trueknn_wave.hip, the C ABI's entry points in tknn_api.hip.
 //
 // Reference functions this file replaces (samples/s01-trueknn):
 //   deviceCode.cu:140-153  __raygen__rayGen            -> active test + point query per lane
@@ -613,472 +613,3 @@ void Engine::solve(const SolveArgs &sa, int kernel, tknnSolveInfo *info, hipStre
 }
 
 }  // namespace owlmi
-
-// ------------------------------------------------------------------------------------------
-// C-ABI
-// ------------------------------------------------------------------------------------------
-using owlmi::Engine;
-
-static thread_local std::string g_last_error;
-
-struct tknnEngine_t {
-  Engine impl;
-};
-
-template <typename F>
-static int guarded(F &&f) {
-  try {
-    f();
-    return TKNN_OK;
-  } catch (const owlmi::LbvhStateError &e) {
-    g_last_error = e.what;
-    return TKNN_E_STATE;
-  } catch (const owlmi::HipError &e) {
-    g_last_error = e.what;
-    return TKNN_E_HIP;
-  } catch (const owlmi::RoundsExceeded &) {
-    g_last_error = "max_rounds reached with unfinished queries (the reference loops forever here, e.g. n <= k)";
-    return TKNN_E_ROUNDS;
-  } catch (const owlmi::ArgError &e) {
-    g_last_error = e.what;
-    return e.code;
-  } catch (const std::exception &e) {
-    g_last_error = e.what();
-    return TKNN_E_HIP;
-  }
-}
-
-// Every engine call runs on the device the engine was created on (the caller's current device at
-// tknnCreate), whatever device is current in the calling thread now; the caller's choice is restored.
-struct DeviceScope {
-  int prev = -1, want;
-  explicit DeviceScope(int device) : want(device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != want && hipSetDevice(want) != hipSuccess) throw owlmi::HipError{"hipSetDevice(engine's device) failed"};
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-  }
-};
-
-template <typename F>
-static int guarded_on(tknnEngine e, F &&f) {
-  return guarded([&] {
-    DeviceScope scope(e->impl.device());
-    f();
-  });
-}
-
-extern "C" {
-
-const char *tknnLastError(void) { return g_last_error.c_str(); }
-
-int tknnDeviceCount(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int tknnCreate(tknnEngine *out) {
-  if (!out) {
-    g_last_error = "tknnCreate: out is NULL";
-    return TKNN_E_ARG;
-  }
-  *out = nullptr;
-  return guarded([&] {
-    int n = 0;
-    OWLMI_HIP(hipGetDeviceCount(&n));
-    if (n <= 0) throw owlmi::HipError{"no HIP device visible: the TrueKNN engine has no CPU fallback"};
-    *out = new tknnEngine_t();
-  });
-}
-
-void tknnDestroy(tknnEngine e) {
-  if (!e) return;
-  try {
-    DeviceScope scope(e->impl.device());
-    delete e;
-  } catch (...) {
-    delete e;
-  }
-}
-
-int tknnBuildIds(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info,
-                 void *stream) {
-  if (!e || !d_xyz || n <= 0 || n >= 0x7fffffffLL) {
-    g_last_error = "tknnBuild: need an engine, a device pointer and 0 < n < 2^31-1";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] { e->impl.build(d_xyz, d_ids, n, info, (hipStream_t)stream); });
-}
-
-int tknnBuild(tknnEngine e, const float *d_xyz, int64_t n, tknnBuildInfo *info, void *stream) {
-  return tknnBuildIds(e, d_xyz, nullptr, n, info, stream);
-}
-
-int tknnSetHalo(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t m, void *stream) {
-  if (!e || m < 0 || m >= 0x7fffffffLL || (m > 0 && (!d_xyz || !d_ids))) {
-    g_last_error = "tknnSetHalo: need an engine and, for m > 0, device pointers to points and ids";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnSetHalo: call tknnBuild first"};
-    e->impl.set_halo(d_xyz, d_ids, m, (hipStream_t)stream);
-  });
-}
-
-int tknnHaloSelect(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
-                   int64_t *d_counts, const int64_t *d_offsets, float *d_rows, void *stream) {
-  if (!e || nboxes < 0 || (nboxes > 0 && (!d_boxes || !d_box_peer)) || (!d_rows && !d_counts) || (d_rows && !d_offsets)) {
-    g_last_error = "tknnHaloSelect: need boxes with their peers, and counts (count pass) or offsets + rows (write pass)";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnHaloSelect: call tknnBuild first"};
-    e->impl.halo_select(d_boxes, d_box_peer, nboxes, npeers, d_counts, d_offsets, d_rows, (hipStream_t)stream);
-  });
-}
-
-int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
-                        const int64_t *d_caps, const int64_t *d_offsets, float *d_rows, int64_t *d_counts, void *stream) {
-  if (!e || nboxes < 0 || (nboxes > 0 && (!d_boxes || !d_box_peer)) || !d_caps || !d_offsets || !d_rows || !d_counts) {
-    g_last_error = "tknnHaloSelectFixed: need boxes with their peers, capacities, offsets, the row buffer and a place for the counts";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnHaloSelectFixed: call tknnBuild first"};
-    e->impl.halo_select(d_boxes, d_box_peer, nboxes, npeers, d_counts, d_offsets, d_rows, (hipStream_t)stream, d_caps);
-  });
-}
-
-int tknnSolve(tknnEngine e, int k, float start_radius, int kernel, int max_rounds, int32_t *d_idx,
-              float *d_dist, int64_t *d_intersections, tknnNeigh *d_fb, tknnSolveInfo *info, void *stream) {
-  tknnSolveOptions o;
-  std::memset(&o, 0, sizeof o);
-  o.k = k;
-  o.start_radius = start_radius;
-  o.kernel = kernel;
-  o.max_rounds = max_rounds;
-  o.d_idx = d_idx;
-  o.d_dist = d_dist;
-  o.d_intersections = d_intersections;
-  o.d_fb = d_fb;
-  return tknnSolveEx(e, &o, info, stream);
-}
-
-int tknnSolveEx(tknnEngine e, const tknnSolveOptions *options, tknnSolveInfo *info, void *stream) {
-  if (!e || !options) {
-    g_last_error = "tknnSolve: engine or options is NULL";
-    return TKNN_E_ARG;
-  }
-  const int k = options->k, kernel = options->kernel, max_rounds = options->max_rounds;
-  const float start_radius = options->start_radius;
-  int32_t *d_idx = options->d_idx;
-  float *d_dist = options->d_dist;
-  int64_t *d_intersections = options->d_intersections;
-  tknnNeigh *d_fb = options->d_fb;
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnSolve: call tknnBuild first"};
-    if (k <= 0) throw owlmi::ArgError{TKNN_E_ARG, "tknnSolve: k must be positive"};
-    if (k > TKNN_MAX_K) throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnSolve: k exceeds TKNN_MAX_K"};
-    if ((int64_t)k >= e->impl.size() && !options->allow_unfinished)
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnSolve: need n > k (the reference never terminates otherwise)"};
-    if (!(start_radius > 0.f) || !std::isfinite(start_radius))
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnSolve: start_radius must be finite and > 0"};
-    if (kernel != TKNN_KERNEL_AUTO && kernel != TKNN_KERNEL_LANE && kernel != TKNN_KERNEL_WAVE &&
-        kernel != TKNN_KERNEL_TEAM)
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnSolve: unknown kernel selector"};
-    owlmi::SolveArgs sa;
-    sa.k = k;
-    sa.start_radius = start_radius;
-    sa.max_rounds = max_rounds > 0 ? std::min(max_rounds, 127) : 64;  // (127: more doublings than fp32 has binades for a radius; the tie flags keep the level in seven bits)
-    sa.d_idx = d_idx;
-    sa.d_dist = d_dist;
-    sa.d_isect = d_intersections;
-    sa.d_fb = d_fb;
-    sa.d_levels = options->d_levels;
-    sa.allow_unfinished = options->allow_unfinished != 0;
-    sa.phase = options->phase;
-    sa.d_start_radii = options->d_start_radii;
-    if (sa.phase < 0 || sa.phase > 3) throw owlmi::ArgError{TKNN_E_ARG, "tknnSolveEx: phase must be 0 (all), 1 (interior), 2 (boundary) or 3 (unfinished)"};
-    if (info) std::memset(info, 0, sizeof(*info));
-    e->impl.solve(sa, kernel, info, (hipStream_t)stream);
-  });
-}
-
-int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_levels, int32_t *d_idx,
-                    float *d_dist, int64_t *repaired, void *stream) {
-  if (!e || !d_levels || !d_idx || !d_dist) {
-    g_last_error = "tknnRepairExact: engine, levels, idx and dist are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRepairExact: call tknnBuild first"};
-    if (k <= 0 || k > TKNN_MAX_K_REGISTERS) throw owlmi::ArgError{TKNN_E_ARG, "tknnRepairExact: k out of range (1 .. 64: the repair pass keeps its lists in registers)"};
-    if (!(start_radius > 0.f) || !std::isfinite(start_radius))
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnRepairExact: start_radius must be finite and > 0"};
-    const int64_t n = e->impl.repair_exact(k, d_levels, d_idx, d_dist, (hipStream_t)stream);
-    if (repaired) *repaired = n;
-  });
-}
-
-int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info, void *stream) {
-  if (!e || !options || (options->m > 0 && !options->d_queries)) {
-    g_last_error = "tknnQuery: engine, options and (for m > 0) the queries are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    const tknnQueryOptions &o = *options;
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnQuery: call tknnBuild first"};
-    if (o.k < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: k must be positive"};
-    if ((int64_t)o.k > e->impl.size()) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: need n >= k (no query can finish otherwise)"};
-    if (!(o.start_radius > 0.f) || !std::isfinite(o.start_radius))
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: start_radius must be finite and > 0"};
-    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: need 0 <= m < 2^31-1"};
-    if (o.allow_unfinished && !o.d_levels)
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnQuery: allow_unfinished needs d_levels (they say which rows were written)"};
-    if (o.k > TKNN_MAX_K_REGISTERS)
-      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnQuery: k out of range (1 .. 64: the query kernels keep their lists in registers)"};
-    if (e->impl.has_halo())
-      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnQuery: a halo tree is set (queries over tiles are not served yet)"};
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (o.m == 0) return;
-    owlmi::QueryArgs qa;
-    qa.d_queries = o.d_queries;
-    qa.m = o.m;
-    qa.k = o.k;
-    qa.start_radius = o.start_radius;
-    qa.max_rounds = o.max_rounds > 0 ? std::min(o.max_rounds, 127) : 64;  // as tknnSolveEx
-    qa.allow_unfinished = o.allow_unfinished != 0;
-    qa.exact = o.exact != 0;
-    qa.d_idx = o.d_idx;
-    qa.d_dist = o.d_dist;
-    qa.d_isect = o.d_intersections;
-    qa.d_levels = o.d_levels;
-    e->impl.query(qa, info, (hipStream_t)stream);
-  });
-}
-
-int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
-               tknnDbscanInfo *info, void *stream) {
-  if (!e || !d_labels) {
-    g_last_error = "tknnDbscan: engine or labels pointer is NULL";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscan: call tknnBuild first"};
-    if (!(eps > 0.f) || !std::isfinite(eps)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscan: eps must be finite and > 0"};
-    if (min_pts < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscan: min_pts must be >= 1"};
-    e->impl.dbscan(eps, min_pts, d_labels, d_core, d_counts, info, (hipStream_t)stream);
-  });
-}
-
-int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32_t *d_labels, tknnDbscanInfo *info,
-                     void *stream) {
-  if (!e || !d_labels || !d_core_label) {
-    g_last_error = "tknnDbscanAssign: engine, core labels or labels pointer is NULL";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscanAssign: call tknnBuild first"};
-    if (!(eps > 0.f) || !std::isfinite(eps)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanAssign: eps must be finite and > 0"};
-    e->impl.dbscan(eps, 1, d_labels, nullptr, nullptr, info, (hipStream_t)stream, d_core_label);
-  });
-}
-
-int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream) {
-  if (!e || !options || !options->d_core_label || !options->d_labels || (options->m > 0 && !options->d_queries)) {
-    g_last_error = "tknnDbscanQuery: engine, options, core labels, labels and (for m > 0) the queries are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    const tknnDbscanQueryOptions &o = *options;
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscanQuery: call tknnBuild first"};
-    if (!(o.eps > 0.f) || !std::isfinite(o.eps)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanQuery: eps must be finite and > 0"};
-    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanQuery: need 0 <= m < 2^31-1"};
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (o.m == 0) return;
-    e->impl.dbscan_query(o.eps, o.d_queries, o.m, o.d_core_label, o.d_labels, o.d_counts, info, (hipStream_t)stream);
-  });
-}
-
-int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusInfo *info, void *stream) {
-  if (!e || !options || !options->d_offsets || (options->m > 0 && !options->d_queries)) {
-    g_last_error = "tknnRadiusQuery: engine, options, d_offsets and (for m > 0) the queries are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    const tknnRadiusOptions &o = *options;
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRadiusQuery: call tknnBuild first"};
-    if (!(o.radius > 0.f) || !std::isfinite(o.radius)) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: radius must be finite and > 0"};
-    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: need 0 <= m < 2^31-1"};
-    if (o.d_dist && !o.d_idx) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: d_dist needs d_idx (both NULL: the count pass)"};
-    if (o.capacity < 0) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusQuery: capacity must not be negative"};
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (o.m == 0) {
-      if (!o.d_idx) {
-        OWLMI_HIP(hipMemsetAsync(o.d_offsets, 0, sizeof(int64_t), (hipStream_t)stream));
-        OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
-      }
-      return;
-    }
-    owlmi::RadiusArgs ra;
-    ra.d_queries = o.d_queries;
-    ra.m = o.m;
-    ra.radius = o.radius;
-    ra.sort = o.sort != 0;
-    ra.d_offsets = o.d_offsets;
-    ra.d_idx = o.d_idx;
-    ra.d_dist = o.d_dist;
-    ra.capacity = o.capacity;
-    e->impl.radius_query(ra, info, (hipStream_t)stream);
-  });
-}
-
-int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusKnnInfo *info, void *stream) {
-  if (!e || !options || !options->d_idx || (options->m > 0 && !options->d_queries)) {
-    g_last_error = "tknnRadiusKnn: engine, options, d_idx and (for m > 0) the queries are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    const tknnRadiusKnnOptions &o = *options;
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnRadiusKnn: call tknnBuild first"};
-    if (o.k < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: k must be positive"};
-    if (o.m < 0 || o.m >= 0x7fffffffLL) throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: need 0 <= m < 2^31-1"};
-    if (!o.d_radii && (!(o.radius > 0.f) || !std::isfinite(o.radius)))
-      throw owlmi::ArgError{TKNN_E_ARG, "tknnRadiusKnn: radius must be finite and > 0 (or give d_radii)"};
-    if (o.k > TKNN_MAX_K_REGISTERS)
-      throw owlmi::ArgError{TKNN_E_UNSUPPORTED, "tknnRadiusKnn: k out of range (1 .. 64: the kernels keep their lists in registers)"};
-    if (info) std::memset(info, 0, sizeof(*info));
-    if (o.m == 0) return;
-    owlmi::RadiusKnnArgs ra;
-    ra.d_queries = o.d_queries;
-    ra.m = o.m;
-    ra.k = o.k;
-    ra.radius = o.radius;
-    ra.d_radii = o.d_radii;
-    ra.d_skip_ids = o.d_skip_ids;
-    ra.d_idx = o.d_idx;
-    ra.d_dist = o.d_dist;
-    ra.d_counts = o.d_counts;
-    e->impl.radius_knn(ra, info, (hipStream_t)stream);
-  });
-}
-
-int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
-                   tknnDbscanAutoInfo *info, void *stream) {
-  if (!e || !d_labels) {
-    g_last_error = "tknnDbscanAuto: engine or labels pointer is NULL";
-    return TKNN_E_ARG;
-  }
-  const int rc = guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscanAuto: call tknnBuild first"};
-    if (!(eps0 > 0.f) || !std::isfinite(eps0)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanAuto: eps0 must be finite and > 0"};
-    if (min_pts < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanAuto: min_pts must be >= 1"};
-    if (!(max_noise >= 0.0) || !(max_noise <= 1.0)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanAuto: max_noise is a share of the points, 0 .. 1"};
-    if (max_rounds < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanAuto: max_rounds must be >= 1"};
-    e->impl.dbscan_auto(eps0, min_pts, max_noise, max_rounds, d_labels, d_core, info, (hipStream_t)stream);
-  });
-  if (rc == TKNN_E_ROUNDS) g_last_error = "tknnDbscanAuto: max_rounds doublings of eps did not bring the noise under the bound";
-  return rc;
-}
-
-int tknnDbscanNoise(tknnEngine e, float eps, int min_pts, uint8_t *d_noise, int64_t *noise_count, void *stream) {
-  if (!e || !d_noise) {
-    g_last_error = "tknnDbscanNoise: engine or flag pointer is NULL";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnDbscanNoise: call tknnBuild first"};
-    if (!(eps > 0.f) || !std::isfinite(eps)) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanNoise: eps must be finite and > 0"};
-    if (min_pts < 1) throw owlmi::ArgError{TKNN_E_ARG, "tknnDbscanNoise: min_pts must be >= 1"};
-    const int64_t count = e->impl.dbscan_noise(eps, min_pts, d_noise, (hipStream_t)stream);
-    if (noise_count) *noise_count = count;
-  });
-}
-
-int tknnSegmentMin(tknnEngine e, const int32_t *d_segment, const int64_t *d_value, int64_t n, int64_t *d_out, void *stream) {
-  if (!e || n < 0 || (n > 0 && (!d_segment || !d_value || !d_out))) {
-    g_last_error = "tknnSegmentMin: engine, segments, values and the output are required";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] { owlmi::db_segment_min(d_segment, d_value, n, d_out, (hipStream_t)stream); });
-}
-
-int tknnExportTree(tknnEngine e, void *nodes, int32_t *rope_node, int32_t *rope_leaf, int32_t *prim_id,
-                   void *stream) {
-  if (!e) {
-    g_last_error = "tknnExportTree: engine is NULL";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTree: call tknnBuild first"};
-    e->impl.tree().download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, (hipStream_t)stream);
-  });
-}
-
-int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_paths, void *stream) {
-  if (!e) {
-    g_last_error = "tknnExportTreeTables: engine is NULL";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeTables: call tknnBuild first"};
-    e->impl.tree().download_tables(split_owner, block_paths, (hipStream_t)stream);
-  });
-}
-
-int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream) {
-  if (!e || !x || (x->which != 0 && x->which != 1) || (x->wide_boxes && x->wide_capacity < 0)) {
-    g_last_error = "tknnExportTreeEx: need an engine, the export record and which = 0 (own tree) or 1 (halo tree)";
-    return TKNN_E_ARG;
-  }
-  return guarded_on(e, [&] {
-    if (!e->impl.built()) throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeEx: call tknnBuild first"};
-    if (x->which == 1 && !(e->impl.has_halo() && e->impl.halo_tree().built()))
-      throw owlmi::ArgError{TKNN_E_STATE, "tknnExportTreeEx: no halo tree is set"};
-    const owlmi::Lbvh &t = x->which == 1 ? e->impl.halo_tree() : e->impl.tree();
-    static_assert(sizeof(x->wide_count) == sizeof(owlmi::Lbvh::DebugInfo::wide_count), "wide levels");
-    owlmi::Lbvh::DebugInfo d;
-    t.download_debug(&d, x->keys, (LbvhPoint *)x->points, x->row_slot, (LbvhBox *)x->wide_boxes, x->wide_capacity, (hipStream_t)stream);
-    t.download((LbvhNode *)x->nodes, x->rope_node, x->rope_leaf, x->prim_id, (hipStream_t)stream);
-    t.download_tables(x->split_owner, nullptr, (hipStream_t)stream);
-    x->n = t.size();
-    x->curve = d.curve;
-    x->nan_count = d.nan_count;
-    x->wide_levels = d.wide_levels;
-    for (int l = 0; l < LBVH_WIDE_LEVELS; l++) x->wide_count[l] = d.wide_count[l];
-    for (int a = 0; a < 6; a++) x->scene[a] = d.scene[a];
-  });
-}
-
-int tknnDebugBoxTree(const float *d_boxes, int64_t n, const float *d_boxes_refit, int mode, void *nodes, int32_t *rope_node,
-                     int32_t *rope_leaf, int32_t *prim_id, float *sorted_boxes, void *stream) {
-  if (!d_boxes || n <= 0 || n >= 0x7fffffffLL || mode < 0 || mode > 2) {
-    g_last_error = "tknnDebugBoxTree: need device boxes, 0 < n < 2^31-1 and mode 0, 1 or 2";
-    return TKNN_E_ARG;
-  }
-  return guarded([&] {
-    const hipStream_t s = (hipStream_t)stream;
-    owlmi::Lbvh tree;
-    if (mode == 0) tree.build_from_boxes((const LbvhBox *)d_boxes, n, s);
-    if (mode == 2) tree.build_from_points(d_boxes, 2 * n, s);
-    if (d_boxes_refit || mode != 0) tree.refit_boxes((const LbvhBox *)(d_boxes_refit ? d_boxes_refit : d_boxes), s);
-    tree.download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, s);
-    if (sorted_boxes) tree.download_boxes((LbvhBox *)sorted_boxes, s);
-    OWLMI_HIP(hipStreamSynchronize(s));
-  });
-}
-
-int tknnDebugThresholds(const float *d_q, const float *d_r, int64_t n, float *d_lo, float *d_hi, void *stream) {
-  if (!d_q || !d_r || !d_lo || !d_hi || n < 0) {
-    g_last_error = "tknnDebugThresholds: null pointer";
-    return TKNN_E_ARG;
-  }
-  return guarded([&] {
-    owlmi::debug_thresholds(d_q, d_r, n, d_lo, d_hi, (hipStream_t)stream);
-    OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
-  });
-}
-
-}  // extern "C"

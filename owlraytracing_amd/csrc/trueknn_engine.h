@@ -34,45 +34,9 @@ struct SolveArgs {
   int phase = 0;  // tknnSolveOptions.phase: 0 every query, 1 interior queries in the own tree only, 2 boundary queries
 };
 
-// tknnQueryOptions as the engine takes it (max_rounds already resolved)
-struct QueryArgs {
-  const float *d_queries = nullptr;
-  int64_t m = 0;
-  int k = 0;
-  float start_radius = 0;
-  int max_rounds = 64;
-  bool allow_unfinished = false;
-  bool exact = false;
-  int32_t *d_idx = nullptr;
-  float *d_dist = nullptr;
-  int64_t *d_isect = nullptr;
-  int32_t *d_levels = nullptr;
-};
-
-// tknnRadiusOptions as the engine takes it (d_idx == nullptr: the count pass)
-struct RadiusArgs {
-  const float *d_queries = nullptr;
-  int64_t m = 0;
-  float radius = 0;
-  bool sort = true;
-  int64_t *d_offsets = nullptr;
-  int32_t *d_idx = nullptr;
-  float *d_dist = nullptr;
-  int64_t capacity = 0;
-};
-
-// tknnRadiusKnnOptions as the engine takes it
-struct RadiusKnnArgs {
-  const float *d_queries = nullptr;
-  int64_t m = 0;
-  int k = 0;
-  float radius = 0;
-  const float *d_radii = nullptr;
-  const int32_t *d_skip_ids = nullptr;
-  int32_t *d_idx = nullptr;
-  float *d_dist = nullptr;
-  int32_t *d_counts = nullptr;
-};
+// tknnSolveOptions.max_rounds and tknnQueryOptions.max_rounds as the solves take them: 64 where the caller gives none, and
+// at most 127 (more doublings than fp32 has binades for a radius; the tie flags keep the level in seven bits)
+inline int resolve_max_rounds(int asked) { return asked > 0 ? (asked < 127 ? asked : 127) : 64; }
 
 template <int... C>
 struct CapacityTable {
@@ -168,12 +132,13 @@ class Engine {
   void db_read_stats(hipStream_t s);
   void dbscan_auto(float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, hipStream_t s);
+  // The three calls below take the caller's options record as tknn_api.hip has validated it (m > 0 among the rest).
   // trueknn_query.hip: TrueKNN rows for m points that are not in the tree (tknnQuery); per-slot solve state is not touched
-  void query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s);
+  void query(const tknnQueryOptions &o, tknnSolveInfo *info, hipStream_t s);
   // radius_query.hip: the points within a radius of m points that are not in the tree, as CSR rows (tknnRadiusQuery); m > 0
-  void radius_query(const RadiusArgs &ra, tknnRadiusInfo *info, hipStream_t s);
+  void radius_query(const tknnRadiusOptions &o, tknnRadiusInfo *info, hipStream_t s);
   // radius_knn.hip: at most k nearest points within a radius of m points that are not in the tree, as dense rows (tknnRadiusKnn); m > 0
-  void radius_knn(const RadiusKnnArgs &ra, tknnRadiusKnnInfo *info, hipStream_t s);
+  void radius_knn(const tknnRadiusKnnOptions &o, tknnRadiusKnnInfo *info, hipStream_t s);
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }

@@ -359,13 +359,13 @@ static void query_pass(QueryKernelArgs &a, int cu_count, unsigned long long *h_w
   OWLMI_HIP(hipEventRecord(after_lane, s));
 }
 
-void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
-  const int64_t m = qa.m;
-  const int k = qa.k;
+void Engine::query(const tknnQueryOptions &o, tknnSolveInfo *info, hipStream_t s) {
+  const int64_t m = o.m;
+  const int k = o.k;
   // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | levels | distances | sort space
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t sort_bytes = query_order_sort_bytes(m, s);
-  const bool own_levels = qa.d_levels == nullptr, own_dist = qa.exact && qa.d_dist == nullptr;
+  const bool own_levels = o.d_levels == nullptr, own_dist = o.exact != 0 && o.d_dist == nullptr;
   const size_t words_b = align(kWsWords * sizeof(unsigned long long)), col_b = align((size_t)m * sizeof(uint32_t)),
                dist_b = own_dist ? align((size_t)m * k * sizeof(float)) : 0;
   char *ws = (char *)workspace(words_b + 6 * col_b + dist_b + align(sort_bytes));
@@ -373,24 +373,24 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   uint32_t *codes = (uint32_t *)(ws + words_b), *codes_alt = (uint32_t *)(ws + words_b + col_b), *order_in = (uint32_t *)(ws + words_b + 2 * col_b),
            *order = (uint32_t *)(ws + words_b + 3 * col_b);
   int32_t *redo = (int32_t *)(ws + words_b + 4 * col_b);
-  int32_t *levels = own_levels ? (int32_t *)(ws + words_b + 5 * col_b) : qa.d_levels;
-  float *dist = own_dist ? (float *)(ws + words_b + 6 * col_b) : qa.d_dist;
+  int32_t *levels = own_levels ? (int32_t *)(ws + words_b + 5 * col_b) : o.d_levels;
+  float *dist = own_dist ? (float *)(ws + words_b + 6 * col_b) : o.d_dist;
   void *sort_tmp = ws + words_b + 6 * col_b + dist_b;
 
   QueryKernelArgs a;
   std::memset(&a, 0, sizeof a);
   a.bvh = bvh_.view();
   a.wide = bvh_.wide_view();
-  a.queries = qa.d_queries;
+  a.queries = o.d_queries;
   a.order = order;
   a.m = (int32_t)m;
-  a.start_radius = qa.start_radius;
+  a.start_radius = o.start_radius;
   a.k = k;
-  a.max_rounds = qa.max_rounds;
+  a.max_rounds = resolve_max_rounds(o.max_rounds);
   if (const char *e = getenv("TKNN_QUERY_FORCE_FALLBACK")) a.force_redo = atoi(e) != 0;
-  a.out_idx = qa.d_idx;
+  a.out_idx = o.d_idx;
   a.out_dist = dist;
-  a.out_isect = qa.d_isect;
+  a.out_isect = o.d_intersections;
   a.levels = levels;
   a.redo = redo;
   a.ws = d_words;
@@ -399,7 +399,7 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   OWLMI_HIP(hipMemsetAsync(levels, 0xff, (size_t)m * sizeof(int32_t), s));
   reset_stat_stripes(s);
-  query_order(qa.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
+  query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   unsigned long long failed = 0, tied = 0, failed_exact = 0, tied_exact = 0;
   query_pass(a, cu_count_, h_counters_, ev_c_, ev_d_, failed, tied, s);
@@ -407,7 +407,7 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   OWLMI_HIP(hipStreamSynchronize(s));
   KernelStats st = fold_stat_stripes(false);
   st.handed_over = failed;
-  if (qa.exact && !(st.unfinished && !qa.allow_unfinished)) {
+  if (o.exact != 0 && !(st.unfinished && o.allow_unfinished == 0)) {
     a.exact = 1;
     query_pass(a, cu_count_, h_counters_, ev_e_, ev_f_, failed_exact, tied_exact, s);
     OWLMI_HIP(hipStreamSynchronize(s));
@@ -421,12 +421,12 @@ void Engine::query(const QueryArgs &qa, tknnSolveInfo *info, hipStream_t s) {
   OWLMI_HIP(hipEventElapsedTime(&walk_ms, ev_b_, ev_c_));
   OWLMI_HIP(hipEventElapsedTime(&lane_ms, ev_c_, ev_d_));
   if (info) {
-    *info = solve_info(st, qa.start_radius, TKNN_KERNEL_QUERY, 16 * query_nreg(k), total_ms);
+    *info = solve_info(st, o.start_radius, TKNN_KERNEL_QUERY, 16 * query_nreg(k), total_ms);
     info->dominant_kernel_ms = walk_ms;  // the walk over the sorted queries; solve_ms also holds the order, the lane pass and the exact pass
     info->tie_rows = (int64_t)tied;
     info->tie_ms = lane_ms;
   }
-  if (st.unfinished && !qa.allow_unfinished) throw RoundsExceeded{};
+  if (st.unfinished && o.allow_unfinished == 0) throw RoundsExceeded{};
 }
 
 }  // namespace owlmi

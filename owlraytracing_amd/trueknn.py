@@ -15,6 +15,14 @@ from .datasets import pad_to_3d
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
 
 
+def _address(t, spare=None):
+    """What a call is given for the optional tensor ``t``: NULL for None, its address, or -- an empty tensor has no
+    address -- that of ``spare`` (with m = 0 a query call is a no-op that still checks its arguments)."""
+    if t is None:
+        return None
+    return t.data_ptr() if t.numel() > 0 else _address(spare)
+
+
 class TrueKNN:
     """One engine on one GPU.  ``points`` may be a numpy array (n,2|3) or a CUDA float32 tensor (n,3)."""
 
@@ -66,6 +74,37 @@ class TrueKNN:
         if ids.dtype != torch.int32 or ids.dim() != 1 or ids.shape[0] != n or not ids.is_cuda:
             raise ValueError("ids must be int32 (n,) on the GPU")
         return ids.contiguous()
+
+    def _queries(self, queries, who):
+        """The ``queries`` of the query call ``who`` as the library takes them: a contiguous float32 (m,3) tensor on the
+        engine's device; a numpy array (m,2|3) is padded and uploaded."""
+        torch = self._torch
+        if isinstance(queries, np.ndarray):
+            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
+                raise ValueError("%s: queries must be (m,2) or (m,3), got %s" % (who, queries.shape))
+            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
+        if not isinstance(queries, torch.Tensor):
+            raise ValueError("%s: queries must be a numpy array or a torch tensor" % who)
+        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("%s: queries must be float32 (m,3), got %s %s" % (who, queries.dtype, tuple(queries.shape)))
+        if queries.device != self.device:
+            raise ValueError("%s: queries are on %s, the engine on %s" % (who, queries.device, self.device))
+        if not queries.is_contiguous():
+            raise ValueError("%s: queries must be contiguous (packed fp32 triples)" % who)
+        return queries
+
+    def _written_in_place(self, who, what, t, shape, dtype):
+        """``t`` (``what`` in the messages of ``who``) is a contiguous tensor of that shape and dtype on the engine's device:
+        the library writes it through its address."""
+        torch = self._torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s must be a tensor" % (who, what))
+        if tuple(t.shape) != shape or t.dtype != dtype:
+            raise ValueError("%s: %s must be %s %s, got %s %s" % (who, what, dtype, shape, t.dtype, tuple(t.shape)))
+        if t.device != self.device:
+            raise ValueError("%s: %s is on %s, the engine on %s" % (who, what, t.device, self.device))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s must be contiguous (it is written in place)" % (who, what))
 
     def build(self, points, ids=None):
         """LBVH over the points.  ``ids`` (optional int32) are the identities reported in neighbour
@@ -214,15 +253,7 @@ class TrueKNN:
         if "levels" not in result or result["levels"] is None:
             raise ValueError("repair_exact needs the levels of the solve (solve(..., want_levels=True))")
         for name, shape, dtype in (("idx", (n, k), torch.int32), ("dist", (n, k), torch.float32), ("levels", (n,), torch.int32)):
-            t = result.get(name)
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("repair_exact: result[%r] must be a tensor" % name)
-            if tuple(t.shape) != shape or t.dtype != dtype:
-                raise ValueError("repair_exact: result[%r] must be %s %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
-            if t.device != self.device:
-                raise ValueError("repair_exact: result[%r] is on %s, the engine on %s" % (name, t.device, self.device))
-            if not t.is_contiguous():
-                raise ValueError("repair_exact: result[%r] must be contiguous (it is written in place)" % name)
+            self._written_in_place("repair_exact", "result[%r]" % name, result.get(name), shape, dtype)
         n_fixed = ctypes.c_int64(0)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.tknnRepairExact(
@@ -240,18 +271,7 @@ class TrueKNN:
         in (dist, index) order.  ``out`` may carry preallocated contiguous tensors of those names."""
         torch = self._torch
         k = int(k)
-        if isinstance(queries, np.ndarray):
-            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
-                raise ValueError("query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
-            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
-        if not isinstance(queries, torch.Tensor):
-            raise ValueError("query: queries must be a numpy array or a torch tensor")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
-            raise ValueError("query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
-        if queries.device != self.device:
-            raise ValueError("query: queries are on %s, the engine on %s" % (queries.device, self.device))
-        if not queries.is_contiguous():
-            raise ValueError("query: queries must be contiguous (packed fp32 triples)")
+        queries = self._queries(queries, "query")
         m = int(queries.shape[0])
         out = dict(out or {})
         shapes = {"idx": ((m, k), torch.int32), "dist": ((m, k), torch.float32), "intersections": ((m,), torch.int64),
@@ -259,15 +279,7 @@ class TrueKNN:
         for name, t in out.items():
             if name not in shapes:
                 raise ValueError("query: out[%r] is not an output of query" % name)
-            shape, dtype = shapes[name]
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("query: out[%r] must be a tensor" % name)
-            if tuple(t.shape) != shape or t.dtype != dtype:
-                raise ValueError("query: out[%r] must be %s %s, got %s %s" % (name, dtype, shape, t.dtype, tuple(t.shape)))
-            if t.device != self.device:
-                raise ValueError("query: out[%r] is on %s, the engine on %s" % (name, t.device, self.device))
-            if not t.is_contiguous():
-                raise ValueError("query: out[%r] must be contiguous (it is written in place)" % name)
+            self._written_in_place("query", "out[%r]" % name, t, *shapes[name])
         with torch.cuda.device(self.device):
             names = ["idx", "dist", "intersections"] + (["levels"] if want_levels or allow_unfinished else [])
             for name in names:
@@ -277,12 +289,10 @@ class TrueKNN:
             opt = _lib.QueryOptions()
             opt.m, opt.k, opt.start_radius = m, k, float(start_radius)
             opt.max_rounds, opt.allow_unfinished, opt.exact = int(max_rounds), int(bool(allow_unfinished)), int(bool(exact))
-            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
             spare = torch.empty((1,), dtype=torch.int64, device=self.device) if m == 0 else None
-            opt.d_queries = queries.data_ptr() if m > 0 else None
+            opt.d_queries = _address(queries)
             for field, name in (("d_idx", "idx"), ("d_dist", "dist"), ("d_intersections", "intersections"), ("d_levels", "levels")):
-                t = out.get(name)
-                setattr(opt, field, None if t is None else (t.data_ptr() if t.numel() > 0 else spare.data_ptr() if spare is not None else None))
+                setattr(opt, field, _address(out.get(name), spare))
             info = _lib.SolveInfo()
             launch_on = self._stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
             _lib.check(self._lib.tknnQuery(self._h, ctypes.byref(opt), ctypes.byref(info), launch_on))
@@ -357,18 +367,7 @@ class TrueKNN:
         core with that label, < 0: not core, as ``dbscan_assign`` takes it).
         Returns dict(labels (m,) int32, [counts (m,) int32], info)."""
         torch = self._torch
-        if isinstance(queries, np.ndarray):
-            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
-                raise ValueError("dbscan_query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
-            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
-        if not isinstance(queries, torch.Tensor):
-            raise ValueError("dbscan_query: queries must be a numpy array or a torch tensor")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
-            raise ValueError("dbscan_query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
-        if queries.device != self.device:
-            raise ValueError("dbscan_query: queries are on %s, the engine on %s" % (queries.device, self.device))
-        if not queries.is_contiguous():
-            raise ValueError("dbscan_query: queries must be contiguous (packed fp32 triples)")
+        queries = self._queries(queries, "dbscan_query")
         m = int(queries.shape[0])
         with torch.cuda.device(self.device):
             core_label = torch.as_tensor(labels, dtype=torch.int32, device=self.device)
@@ -383,14 +382,13 @@ class TrueKNN:
             out = {"labels": torch.empty((m,), dtype=torch.int32, device=self.device)}
             if want_counts:
                 out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
-            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
             spare = torch.empty((1,), dtype=torch.int32, device=self.device) if m == 0 else None
             opt = _lib.DbscanQueryOptions()
             opt.m, opt.eps = m, float(eps)
-            opt.d_queries = queries.data_ptr() if m > 0 else None
-            opt.d_core_label = core_label.data_ptr() if self.n > 0 else None
-            opt.d_labels = out["labels"].data_ptr() if m > 0 else spare.data_ptr()
-            opt.d_counts = None if not want_counts else (out["counts"].data_ptr() if m > 0 else spare.data_ptr())
+            opt.d_queries = _address(queries)
+            opt.d_core_label = _address(core_label)
+            opt.d_labels = _address(out["labels"], spare)
+            opt.d_counts = _address(out.get("counts"), spare)
             info = _lib.DbscanInfo()
             _lib.check(self._lib.tknnDbscanQuery(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
         out["info"] = info.as_dict()
@@ -405,24 +403,13 @@ class TrueKNN:
         Returns dict(offsets (m+1,) int64, idx (total,) int32, dist (total,) float32 [with ``want_dist``], info); ``info`` is
         the fill pass's (the count pass's where there is nothing to fill), ``count_info`` the count pass's."""
         torch = self._torch
-        if isinstance(queries, np.ndarray):
-            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
-                raise ValueError("radius_query: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
-            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
-        if not isinstance(queries, torch.Tensor):
-            raise ValueError("radius_query: queries must be a numpy array or a torch tensor")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
-            raise ValueError("radius_query: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
-        if queries.device != self.device:
-            raise ValueError("radius_query: queries are on %s, the engine on %s" % (queries.device, self.device))
-        if not queries.is_contiguous():
-            raise ValueError("radius_query: queries must be contiguous (packed fp32 triples)")
+        queries = self._queries(queries, "radius_query")
         m = int(queries.shape[0])
         with torch.cuda.device(self.device):
             offsets = torch.empty((m + 1,), dtype=torch.int64, device=self.device)
             opt = _lib.RadiusOptions()
             opt.m, opt.radius, opt.sort = m, float(radius), int(bool(sort))
-            opt.d_queries = queries.data_ptr() if m > 0 else None
+            opt.d_queries = _address(queries)
             opt.d_offsets = offsets.data_ptr()
             count_info = _lib.RadiusInfo()
             _lib.check(self._lib.tknnRadiusQuery(self._h, ctypes.byref(opt), ctypes.byref(count_info), self._stream()))
@@ -450,18 +437,7 @@ class TrueKNN:
         tensors on the engine's device.  ``queries``: numpy (m,2|3) or a contiguous float32 CUDA tensor (m,3) on the engine's
         device.  Returns dict(idx (m,k) int32, dist (m,k) float32 [with ``want_dist``], counts (m,) int32, info)."""
         torch = self._torch
-        if isinstance(queries, np.ndarray):
-            if queries.ndim != 2 or queries.shape[1] not in (2, 3):
-                raise ValueError("radius_knn: queries must be (m,2) or (m,3), got %s" % (queries.shape,))
-            queries = torch.from_numpy(pad_to_3d(queries)).to(self.device)
-        if not isinstance(queries, torch.Tensor):
-            raise ValueError("radius_knn: queries must be a numpy array or a torch tensor")
-        if queries.dtype != torch.float32 or queries.dim() != 2 or queries.shape[1] != 3:
-            raise ValueError("radius_knn: queries must be float32 (m,3), got %s %s" % (queries.dtype, tuple(queries.shape)))
-        if queries.device != self.device:
-            raise ValueError("radius_knn: queries are on %s, the engine on %s" % (queries.device, self.device))
-        if not queries.is_contiguous():
-            raise ValueError("radius_knn: queries must be contiguous (packed fp32 triples)")
+        queries = self._queries(queries, "radius_knn")
         if (radius is None) == (radii is None):
             raise ValueError("radius_knn: give exactly one of radius and radii")
         m, k = int(queries.shape[0]), int(k)
@@ -482,16 +458,15 @@ class TrueKNN:
             if want_dist:
                 out["dist"] = torch.empty((m, rows), dtype=torch.float32, device=self.device)
             out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
-            # (an empty tensor has no address: with m = 0 the call is a no-op that still checks its arguments)
             spare = torch.empty((1,), dtype=torch.int32, device=self.device)
             opt = _lib.RadiusKnnOptions()
             opt.m, opt.k, opt.radius = m, k, 0.0 if radius is None else float(radius)
-            opt.d_queries = queries.data_ptr() if m > 0 else None
-            opt.d_radii = None if radii is None else (radii.data_ptr() if m > 0 else spare.data_ptr())
-            opt.d_skip_ids = None if skip_ids is None or m == 0 else skip_ids.data_ptr()
-            opt.d_idx = out["idx"].data_ptr() if m * rows > 0 else spare.data_ptr()
-            opt.d_dist = out["dist"].data_ptr() if want_dist and m * rows > 0 else None
-            opt.d_counts = out["counts"].data_ptr() if m > 0 else None
+            opt.d_queries = _address(queries)
+            opt.d_radii = _address(radii, spare)
+            opt.d_skip_ids = _address(skip_ids)
+            opt.d_idx = _address(out["idx"], spare)
+            opt.d_dist = _address(out.get("dist"))
+            opt.d_counts = _address(out["counts"])
             info = _lib.RadiusKnnInfo()
             _lib.check(self._lib.tknnRadiusKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
         out["info"] = info.as_dict()
@@ -586,58 +561,38 @@ def debug_box_tree(boxes, refit=None, mode=0, device=None):
     return {"nodes": nodes[: n - 1], "rope_node": rope_node[: n - 1], "rope_leaf": rope_leaf, "prim_id": prim, "sorted_boxes": sorted_boxes}
 
 
-def trueknn(points, k, start_radius, **kw):
-    """One-shot helper: build + solve, results as numpy arrays."""
+def _one_shot(points, call):
+    """An engine built over ``points`` for the one ``call(engine)``: its results as numpy arrays, and the build's info."""
     eng = TrueKNN()
     try:
         eng.build(points)
-        r = eng.solve(k, start_radius, **kw)
-        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
+        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in call(eng).items()}
         res["build_info"] = eng.build_info
         return res
     finally:
         eng.close()
+
+
+def trueknn(points, k, start_radius, **kw):
+    """One-shot helper: build + solve, results as numpy arrays."""
+    return _one_shot(points, lambda eng: eng.solve(k, start_radius, **kw))
 
 
 def trueknn_query(points, queries, k, start_radius, **kw):
     """One-shot helper: build over ``points``, answer for ``queries`` (TrueKNN.query), results as numpy arrays."""
-    eng = TrueKNN()
-    try:
-        eng.build(points)
-        r = eng.query(queries, k, start_radius, **kw)
-        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
-        res["build_info"] = eng.build_info
-        return res
-    finally:
-        eng.close()
+    return _one_shot(points, lambda eng: eng.query(queries, k, start_radius, **kw))
 
 
 def radius_query(points, queries, radius, **kw):
     """One-shot helper: build over ``points``, the neighbours of ``queries`` within ``radius`` (TrueKNN.radius_query), results
     as numpy arrays."""
-    eng = TrueKNN()
-    try:
-        eng.build(points)
-        r = eng.radius_query(queries, radius, **kw)
-        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
-        res["build_info"] = eng.build_info
-        return res
-    finally:
-        eng.close()
+    return _one_shot(points, lambda eng: eng.radius_query(queries, radius, **kw))
 
 
 def radius_knn(points, queries, k, **kw):
     """One-shot helper: build over ``points``, at most ``k`` nearest points within a radius of ``queries`` (TrueKNN.radius_knn),
     results as numpy arrays."""
-    eng = TrueKNN()
-    try:
-        eng.build(points)
-        r = eng.radius_knn(queries, k, **kw)
-        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in r.items()}
-        res["build_info"] = eng.build_info
-        return res
-    finally:
-        eng.close()
+    return _one_shot(points, lambda eng: eng.radius_knn(queries, k, **kw))
 
 
 def radius_graph(points, k, radius, loop=False):

@@ -80,6 +80,25 @@ def test_fingerprints_follow_the_split_of_the_clustering_kernels(tmp_path, monke
         assert {kernel for kernel in kernels if after[kernel] != before[kernel]} == changed, name
 
 
+def test_fingerprints_leave_out_the_c_abi(tmp_path, monkeypatch):
+    """tknn_api.hip holds the C ABI's argument checks and messages and no kernel: an edit of it changes the library's
+    fingerprint and that of no kernel of the team_, bigk_, tie_fix_ and db_ families (on a copy of csrc/ and include/)."""
+    import shutil
+
+    pkg = tmp_path / "owlraytracing_amd"
+    shutil.copytree(os.path.join(_lib._HERE, "csrc"), pkg / "csrc", ignore=shutil.ignore_patterns("*.o", "diagobj"))
+    shutil.copytree(os.path.join(ROOT, "include"), tmp_path / "include")
+    monkeypatch.setattr(_lib, "_HERE", str(pkg))
+    assert all("tknn_api.hip" in skip for skip in _lib._NOT_IN.values())
+    kernels = (None, "team_kernel", "team_prep_kernel", "team_walk_kernel", "tie_fix_kernel", "bigk_walk_kernel", "db_core_kernel",
+               "db_noise_probe_kernel", "db_group_union_kernel", "db_uniform_kernel", "db_label_kernel", "db_rows_from_slots_kernel", "db_query_kernel")
+    before = {kernel: _lib.source_fingerprint(kernel) for kernel in kernels}
+    with open(pkg / "csrc" / "tknn_api.hip", "ab") as fh:
+        fh.write(b"\n")
+    after = {kernel: _lib.source_fingerprint(kernel) for kernel in kernels}
+    assert {kernel for kernel in kernels if after[kernel] != before[kernel]} == {None}
+
+
 def test_committed_records_name_the_sources_they_were_taken_on():
     recs = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
     assert recs, "profiles/hbm_traffic.json is empty"

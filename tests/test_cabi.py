@@ -1,10 +1,17 @@
 """The C-ABI library loads and exports every symbol include/owlknn.h declares (no GPU needed)."""
+import ctypes
 import os
 import re
+import sys
 
 import pytest
+import torch  # noqa: F401  before the library is loaded: torch brings its own HIP runtime, and a process that loads the
+#                            system's first ends up with two, of which the second to start finds no device
 
 from owlraytracing_amd import _lib
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cabi_calls as cc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,11 +64,14 @@ def test_product_package_never_imports_the_oracle():
 
 def test_ctypes_structs_have_the_header_layout(tmp_path):
     """Sizes and field offsets of the ctypes mirrors against include/owlknn.h compiled by gcc as C99."""
-    import ctypes
     import subprocess
     pairs = {"tknnSolveInfo": _lib.SolveInfo, "tknnSolveOptions": _lib.SolveOptions,
              "tknnDbscanInfo": _lib.DbscanInfo, "tknnDbscanAutoInfo": _lib.DbscanAutoInfo, "tknnBuildInfo": _lib.BuildInfo,
-             "tknnTreeExport": _lib.TreeExport}
+             "tknnTreeExport": _lib.TreeExport, "tknnQueryOptions": _lib.QueryOptions, "tknnDbscanQueryOptions": _lib.DbscanQueryOptions,
+             "tknnRadiusOptions": _lib.RadiusOptions, "tknnRadiusInfo": _lib.RadiusInfo, "tknnRadiusKnnOptions": _lib.RadiusKnnOptions,
+             "tknnRadiusKnnInfo": _lib.RadiusKnnInfo}
+    mirrors = {c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and getattr(c, "_fields_", None)}
+    assert mirrors == set(pairs.values()), "a ctypes structure of _lib is not compared with the header"
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "owlknn.h"', "int main(void) {"]
     for cname, cls in pairs.items():
         lines.append('  printf("%s size %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -83,3 +93,39 @@ def test_ctypes_structs_have_the_header_layout(tmp_path):
             assert getattr(cls, what).offset == int(value), (cname, what)
         seen += 1
     assert seen == sum(len(c._fields_) + 1 for c in pairs.values())
+
+
+def test_a_null_engine_is_refused_by_every_call_without_a_device():
+    """Every call that takes an engine, with e = NULL and otherwise plausible arguments (addresses of host memory that no
+    refusal reads): TKNN_E_ARG, said in the call's own name, on a machine with or without a GPU."""
+    lib = _lib.load()
+    assert set(cc.CALLS) == {name for name, (_, args) in _lib.SIGNATURES.items()
+                             if name not in ("tknnCreate", "tknnDestroy") and not name.startswith("tknnDebug") and args}, "a call is missing"
+    spare = ctypes.create_string_buffer(4096)
+    addr = ctypes.addressof(spare)
+    for fn in sorted(cc.CALLS):
+        rc, message, info, _ = cc.call(lib, fn, None, addr, addr)
+        assert rc == cc.E_ARG, (fn, rc, message)
+        assert message.startswith(cc.SPEAKS_AS.get(fn, fn)), (fn, message)
+        assert info is None or info == bytes([cc.INFO_FILL]) * len(info), fn  # (refused: info untouched)
+    assert spare.raw == bytes(4096)
+
+
+def test_calls_without_an_engine_refuse_bad_arguments():
+    """tknnDestroy(NULL) does nothing; tknnCreate(NULL) and the two debug entry points with a NULL or out-of-range argument
+    are refused before any device is looked for."""
+    lib = _lib.load()
+    lib.tknnDestroy(None)
+    assert lib.tknnCreate(None) == cc.E_ARG
+    assert lib.tknnLastError().decode().startswith("tknnCreate")
+    spare = ctypes.create_string_buffer(4096)
+    p = ctypes.addressof(spare)
+    good = dict(d_boxes=p, n=4, d_boxes_refit=None, mode=0, nodes=p, rope_node=p, rope_leaf=p, prim_id=p, sorted_boxes=p)
+    for fault in (dict(d_boxes=None), dict(n=0), dict(n=-1), dict(n=cc.TOO_MANY), dict(mode=-1), dict(mode=3)):
+        assert lib.tknnDebugBoxTree(*dict(good, **fault).values(), None) == cc.E_ARG, fault
+        assert lib.tknnLastError().decode().startswith("tknnDebugBoxTree"), fault
+    good = dict(d_q=p, d_r=p, n=4, d_lo=p, d_hi=p)
+    for fault in (dict(d_q=None), dict(d_r=None), dict(d_lo=None), dict(d_hi=None), dict(n=-1)):
+        assert lib.tknnDebugThresholds(*dict(good, **fault).values(), None) == cc.E_ARG, fault
+        assert lib.tknnLastError().decode().startswith("tknnDebugThresholds"), fault
+    assert spare.raw == bytes(4096)
