@@ -65,6 +65,9 @@ class Lbvh {
   const int32_t *block_paths_device() const { return point_mode_ && n_ > 1 ? block_paths_ : nullptr; }
   // point trees: row_slot[row] = the sorted slot of the caller's row `row` (the inverse of prim_id), n entries
   const int32_t *row_slot_device() const { return point_mode_ && built_ ? reinterpret_cast<const int32_t *>(order_) : nullptr; }
+  // the sorted 21-level curve keys of the slots (n; what download_debug exports as `keys`): the sort's output buffer, which nothing
+  // writes between two builds -- a point's place in the order is a search in it (knn_seed.hip)
+  const uint64_t *keys_device() const { return built_ ? codes_alt_ : nullptr; }
   int curve() const { return curve_; }  // CURVE_HILBERT / CURVE_MORTON (curve_key.h): the key the tree was sorted by
   int64_t size() const { return n_; }
   bool built() const { return built_; }

@@ -17,6 +17,7 @@
 #include "knn_thresholds.h"  // knn_gate_from_worst
 #include "lane_walk.h"
 #include "query_order.h"
+#include "radius_knn_walk.h"
 #include "team_lanes.h"
 #include "team_walk.h"
 #include "trueknn_engine.h"
@@ -35,27 +36,6 @@ constexpr int kRknnBlock = 64;        // one wave per workgroup, four teams
 constexpr int kRknnBlocksPerCu = 16;  // 7.3 KB of LDS each
 constexpr int kRknnLaneBlock = 256;
 
-// words of the call's own counters (in the workspace, zeroed per call)
-enum { kWsCursor = 0, kWsRedo = 1, kWsTotal = 2, kWsFullRows = 3, kWsNodeTests = 4, kWsPointTests = 5, kWsWords = 8 };
-
-struct RadiusKnnKernelArgs {
-  LbvhView bvh;
-  LbvhWideView wide;
-  const float *queries;     // m packed triples, caller order
-  const uint32_t *order;    // m: the query worked on at sorted position i
-  int32_t m;
-  int k;
-  float radius;             // every row's radius if radii is null
-  const float *radii;       // m, by the caller's j (may be null)
-  const int32_t *skip_ids;  // m, by the caller's j (may be null)
-  int force_redo;           // TKNN_RADIUS_KNN_FORCE_FALLBACK (tests): the walk leaves every query to the lane kernel
-  int32_t *out_idx;         // m*k
-  float *out_dist;          // m*k (may be null)
-  int32_t *out_counts;      // m (may be null)
-  int32_t *redo;            // m: queries left to the lane kernel
-  unsigned long long *ws;   // kWsWords counters
-};
-
 // ---- a query's radius, gate and skipped point ----------------------------------------------------------------------------------
 struct RknnQuery {
   LbvhPoint q;
@@ -63,7 +43,7 @@ struct RknnQuery {
   float r_wide;  // r * (1 + 1e-6): the box prefilter must not cut what the rounded sphere test accepts (radius_query.hip)
   float gate_r;  // the squared-distance gate of an empty list: every d2 whose rounded root can be <= r passes
   int32_t skip;  // the point left out of the row (no point has a negative id)
-  bool valid;    // a finite positive radius (a row without one is empty)
+  bool valid;    // a finite positive radius, or a zero one where the call takes it (a row without one is empty)
 };
 __device__ __forceinline__ RknnQuery rknn_query(const RadiusKnnKernelArgs &a, int32_t qi, bool has_q) {
   RknnQuery s;
@@ -71,7 +51,7 @@ __device__ __forceinline__ RknnQuery rknn_query(const RadiusKnnKernelArgs &a, in
   s.q.id = -1;
   s.r = a.radii ? (has_q ? a.radii[qi] : 0.f) : a.radius;
   s.skip = a.skip_ids && has_q ? a.skip_ids[qi] : -1;
-  s.valid = s.r > 0.f && s.r <= FLT_MAX;  // (NaN: neither)
+  s.valid = (s.r > 0.f || (a.zero_radius_ok && s.r == 0.f)) && s.r <= FLT_MAX;  // (NaN: neither)
   s.r_wide = s.r * 1.000001f;
   s.gate_r = knn_gate_from_worst(s.r);
   return s;
@@ -80,26 +60,16 @@ __device__ __forceinline__ RknnQuery rknn_query(const RadiusKnnKernelArgs &a, in
 // candidate beyond it is farther than r or farther than the k-th entry; one AT the k-th distance passes, the index decides.
 __device__ __forceinline__ float rknn_gate(float gate_r, float kth) { return fminf(gate_r, knn_gate_from_worst(kth)); }
 
-// t_kth_dist (team_walk.h) with the register picked by masks instead of a chain of selects: the compiler turns that chain into a load
-// through a selected address, which keeps registers 1 .. NREG - 1 of the list in scratch (16 / 32 bytes for NREG = 3 / 4 in
-// query_walk_kernel); picked this way the list stays in registers for every NREG.
-template <int NREG>
-__device__ __forceinline__ float rknn_kth_dist(const uint32_t (&bd)[NREG], int k, int team) {
-  const uint32_t sel = (uint32_t)(k - 1) >> 4;
-  uint32_t reg = 0u;
-#pragma unroll
-  for (int j = 0; j < NREG; j++) reg |= bd[j] & (0u - (uint32_t)(sel == (uint32_t)j));
-  return __uint_as_float(t_lane_read(reg, (team << 4) + ((k - 1) & 15)));
-}
-
 __device__ __forceinline__ void rknn_add_stats(unsigned long long *ws, int lane, unsigned long long total, unsigned long long full_rows,
-                                               unsigned long long node_tests, unsigned long long point_tests) {
-  const unsigned long long tsum = t_wave_sum(total), fsum = t_wave_sum(full_rows), nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests);
+                                               unsigned long long node_tests, unsigned long long point_tests, unsigned long long tightened) {
+  const unsigned long long tsum = t_wave_sum(total), fsum = t_wave_sum(full_rows), nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests),
+                           tight = t_wave_sum(tightened);
   if (lane == 0) {
-    if (tsum) atomicAdd(&ws[kWsTotal], tsum);
-    if (fsum) atomicAdd(&ws[kWsFullRows], fsum);
-    if (nt) atomicAdd(&ws[kWsNodeTests], nt);
-    if (pt) atomicAdd(&ws[kWsPointTests], pt);
+    if (tsum) atomicAdd(&ws[kRknnWsTotal], tsum);
+    if (fsum) atomicAdd(&ws[kRknnWsFullRows], fsum);
+    if (nt) atomicAdd(&ws[kRknnWsNodeTests], nt);
+    if (pt) atomicAdd(&ws[kRknnWsPointTests], pt);
+    if (tight) atomicAdd(&ws[kRknnWsTightened], tight);
   }
 }
 
@@ -124,14 +94,14 @@ __global__ void __launch_bounds__(kRknnBlock) __attribute__((amdgpu_waves_per_eu
   walk_fill_levels<1>(levels, &a.wide, lane);
   t_wave_sync();
   const LbvhWideView &wv = a.wide;
-  unsigned long long node_tests = 0, point_tests = 0, total = 0, full_rows = 0;
+  unsigned long long node_tests = 0, point_tests = 0, total = 0, full_rows = 0, tightened = 0;
   for (;;) {
     int got = 0;
-    if (lane == 0) got = (int)atomicAdd(&a.ws[kWsCursor], 4ull);
+    if (lane == 0) got = (int)atomicAdd(&a.ws[kRknnWsCursor], 4ull);
     const int base = __builtin_amdgcn_readfirstlane(got);
     if (base >= a.m) break;
     const bool has_q = base + team < a.m;
-    const int32_t qi = has_q ? (int32_t)a.order[base + team] : 0;
+    const int32_t qi = has_q ? (a.order ? (int32_t)a.order[base + team] : base + team) : 0;
     const RknnQuery s = rknn_query(a, qi, has_q);
     const LbvhPoint &q = s.q;
     const bool active = has_q && s.valid && !a.force_redo;
@@ -179,6 +149,7 @@ __global__ void __launch_bounds__(kRknnBlock) __attribute__((amdgpu_waves_per_eu
     // ---- the row: k entries, sixteen lanes at a time (64 contiguous bytes per array), the tail padded ----
     const bool redo = has_q && (overflow || a.force_redo);  // left to the lane kernel, which starts the row again
     const bool write = has_q && !redo;
+    const int32_t row = write && a.out_row ? a.out_row[qi] : qi;
     uint32_t cnt = 0;
 #pragma unroll
     for (int reg = 0; reg < NREG; reg++) {
@@ -186,19 +157,21 @@ __global__ void __launch_bounds__(kRknnBlock) __attribute__((amdgpu_waves_per_eu
       const bool real = j < a.k && !(bd[reg] == 0x7f7fffffu && bi[reg] == 0u);
       cnt += __popc((uint32_t)(__ballot(real) >> (team << 4)) & 0xffffu);
       if (write && j < a.k) {
-        const int64_t o = (int64_t)qi * a.k + j;
+        const int64_t o = (int64_t)row * a.k + j;
         a.out_idx[o] = real ? (int32_t)bi[reg] : -1;
         if (a.out_dist) a.out_dist[o] = real ? __uint_as_float(bd[reg]) : INFINITY;
       }
     }
-    if (tl == 0 && redo) a.redo[atomicAdd(&a.ws[kWsRedo], 1ull)] = qi;
+    if (tl == 0 && redo) a.redo[atomicAdd(&a.ws[kRknnWsRedo], 1ull)] = qi;
+    const float kth = rknn_kth_dist<NREG>(bd, a.k, team);
     if (tl == 0 && write) {
-      if (a.out_counts) a.out_counts[qi] = (int32_t)cnt;
+      if (a.out_counts) a.out_counts[row] = (int32_t)cnt;
       total += cnt;
       full_rows += cnt == (uint32_t)a.k ? 1u : 0u;
+      tightened += cnt == (uint32_t)a.k && kth < s.r ? 1u : 0u;
     }
   }
-  rknn_add_stats(a.ws, lane, total, full_rows, node_tests, point_tests);
+  rknn_add_stats(a.ws, lane, total, full_rows, node_tests, point_tests, tightened);
 }
 
 // ---- 3. one query per lane: the queries of the redo list ---------------------------------------------------------------------------
@@ -207,7 +180,7 @@ __global__ void __launch_bounds__(kRknnBlock) __attribute__((amdgpu_waves_per_eu
 template <int K>
 __global__ void __launch_bounds__(kRknnLaneBlock) radius_knn_lane_kernel(RadiusKnnKernelArgs a) {
   const int64_t t = (int64_t)blockIdx.x * kRknnLaneBlock + threadIdx.x;
-  const bool has_q = t < (int64_t)a.ws[kWsRedo];
+  const bool has_q = t < (int64_t)a.ws[kRknnWsRedo];
   const int32_t qi = has_q ? a.redo[t] : 0;
   const RknnQuery s = rknn_query(a, qi, has_q);
   const LbvhPoint &q = s.q;
@@ -237,8 +210,13 @@ __global__ void __launch_bounds__(kRknnLaneBlock) radius_knn_lane_kernel(RadiusK
           return lane_rope();
         });
   uint32_t cnt = 0;
+  bool tightened = false;
   if (has_q) {
-    const int64_t base = (int64_t)qi * a.k;
+    const int32_t row = a.out_row ? a.out_row[qi] : qi;
+    const int64_t base = (int64_t)row * a.k;
+    uint64_t kth = list.key[0];  // entry k - 1
+#pragma unroll
+    for (int j = 1; j < K; j++) kth = j == a.k - 1 ? list.key[j] : kth;
 #pragma unroll
     for (int j = 0; j < K; j++)
       if (j < a.k) {
@@ -247,10 +225,11 @@ __global__ void __launch_bounds__(kRknnLaneBlock) radius_knn_lane_kernel(RadiusK
         if (a.out_dist) a.out_dist[base + j] = real ? knn_key_dist(list.key[j]) : INFINITY;
         cnt += real ? 1u : 0u;
       }
-    if (a.out_counts) a.out_counts[qi] = (int32_t)cnt;
+    if (a.out_counts) a.out_counts[row] = (int32_t)cnt;
+    tightened = cnt == (uint32_t)a.k && knn_key_dist(kth) < s.r;
   }
   // (all lanes of the wave are here)
-  rknn_add_stats(a.ws, threadIdx.x & 63, cnt, has_q && cnt == (uint32_t)a.k ? 1u : 0u, node_tests, point_tests);
+  rknn_add_stats(a.ws, threadIdx.x & 63, cnt, has_q && cnt == (uint32_t)a.k ? 1u : 0u, node_tests, point_tests, tightened ? 1u : 0u);
 }
 
 using RknnWalkEntry = void (*)(RadiusKnnKernelArgs);
@@ -258,12 +237,32 @@ const RknnWalkEntry kRknnWalks[4] = {radius_knn_walk_kernel<1>, radius_knn_walk_
 
 }  // namespace
 
+// the walk, then the lane kernel for what the walk left
+unsigned long long radius_knn_walks(const RadiusKnnKernelArgs &a, int cu_count, unsigned long long *h_words, hipStream_t s) {
+  const int blocks = (int)std::min<int64_t>(((int64_t)a.m + 3) / 4, (int64_t)cu_count * kRknnBlocksPerCu);
+  void *kargs[] = {(void *)&a};
+  OWLMI_HIP(hipLaunchKernel((const void *)kRknnWalks[query_nreg(a.k) - 1], dim3(blocks), dim3(kRknnBlock), kargs, 0, s));
+  OWLMI_HIP(hipGetLastError());
+  OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kRknnWsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  OWLMI_HIP(hipStreamSynchronize(s));  // the call's one host sync before its last: the redo list's length
+  const unsigned long long n_redo = h_words[kRknnWsRedo];
+  if (n_redo) {
+    const unsigned lane_blocks = (unsigned)((n_redo + kRknnLaneBlock - 1) / kRknnLaneBlock);
+    ListCapacities::dispatch(list_capacity_for(a.k), [&](auto cap) {
+      hipLaunchKernelGGL(radius_knn_lane_kernel<decltype(cap)::value>, dim3(lane_blocks), dim3(kRknnLaneBlock), 0, s, a);
+    });
+    OWLMI_HIP(hipGetLastError());
+    OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kRknnWsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  }
+  return n_redo;
+}
+
 void Engine::radius_knn(const tknnRadiusKnnOptions &o, tknnRadiusKnnInfo *info, hipStream_t s) {
   const int64_t m = o.m;
   // the call's workspace: counters | codes, order (+ the sort's second halves) | lane list | sort space
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t sort_bytes = query_order_sort_bytes(m, s);
-  const size_t words_b = align(kWsWords * sizeof(unsigned long long)), col_b = align((size_t)m * sizeof(uint32_t));
+  const size_t words_b = align(kRknnWsWords * sizeof(unsigned long long)), col_b = align((size_t)m * sizeof(uint32_t));
   char *ws = (char *)workspace(words_b + 5 * col_b + align(sort_bytes));
   unsigned long long *d_words = (unsigned long long *)ws;
   uint32_t *codes = (uint32_t *)(ws + words_b), *codes_alt = (uint32_t *)(ws + words_b + col_b), *order_in = (uint32_t *)(ws + words_b + 2 * col_b),
@@ -290,33 +289,18 @@ void Engine::radius_knn(const tknnRadiusKnnOptions &o, tknnRadiusKnnInfo *info, 
   a.ws = d_words;
 
   OWLMI_HIP(hipEventRecord(ev_a_, s));
-  OWLMI_HIP(hipMemsetAsync(d_words, 0, kWsWords * sizeof(unsigned long long), s));
+  OWLMI_HIP(hipMemsetAsync(d_words, 0, kRknnWsWords * sizeof(unsigned long long), s));
   query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, sort_tmp, sort_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
-  // the walk, then the lane kernel for what the walk left
-  const int blocks = (int)std::min<int64_t>((m + 3) / 4, (int64_t)cu_count_ * kRknnBlocksPerCu);
-  void *kargs[] = {(void *)&a};
-  OWLMI_HIP(hipLaunchKernel((const void *)kRknnWalks[query_nreg(a.k) - 1], dim3(blocks), dim3(kRknnBlock), kargs, 0, s));
-  OWLMI_HIP(hipGetLastError());
   unsigned long long *h_words = h_counters_;
-  OWLMI_HIP(hipMemcpyAsync(h_words, d_words, kWsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipStreamSynchronize(s));  // the call's one host sync before its last: the redo list's length
-  const unsigned long long n_redo = h_words[kWsRedo];
-  if (n_redo) {
-    const unsigned lane_blocks = (unsigned)((n_redo + kRknnLaneBlock - 1) / kRknnLaneBlock);
-    ListCapacities::dispatch(list_capacity_for(a.k), [&](auto cap) {
-      hipLaunchKernelGGL(radius_knn_lane_kernel<decltype(cap)::value>, dim3(lane_blocks), dim3(kRknnLaneBlock), 0, s, a);
-    });
-    OWLMI_HIP(hipGetLastError());
-    OWLMI_HIP(hipMemcpyAsync(h_words, d_words, kWsWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  }
+  const unsigned long long n_redo = radius_knn_walks(a, cu_count_, h_words, s);
   OWLMI_HIP(hipEventRecord(ev_c_, s));
   OWLMI_HIP(hipStreamSynchronize(s));
   if (info) {
-    info->total = (int64_t)h_words[kWsTotal];
-    info->full_rows = (int64_t)h_words[kWsFullRows];
-    info->node_tests = (int64_t)h_words[kWsNodeTests];
-    info->point_tests = (int64_t)h_words[kWsPointTests];
+    info->total = (int64_t)h_words[kRknnWsTotal];
+    info->full_rows = (int64_t)h_words[kRknnWsFullRows];
+    info->node_tests = (int64_t)h_words[kRknnWsNodeTests];
+    info->point_tests = (int64_t)h_words[kRknnWsPointTests];
     info->lane_rows = (int64_t)n_redo;
     OWLMI_HIP(hipEventElapsedTime(&info->solve_ms, ev_a_, ev_c_));
     OWLMI_HIP(hipEventElapsedTime(&info->order_ms, ev_a_, ev_b_));

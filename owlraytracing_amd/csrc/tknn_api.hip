@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h and include/owlknn_knn.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -323,6 +323,23 @@ int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusK
     c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
     zero(info);
     if (o.m > 0) e->impl.radius_knn(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnKnn(tknnEngine e, const tknnKnnOptions *options, tknnKnnInfo *info, void *stream) {
+  return api("tknnKnn", e, [&](const Call &c) {
+    const tknnKnnOptions &o = c.record(options);
+    c.need(o.d_idx, "d_idx");
+    if (!o.d_queries) {  // the set's own points
+      c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
+      c.require(!o.d_skip_ids, "d_queries is NULL (the set's own points): d_skip_ids must be NULL, every point is left out of its own row");
+    }
+    c.built();
+    c.require(o.k >= 1, "k must be positive");
+    c.count(o.m, "m");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
+    zero(info);
+    if (o.m > 0) e->impl.knn(o, info, (hipStream_t)stream);
   });
 }
 

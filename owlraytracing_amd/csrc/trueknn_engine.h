@@ -9,6 +9,7 @@
 #include "knn_device.h"
 #include "lbvh.h"
 #include "owlknn.h"
+#include "owlknn_knn.h"
 
 namespace owlmi {
 
@@ -139,6 +140,9 @@ class Engine {
   void radius_query(const tknnRadiusOptions &o, tknnRadiusInfo *info, hipStream_t s);
   // radius_knn.hip: at most k nearest points within a radius of m points that are not in the tree, as dense rows (tknnRadiusKnn); m > 0
   void radius_knn(const tknnRadiusKnnOptions &o, tknnRadiusKnnInfo *info, hipStream_t s);
+  // knn_seed.hip: the k nearest points, exactly, of m points that are not in the tree or (d_queries null) of the tree's own points,
+  // with no radius from the caller (tknnKnn); m > 0
+  void knn(const tknnKnnOptions &o, tknnKnnInfo *info, hipStream_t s);
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }

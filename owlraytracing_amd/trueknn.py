@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _knn_lib, _lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -472,6 +472,50 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def knn(self, queries=None, k=1, skip_ids=None, want_dist=True):
+        """The ``k`` nearest points of the built set, exactly and with no radius to choose, as dense rows (tknnKnn): row j holds
+        the points p whose fp32 distance sqrt((dx*dx + dy*dy) + dz*dz) is finite, ascending in (distance, index), cut after k and
+        padded with idx -1 / dist +inf -- ``radius_knn``'s row at the largest finite radius.  With ``queries`` (numpy (m,2|3) or
+        a contiguous float32 CUDA tensor (m,3) on the engine's device) nothing is self unless ``skip_ids`` (length m, int32,
+        numpy or a tensor on the engine's device) says so: the point named skip_ids[j] (its id on trees built with ids, its row
+        otherwise) is left out of row j; a negative value skips nothing.  Without ``queries`` row j answers for point j of the
+        built set, every point left out of its own row (a coinciding duplicate stays, at distance 0): the exact all-kNN of the
+        set; ``skip_ids`` must then be None.  Returns dict(idx (m,k) int32, dist (m,k) float32 [with ``want_dist``], counts (m,)
+        int32, info)."""
+        torch = self._torch
+        if queries is None:
+            if skip_ids is not None:
+                raise ValueError("knn: skip_ids go with queries (without queries every point is left out of its own row)")
+            m = self.n
+        else:
+            queries = self._queries(queries, "knn")
+            m = int(queries.shape[0])
+        k = int(k)
+        with torch.cuda.device(self.device):
+            if skip_ids is not None:
+                if isinstance(skip_ids, torch.Tensor) and skip_ids.device != self.device:
+                    raise ValueError("knn: skip_ids is on %s, the engine on %s" % (skip_ids.device, self.device))
+                skip_ids = torch.as_tensor(skip_ids, device=self.device).to(torch.int32).contiguous()
+                if skip_ids.shape != (m,):
+                    raise ValueError("knn: skip_ids must have one entry per query")
+            rows = max(k, 0)
+            out = {"idx": torch.empty((m, rows), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((m, rows), dtype=torch.float32, device=self.device)
+            out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _knn_lib.KnnOptions()
+            opt.m, opt.k = m, k
+            opt.d_queries = None if queries is None else _address(queries, spare)
+            opt.d_skip_ids = _address(skip_ids, spare)
+            opt.d_idx = _address(out["idx"], spare)
+            opt.d_dist = _address(out.get("dist"))
+            opt.d_counts = _address(out["counts"])
+            info = _knn_lib.KnnInfo()
+            _lib.check(_knn_lib.load().tknnKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -602,6 +646,20 @@ def radius_graph(points, k, radius, loop=False):
     points = pad_to_3d(np.asarray(points, np.float32))
     skip = None if loop else np.arange(len(points), dtype=np.int32)
     return radius_knn(points, points, k, radius=radius, skip_ids=skip)
+
+
+def knn(points, queries, k, **kw):
+    """One-shot helper: build over ``points``, the exact ``k`` nearest points of ``queries`` (TrueKNN.knn), results as numpy
+    arrays."""
+    return _one_shot(points, lambda eng: eng.knn(queries, k, **kw))
+
+
+def knn_graph(points, k, loop=False):
+    """One-shot helper: for every point of ``points`` its ``k`` nearest other points, exactly -- TrueKNN.knn over the set's own
+    points; with ``loop`` the points are queries like any others, so the point itself is an entry, at distance 0.  Results as
+    numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
+    points = pad_to_3d(np.asarray(points, np.float32))
+    return knn(points, points if loop else None, k)
 
 
 def dbscan_query(points, queries, eps, min_pts):
