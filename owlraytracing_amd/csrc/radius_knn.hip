@@ -56,23 +56,6 @@ __device__ __forceinline__ RknnQuery rknn_query(const RadiusKnnKernelArgs &a, in
   s.gate_r = knn_gate_from_worst(s.r);
   return s;
 }
-// The gate of a list whose k-th entry lies at distance `kth` (FLT_MAX: fewer than k entries, the gate stays the radius's).  A
-// candidate beyond it is farther than r or farther than the k-th entry; one AT the k-th distance passes, the index decides.
-__device__ __forceinline__ float rknn_gate(float gate_r, float kth) { return fminf(gate_r, knn_gate_from_worst(kth)); }
-
-__device__ __forceinline__ void rknn_add_stats(unsigned long long *ws, int lane, unsigned long long total, unsigned long long full_rows,
-                                               unsigned long long node_tests, unsigned long long point_tests, unsigned long long tightened) {
-  const unsigned long long tsum = t_wave_sum(total), fsum = t_wave_sum(full_rows), nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests),
-                           tight = t_wave_sum(tightened);
-  if (lane == 0) {
-    if (tsum) atomicAdd(&ws[kRknnWsTotal], tsum);
-    if (fsum) atomicAdd(&ws[kRknnWsFullRows], fsum);
-    if (nt) atomicAdd(&ws[kRknnWsNodeTests], nt);
-    if (pt) atomicAdd(&ws[kRknnWsPointTests], pt);
-    if (tight) atomicAdd(&ws[kRknnWsTightened], tight);
-  }
-}
-
 // ---- 2. the walk -------------------------------------------------------------------------------------------------------------
 // The box rule.  A child box that overlaps the query's box is declined if its near corner lies beyond the list's gate tau2:
 // near2 * 0.999995 > tau2 (beyond_gate, the margin lane_counts_subtree keeps).  The margin's direction: near2 is at most every

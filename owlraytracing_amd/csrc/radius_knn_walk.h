@@ -1,11 +1,13 @@
 // radius_knn_walk.h -- the walk of radius_knn.hip as its two callers launch it: tknnRadiusKnn (radius_knn.hip) with the caller's
 // radii, tknnKnn (knn_seed.hip) with the bounds its seed kernel found.  The kernels themselves are in radius_knn.hip, once.
+// The counter words, the gate, the statistics and the k-th distance below also serve the periodic walk (periodic_knn.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_thresholds.h"  // knn_gate_from_worst
 #include "owl/lbvh_device.h"
-#include "team_lanes.h"  // t_lane_read
+#include "team_lanes.h"  // t_lane_read, t_wave_sum
 
 namespace owlmi {
 
@@ -48,6 +50,23 @@ struct RadiusKnnKernelArgs {
 unsigned long long radius_knn_walks(const RadiusKnnKernelArgs &a, int cu_count, unsigned long long *h_words, hipStream_t s);
 
 namespace {
+
+// The gate of a list whose k-th entry lies at distance `kth` (FLT_MAX: fewer than k entries, the gate stays the radius's).  A
+// candidate beyond it is farther than r or farther than the k-th entry; one AT the k-th distance passes, the index decides.
+__device__ __forceinline__ float rknn_gate(float gate_r, float kth) { return fminf(gate_r, knn_gate_from_worst(kth)); }
+
+__device__ __forceinline__ void rknn_add_stats(unsigned long long *ws, int lane, unsigned long long total, unsigned long long full_rows,
+                                               unsigned long long node_tests, unsigned long long point_tests, unsigned long long tightened) {
+  const unsigned long long tsum = t_wave_sum(total), fsum = t_wave_sum(full_rows), nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests),
+                           tight = t_wave_sum(tightened);
+  if (lane == 0) {
+    if (tsum) atomicAdd(&ws[kRknnWsTotal], tsum);
+    if (fsum) atomicAdd(&ws[kRknnWsFullRows], fsum);
+    if (nt) atomicAdd(&ws[kRknnWsNodeTests], nt);
+    if (pt) atomicAdd(&ws[kRknnWsPointTests], pt);
+    if (tight) atomicAdd(&ws[kRknnWsTightened], tight);
+  }
+}
 
 // t_kth_dist (team_walk.h) with the register picked by masks instead of a chain of selects: the compiler turns that chain into a load
 // through a selected address, which keeps registers 1 .. NREG - 1 of the list in scratch (16 / 32 bytes for NREG = 3 / 4 in

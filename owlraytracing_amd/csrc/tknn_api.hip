@@ -1,10 +1,11 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h and include/owlknn_knn.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h and include/owlknn_periodic.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
 // current (a failure of that is TKNN_E_HIP, whatever else is wrong with the call), required pointers are checked, then the
 // engine's state (TKNN_E_STATE before tknnBuild), then values; a refused call has written nothing, its info included (info is zeroed once the arguments are
 // accepted); a message starts with the function's name and names the argument or the constraint.
+#include "periodic_metric.h"  // periodic_in_cell
 #include "trueknn_engine.h"
 
 #include <cmath>
@@ -340,6 +341,35 @@ int tknnKnn(tknnEngine e, const tknnKnnOptions *options, tknnKnnInfo *info, void
     c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
     zero(info);
     if (o.m > 0) e->impl.knn(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnPeriodicKnn(tknnEngine e, const tknnPeriodicKnnOptions *options, tknnPeriodicKnnInfo *info, void *stream) {
+  return api("tknnPeriodicKnn", e, [&](const Call &c) {
+    const tknnPeriodicKnnOptions &o = c.record(options);
+    c.need(o.d_idx, "d_idx");
+    if (!o.d_queries) {  // the set's own points
+      c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
+      c.require(!o.d_skip_ids, "d_queries is NULL (the set's own points): d_skip_ids must be NULL, every point is left out of its own row");
+    }
+    c.built();
+    c.require(o.k >= 1, "k must be positive");
+    c.count(o.m, "m");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
+    static const char *const axis[3] = {"x", "y", "z"};
+    for (int a = 0; a < 3; a++) {
+      if (!(o.period[a] >= 0.f) || !std::isfinite(o.period[a])) c.refuse(TKNN_E_ARG, std::string("period of axis ") + axis[a] + " must be finite and >= 0 (0: an open axis)");
+      if (o.period[a] > 0.f && !std::isfinite(o.lo[a])) c.refuse(TKNN_E_ARG, std::string("lo of the periodic axis ") + axis[a] + " must be finite");
+    }
+    if (!o.d_radii) c.positive(o.radius, "radius (FLT_MAX: none; or give d_radii)");
+    const float *scene = e->impl.scene();
+    for (int a = 0; a < 3; a++) {
+      if (!(o.period[a] > 0.f) || !(scene[a] <= scene[3 + a])) continue;  // (an open axis; a set of NaN points only: no box)
+      const bool inside = periodic_in_cell(scene[a], o.lo[a], o.period[a]) && periodic_in_cell(scene[3 + a], o.lo[a], o.period[a]);  // (then so is every point between)
+      if (!inside) c.refuse(TKNN_E_ARG, std::string("the built set does not lie in the cell on the periodic axis ") + axis[a] + " (nothing is wrapped for the caller)");
+    }
+    zero(info);
+    if (o.m > 0) e->impl.periodic_knn(o, info, (hipStream_t)stream);
   });
 }
 

@@ -10,6 +10,7 @@
 #include "lbvh.h"
 #include "owlknn.h"
 #include "owlknn_knn.h"
+#include "owlknn_periodic.h"
 
 namespace owlmi {
 
@@ -143,10 +144,14 @@ class Engine {
   // knn_seed.hip: the k nearest points, exactly, of m points that are not in the tree or (d_queries null) of the tree's own points,
   // with no radius from the caller (tknnKnn); m > 0
   void knn(const tknnKnnOptions &o, tknnKnnInfo *info, hipStream_t s);
+  // periodic_knn.hip: at most k nearest points under a per-axis periodic metric, with or without a radius, of m points that are
+  // not in the tree or (d_queries null) of the tree's own points (tknnPeriodicKnn); m > 0
+  void periodic_knn(const tknnPeriodicKnnOptions &o, tknnPeriodicKnnInfo *info, hipStream_t s);
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }
   int64_t size() const { return bvh_.size(); }
+  const float *scene() const { return scene_; }  // lo xyz, hi xyz of the built set, NaN points ignored (host copy)
   const Lbvh &tree() const { return bvh_; }
   const Lbvh &halo_tree() const { return halo_; }  // meaningful while has_halo()
 

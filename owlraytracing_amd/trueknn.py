@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _knn_lib, _lib
+from . import _knn_lib, _lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -513,6 +513,72 @@ class TrueKNN:
             opt.d_counts = _address(out["counts"])
             info = _knn_lib.KnnInfo()
             _lib.check(_knn_lib.load().tknnKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
+    def periodic_knn(self, queries=None, k=1, lo=(0, 0, 0), period=None, radius=None, radii=None, skip_ids=None, want_dist=True):
+        """At most ``k`` nearest points of the built set in a periodic cell, as dense rows (tknnPeriodicKnn): ``knn`` and
+        ``radius_knn`` under the wrapped distance.  The cell is ``lo`` and ``period`` (three values each; 2-D data: two, z stays
+        open); axis a is periodic iff period[a] > 0, 0 means open -- scipy's ``cKDTree(data, boxsize=L)`` is ``lo=0, period=L``.
+        Per axis a = |p - q| and w = min(a, |period - a|) on a periodic axis, the distance is sqrt((wx*wx + wy*wy) + wz*wz) in
+        fp32; row j holds the points with a finite distance <= r_j, ascending in (distance, index), cut after k and padded with
+        idx -1 / dist +inf.  The built set must lie in the cell on every periodic axis (nothing is wrapped for the caller); a
+        query outside the cell, or one with a NaN, has an empty row.  At most one of ``radius`` (one for all rows) and ``radii``
+        (length m; a row whose radius is NaN, not finite or <= 0 is empty) is given; neither: no radius, the exact k nearest.
+        ``queries``, ``skip_ids``: as ``knn`` takes them; without ``queries`` row j answers for point j of the built set, every
+        point left out of its own row.  Returns dict(idx (m,k) int32, dist (m,k) float32 [with ``want_dist``], counts (m,) int32,
+        info)."""
+        torch = self._torch
+        if period is None:
+            raise ValueError("periodic_knn: give the cell's periods (0 for an open axis)")
+        if radius is not None and radii is not None:
+            raise ValueError("periodic_knn: give at most one of radius and radii")
+        def triple(values, name):
+            v = np.atleast_1d(np.asarray(values, np.float64))
+            v = np.repeat(v, 3) if v.shape == (1,) else v
+            if v.shape not in ((2,), (3,)):
+                raise ValueError("periodic_knn: %s must have two or three values (or be one for all axes)" % name)
+            return [float(x) for x in v] + [0.0] * (3 - len(v))
+
+        cell = [triple(lo, "lo"), triple(period, "period")]
+        if queries is None:
+            if skip_ids is not None:
+                raise ValueError("periodic_knn: skip_ids go with queries (without queries every point is left out of its own row)")
+            m = self.n
+        else:
+            queries = self._queries(queries, "periodic_knn")
+            m = int(queries.shape[0])
+        k = int(k)
+
+        def column(values, dtype, name):
+            if isinstance(values, torch.Tensor) and values.device != self.device:
+                raise ValueError("periodic_knn: %s is on %s, the engine on %s" % (name, values.device, self.device))
+            values = torch.as_tensor(values, device=self.device).to(dtype).contiguous()
+            if values.shape != (m,):
+                raise ValueError("periodic_knn: %s must have one entry per query" % name)
+            return values
+
+        with torch.cuda.device(self.device):
+            radii = None if radii is None else column(radii, torch.float32, "radii")
+            skip_ids = None if skip_ids is None else column(skip_ids, torch.int32, "skip_ids")
+            rows = max(k, 0)
+            out = {"idx": torch.empty((m, rows), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((m, rows), dtype=torch.float32, device=self.device)
+            out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _periodic_lib.PeriodicKnnOptions()
+            opt.m, opt.k = m, k
+            opt.radius = float(np.finfo(np.float32).max) if radius is None else float(radius)
+            opt.lo, opt.period = (ctypes.c_float * 3)(*cell[0]), (ctypes.c_float * 3)(*cell[1])
+            opt.d_queries = None if queries is None else _address(queries, spare)
+            opt.d_radii = _address(radii, spare)
+            opt.d_skip_ids = _address(skip_ids, spare)
+            opt.d_idx = _address(out["idx"], spare)
+            opt.d_dist = _address(out.get("dist"))
+            opt.d_counts = _address(out["counts"])
+            info = _periodic_lib.PeriodicKnnInfo()
+            _lib.check(_periodic_lib.load().tknnPeriodicKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
         out["info"] = info.as_dict()
         return out
 
