@@ -44,7 +44,11 @@ class Lbvh {
   // xyz: device pointer to n packed fp32 triples (the reference's Sphere buffer, 12 B/point).
   // d_ids (optional): identity of each point as the caller wants it reported (e.g. a global index
   // when the buffer is one shard of a larger set); default is the position in d_xyz.
-  void build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, const int32_t *d_ids = nullptr);
+  // d_batch (optional): a label per point, 0 <= label < 2^batch_bits (the caller has checked them); the key of a point without
+  // a NaN becomes (label << (63 - batch_bits)) | (key >> batch_bits), so the points of a label are one range of sorted slots, in
+  // curve order inside (include/owlknn_batch.h).  Without it the build is what it always was.
+  void build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, const int32_t *d_ids = nullptr, const int32_t *d_batch = nullptr,
+                         int batch_bits = 0);
   // boxes: device pointer to n {lo[3],hi[3]} (24 B, owl::box3f) in caller primitive order.
   void build_from_boxes(const LbvhBox *d_boxes, int64_t n, hipStream_t stream);
   // same topology, new boxes (only for build_from_boxes trees)

@@ -130,6 +130,17 @@ __global__ void __launch_bounds__(kBlock) morton_kernel(const float *__restrict_
   order[i] = (uint32_t)i;
 }
 
+// batched point trees (Lbvh::build_from_points with labels): the label above the key's leading 63 - bits bits, which are the
+// point's cell at level 21 - bits / 3 of the same grid (the key is hierarchical); a NaN point keeps its key, bit 63 alone.  A
+// kernel of its own behind morton_kernel, so that the plain build's kernels are what they were.
+__global__ void __launch_bounds__(kBlock) batch_key_kernel(uint64_t *__restrict__ codes, const int32_t *__restrict__ batch, int64_t n, int bits) {
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t code = codes[i];
+  if (code >> 63) return;
+  codes[i] = ((uint64_t)(uint32_t)batch[i] << (63 - bits)) | (code >> bits);
+}
+
 template <bool POINTS>
 __global__ void __launch_bounds__(kBlock) gather_kernel(const float *__restrict__ xyz,
                                                        const LbvhBox *__restrict__ boxes, int64_t n,
@@ -497,7 +508,7 @@ void Lbvh::fit(hipStream_t stream) {
   OWLMI_HIP(hipGetLastError());
 }
 
-void Lbvh::build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, const int32_t *d_ids) {
+void Lbvh::build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, const int32_t *d_ids, const int32_t *d_batch, int batch_bits) {
   if (n <= 0 || n >= 0x7fffffffLL) throw HipError{"Lbvh: primitive count out of range"};
   built_ = false;  // until the last launch below has been issued without an error
   reserve(n);
@@ -510,6 +521,7 @@ void Lbvh::build_from_points(const float *d_xyz, int64_t n, hipStream_t stream, 
   hipLaunchKernelGGL(scene_final_kernel, dim3(1), dim3(kBlock), 0, stream, partials_, pb, scene_);
   hipLaunchKernelGGL(morton_kernel<true>, dim3(blocks_for(n)), dim3(kBlock), 0, stream, d_xyz,
                      (const LbvhBox *)nullptr, n, scene_, codes_, order_, curve_);
+  if (d_batch) hipLaunchKernelGGL(batch_key_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, stream, codes_, d_batch, n, batch_bits);
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipMemsetAsync(nan_count(), 0, sizeof(int32_t), stream));
   sort_and_tree(stream);

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h and include/owlknn_periodic.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h and include/owlknn_batch.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -53,6 +53,9 @@ struct Call {
   }
   void built() const {
     if (!e->impl.built()) refuse(TKNN_E_STATE, "call tknnBuild first");
+  }
+  void batched() const {
+    if (!e->impl.batched()) refuse(TKNN_E_STATE, "call tknnBuildBatched first (the engine's tree is not a batched one)");
   }
   void positive(float x, const char *name) const {
     if (!(x > 0.f) || !std::isfinite(x)) refuse(TKNN_E_ARG, std::string(name) + " must be finite and > 0");
@@ -370,6 +373,43 @@ int tknnPeriodicKnn(tknnEngine e, const tknnPeriodicKnnOptions *options, tknnPer
     }
     zero(info);
     if (o.m > 0) e->impl.periodic_knn(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnBuildBatched(tknnEngine e, const float *d_xyz, const int32_t *d_ids, const int32_t *d_batch, int32_t num_batches, int64_t n, tknnBuildInfo *info,
+                     void *stream) {
+  return api("tknnBuildBatched", e, [&](const Call &c) {
+    c.need(d_xyz, "d_xyz"), c.need(d_batch, "d_batch");
+    c.count(n, "n", 1);
+    c.require(num_batches >= 1, "num_batches must be positive");
+    if (num_batches > TKNN_MAX_BATCHES) c.refuse(TKNN_E_UNSUPPORTED, "num_batches out of range (1 .. " + std::to_string(TKNN_MAX_BATCHES) + ")");
+    e->impl.build_batched(d_xyz, d_ids, d_batch, num_batches, n, info, (hipStream_t)stream);
+  });
+}
+
+int tknnBatchLayout(tknnEngine e, int32_t *num_batches, int32_t *key_bits, int32_t *d_starts, void *stream) {
+  return api("tknnBatchLayout", e, [&](const Call &c) {
+    c.batched();
+    e->impl.batch_layout(num_batches, key_bits, d_starts, (hipStream_t)stream);
+  });
+}
+
+int tknnBatchKnn(tknnEngine e, const tknnBatchKnnOptions *options, tknnBatchKnnInfo *info, void *stream) {
+  return api("tknnBatchKnn", e, [&](const Call &c) {
+    const tknnBatchKnnOptions &o = c.record(options);
+    c.need(o.d_idx, "d_idx");
+    if (!o.d_queries) {  // the set's own points
+      c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
+      c.require(!o.d_skip_ids, "d_queries is NULL (the set's own points): d_skip_ids must be NULL, every point is left out of its own row");
+    }
+    c.require(!o.d_queries == !o.d_query_batch, "d_queries and d_query_batch go together: both given, or both NULL (the set's own points)");
+    c.batched();
+    c.require(o.k >= 1, "k must be positive");
+    c.count(o.m, "m");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_UNSUPPORTED);  // (the kernels keep their lists in registers)
+    if (!o.d_radii) c.positive(o.radius, "radius (FLT_MAX: none; or give d_radii)");
+    zero(info);
+    if (o.m > 0) e->impl.batch_knn(o, info, (hipStream_t)stream);
   });
 }
 

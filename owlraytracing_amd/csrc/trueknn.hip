@@ -305,6 +305,7 @@ Engine::~Engine() {
   if (counters_) (void)hipFree(counters_);
   if (halo_mask_) (void)hipFree(halo_mask_);
   if (slot_list_) (void)hipFree(slot_list_);
+  if (batch_starts_) (void)hipFree(batch_starts_);
   if (h_counters_) (void)hipHostFree(h_counters_);
   if (wave_ws_) (void)hipFree(wave_ws_);
   if (ev_a_) (void)hipEventDestroy(ev_a_);
@@ -359,8 +360,9 @@ LbvhView Engine::halo_view() const {
   return v;
 }
 
-void Engine::build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, hipStream_t s) {
+void Engine::build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, hipStream_t s, const int32_t *d_batch, int batch_bits) {
   OWLMI_HIP(hipEventRecord(ev_a_, s));
+  num_batches_ = 0;  // a plain tree until build_batched says otherwise
   halo_n_ = 0;
   boundary_valid_ = false;
   ids_given_ = d_ids != nullptr;
@@ -391,7 +393,7 @@ void Engine::build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuil
     state_cap_ = n;
   }
   try {
-    bvh_.build_from_points(d_xyz, n, s, d_ids);
+    bvh_.build_from_points(d_xyz, n, s, d_ids, d_batch, batch_bits);
   } catch (...) {
     bvh_.clear();
     throw;

@@ -9,6 +9,7 @@
 #include "knn_device.h"
 #include "lbvh.h"
 #include "owlknn.h"
+#include "owlknn_batch.h"
 #include "owlknn_knn.h"
 #include "owlknn_periodic.h"
 
@@ -111,7 +112,15 @@ class Engine {
   Engine(const Engine &) = delete;
   Engine &operator=(const Engine &) = delete;
 
-  void build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, hipStream_t s);
+  // d_batch, batch_bits: build_batched's (Lbvh::build_from_points); every build through here leaves a plain tree behind
+  void build(const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, hipStream_t s, const int32_t *d_batch = nullptr,
+             int batch_bits = 0);
+  // batch_knn.hip: a tree over num_batches labelled clouds, each one range of sorted slots (tknnBuildBatched); the labels are
+  // checked on the device first, one outside [0, num_batches) is an ArgError that leaves the engine without a tree
+  void build_batched(const float *d_xyz, const int32_t *d_ids, const int32_t *d_batch, int32_t num_batches, int64_t n, tknnBuildInfo *info,
+                     hipStream_t s);
+  // batch_knn.hip: the batches' ranges of sorted slots, num_batches + 1 words copied to d_starts (device; may be null)
+  void batch_layout(int32_t *num_batches, int32_t *key_bits, int32_t *d_starts, hipStream_t s);
   void set_halo(const float *d_xyz, const int32_t *d_ids, int64_t m, hipStream_t s);
   LbvhView halo_view() const;
   // halo_select.hip: my points inside any box of each peer, as 16-byte wire rows (count pass: d_rows == nullptr)
@@ -147,6 +156,10 @@ class Engine {
   // periodic_knn.hip: at most k nearest points under a per-axis periodic metric, with or without a radius, of m points that are
   // not in the tree or (d_queries null) of the tree's own points (tknnPeriodicKnn); m > 0
   void periodic_knn(const tknnPeriodicKnnOptions &o, tknnPeriodicKnnInfo *info, hipStream_t s);
+  // batch_knn.hip: at most k nearest points of the query's own batch, with or without a radius, of m labelled points that are
+  // not in the tree or (d_queries null) of the tree's own points (tknnBatchKnn); m > 0, the tree a batched one
+  void batch_knn(const tknnBatchKnnOptions &o, tknnBatchKnnInfo *info, hipStream_t s);
+  bool batched() const { return bvh_.built() && num_batches_ > 0; }
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }
@@ -200,6 +213,12 @@ class Engine {
   Lbvh bvh_;
   // the last build was given ids (tknnBuildIds with d_ids): neighbour lists then name points by id, not by input row
   bool ids_given_ = false;
+  // the last build was build_batched: the batches, the bits their labels take at the top of the keys, and the first sorted
+  // slot of each (num_batches_ + 1 words on the device; the last: the points without a NaN).  0 batches: a plain tree.
+  int32_t num_batches_ = 0;
+  int batch_bits_ = 0;
+  int32_t *batch_starts_ = nullptr;
+  int64_t batch_starts_cap_ = 0;
   Lbvh halo_;
   int64_t halo_n_ = 0;
   // A phase-1 solve (queries no halo point can reach) runs beside the halo exchange: tknnSetHalo may rebuild

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _knn_lib, _lib, _periodic_lib
+from . import _batch_lib, _knn_lib, _lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -106,21 +106,59 @@ class TrueKNN:
         if not t.is_contiguous():
             raise ValueError("%s: %s must be contiguous (it is written in place)" % (who, what))
 
-    def build(self, points, ids=None):
+    def build(self, points, ids=None, batch=None, num_batches=None):
         """LBVH over the points.  ``ids`` (optional int32) are the identities reported in neighbour
-        lists (global indices when these points are one tile of a larger set)."""
+        lists (global indices when these points are one tile of a larger set).
+        ``batch`` (optional, (n,) int32 labels, numpy or a tensor on the engine's device, in any order): the points are
+        ``num_batches`` clouds in one tree (tknnBuildBatched) -- every call treats the tree as one set but ``batch_knn``,
+        which looks for neighbours inside a query's own cloud.  ``num_batches`` defaults to the largest label + 1."""
         torch = self._torch
         points = self._points(points)
         ids = self._ids(ids, points.shape[0])
         info = _lib.BuildInfo()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.tknnBuildIds(self._h, ctypes.c_void_p(points.data_ptr()),
-                                              None if ids is None else ctypes.c_void_p(ids.data_ptr()),
-                                              points.shape[0], ctypes.byref(info), self._stream()))
+        if batch is None:
+            if num_batches is not None:
+                raise ValueError("build: num_batches goes with batch")
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.tknnBuildIds(self._h, ctypes.c_void_p(points.data_ptr()),
+                                                  None if ids is None else ctypes.c_void_p(ids.data_ptr()),
+                                                  points.shape[0], ctypes.byref(info), self._stream()))
+        else:
+            with torch.cuda.device(self.device):
+                batch = self._labels(batch, points.shape[0], "build", "batch", "point")
+                if num_batches is None:
+                    num_batches = int(batch.max()) + 1  # (a negative label is refused by the library)
+                _lib.check(_batch_lib.load().tknnBuildBatched(self._h, ctypes.c_void_p(points.data_ptr()),
+                                                              None if ids is None else ctypes.c_void_p(ids.data_ptr()),
+                                                              ctypes.c_void_p(batch.data_ptr()), int(num_batches), points.shape[0],
+                                                              ctypes.byref(info), self._stream()))
         self.n = int(points.shape[0])
         self.halo_n = 0  # a build drops the halo tree
         self.build_info = info.as_dict()
         return self.build_info
+
+    def _labels(self, values, count, who, name, per):
+        """Batch labels as the library takes them: a contiguous int32 (count,) tensor on the engine's device."""
+        torch = self._torch
+        if isinstance(values, torch.Tensor) and values.device != self.device:
+            raise ValueError("%s: %s is on %s, the engine on %s" % (who, name, values.device, self.device))
+        values = torch.as_tensor(values, device=self.device).to(torch.int32).contiguous()
+        if values.shape != (count,):
+            raise ValueError("%s: %s must have one entry per %s" % (who, name, per))
+        return values
+
+    def batch_layout(self):
+        """What the last batched ``build`` made (tknnBatchLayout): dict(num_batches, key_bits, starts) -- ``starts`` a
+        (num_batches + 1,) int32 tensor on the engine's device, batch b being the sorted slots starts[b] .. starts[b + 1] - 1
+        of the tree and starts[num_batches] the number of points without a NaN."""
+        torch = self._torch
+        lib = _batch_lib.load()
+        nb, bits = ctypes.c_int32(0), ctypes.c_int32(0)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.tknnBatchLayout(self._h, ctypes.byref(nb), ctypes.byref(bits), None, self._stream()))
+            starts = torch.empty((nb.value + 1,), dtype=torch.int32, device=self.device)
+            _lib.check(lib.tknnBatchLayout(self._h, None, None, ctypes.c_void_p(starts.data_ptr()), self._stream()))
+        return {"num_batches": int(nb.value), "key_bits": int(bits.value), "starts": starts}
 
     def set_halo(self, points=None, ids=None):
         """Second point set every query also searches (border points of neighbouring tiles)."""
@@ -582,6 +620,65 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def batch_knn(self, queries=None, k=1, batch=None, radius=None, radii=None, skip_ids=None, want_dist=True):
+        """At most ``k`` nearest points of the query's own batch, as dense rows (tknnBatchKnn), on a tree built with
+        ``build(points, batch=...)``: ``knn`` and ``radius_knn`` among the points that carry the query's label -- what
+        torch-cluster's ``knn(x, y, k, batch_x, batch_y)`` and ``radius(..., batch_x, batch_y, max_num_neighbors)`` answer.
+        Row j holds the points p with batch[p] == batch[j] whose fp32 distance sqrt((dx*dx + dy*dy) + dz*dz) is finite and
+        <= r_j, ascending in (distance, index), cut after k and padded with idx -1 / dist +inf.  ``queries`` (numpy (m,2|3) or
+        a contiguous float32 CUDA tensor (m,3)) come with ``batch`` ((m,) int32 labels); a query with a NaN, with a label no
+        batch has, or in an empty batch has an empty row.  At most one of ``radius`` (one for all rows) and ``radii`` (length
+        m; a row whose radius is NaN, not finite or <= 0 is empty) is given; neither: no radius, the exact k nearest of the
+        batch.  ``skip_ids``: as ``knn`` takes them.  Without ``queries`` (and ``batch``) row j answers for point j of the built
+        set in its own batch, every point left out of its own row.  Returns dict(idx (m,k) int32, dist (m,k) float32 [with
+        ``want_dist``], counts (m,) int32, info)."""
+        torch = self._torch
+        if radius is not None and radii is not None:
+            raise ValueError("batch_knn: give at most one of radius and radii")
+        if (queries is None) != (batch is None):
+            raise ValueError("batch_knn: queries and batch go together (neither: the set's own points)")
+        if queries is None:
+            if skip_ids is not None:
+                raise ValueError("batch_knn: skip_ids go with queries (without queries every point is left out of its own row)")
+            m = self.n
+        else:
+            queries = self._queries(queries, "batch_knn")
+            m = int(queries.shape[0])
+        k = int(k)
+
+        def column(values, dtype, name):
+            if isinstance(values, torch.Tensor) and values.device != self.device:
+                raise ValueError("batch_knn: %s is on %s, the engine on %s" % (name, values.device, self.device))
+            values = torch.as_tensor(values, device=self.device).to(dtype).contiguous()
+            if values.shape != (m,):
+                raise ValueError("batch_knn: %s must have one entry per query" % name)
+            return values
+
+        with torch.cuda.device(self.device):
+            batch = None if batch is None else self._labels(batch, m, "batch_knn", "batch", "query")
+            radii = None if radii is None else column(radii, torch.float32, "radii")
+            skip_ids = None if skip_ids is None else column(skip_ids, torch.int32, "skip_ids")
+            rows = max(k, 0)
+            out = {"idx": torch.empty((m, rows), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((m, rows), dtype=torch.float32, device=self.device)
+            out["counts"] = torch.empty((m,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _batch_lib.BatchKnnOptions()
+            opt.m, opt.k = m, k
+            opt.radius = float(np.finfo(np.float32).max) if radius is None else float(radius)
+            opt.d_queries = None if queries is None else _address(queries, spare)
+            opt.d_query_batch = _address(batch, spare)
+            opt.d_radii = _address(radii, spare)
+            opt.d_skip_ids = _address(skip_ids, spare)
+            opt.d_idx = _address(out["idx"], spare)
+            opt.d_dist = _address(out.get("dist"))
+            opt.d_counts = _address(out["counts"])
+            info = _batch_lib.BatchKnnInfo()
+            _lib.check(_batch_lib.load().tknnBatchKnn(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -726,6 +823,28 @@ def knn_graph(points, k, loop=False):
     numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
     points = pad_to_3d(np.asarray(points, np.float32))
     return knn(points, points if loop else None, k)
+
+
+def batch_knn(points, batch_x, queries, batch_y, k, **kw):
+    """One-shot helper: build over ``points`` with the labels ``batch_x``, at most ``k`` nearest points of ``queries`` among the
+    points that carry their label ``batch_y`` (TrueKNN.batch_knn; torch-cluster's ``knn(x, y, k, batch_x, batch_y)``), results as
+    numpy arrays.  ``queries`` and ``batch_y`` None: the points' own rows."""
+    eng = TrueKNN()
+    try:
+        eng.build(points, batch=batch_x)
+        res = {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in eng.batch_knn(queries, k, batch=batch_y, **kw).items()}
+        res["build_info"] = eng.build_info
+        return res
+    finally:
+        eng.close()
+
+
+def batch_knn_graph(points, batch, k, loop=False):
+    """One-shot helper: for every point of ``points`` its ``k`` nearest other points of its own batch, exactly (torch-cluster's
+    ``knn_graph(x, k, batch, loop)``); with ``loop`` the points are queries like any others, so the point itself is an entry, at
+    distance 0.  Results as numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
+    points = pad_to_3d(np.asarray(points, np.float32))
+    return batch_knn(points, batch, points if loop else None, batch if loop else None, k)
 
 
 def dbscan_query(points, queries, eps, min_pts):
