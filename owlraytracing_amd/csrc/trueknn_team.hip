@@ -602,13 +602,16 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
     // One gather may serve MORE than the step it is made for: when the queries are unlikely all to finish inside the step
     // (levels level .. level+m-1), the walk is made at the radius of the level after it ("extension"), and every block a
     // query needs is listed either at the front of its list (needed inside the step) or at its back (needed at the
-    // extension level only).  The step's passes work on the front parts; the next turn of the level loop then finds its
-    // lists in LDS (`reuse`) and runs its passes without a walk of its own -- at BASELINE config 2 (levels 0 and 1 share a
-    // step, 59 % of the queries go on to level 2) one pyramid walk per packet instead of two.  A packet whose extended
-    // lists do not fit walks again for the step alone.
+    // extension level only).  The step's COUNT pass works on the front parts; its SELECT pass serves the queries that finish
+    // inside the step on their front parts and, on their whole lists, those that go on to the extension level with enough
+    // others to finish there almost surely (see the passes) -- at BASELINE config 2 (levels 0 and 1 share a step, 59 % of
+    // the queries go on to level 2) one pyramid walk and one SELECT pass per packet instead of two of each.  Queries that pass
+    // has not served find their lists in LDS in the next turn of the level loop (`reuse`), which runs its passes without a
+    // walk of its own.  A packet whose extended lists do not fit walks again for the step alone.
     bool reuse = false;          // wave-uniform: this level's lists are in LDS already
     int ext_next = a.first_ext;  // wave-uniform: extend the next gather
     bool ext_ok = a.first_ext >= 0;  // ... no more for this packet once its extended lists did not fit (its boxes only grow); < 0: never
+    bool served = false;         // per lane, for a `reuse` turn: the step's SELECT pass has served me at this level already
     for (;;) {  // radius levels
       PHASE_END(4);
       // ---- 1. query records, conservative query boxes ---------------------------------------
@@ -915,13 +918,20 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       // count all m nested boxes in one pass, pick the first level with >= k others, select there.
       // A row is written only when its query really has >= k others in the chosen box, so neither
       // speculation nor level grouping can change a result.
-      const bool speculate = m == 1 && active && level > 0 && prev_others * 8u >= (uint32_t)(a.k + a.k / 2);
-      const bool count_first = active && !speculate;
+      // A gather with an extension has the lists of the level after the step at hand, so an unfinished query that would
+      // speculate at that level in the next turn does so NOW: it joins the step's SELECT pass with its whole list and the
+      // extension level's radius (fin_at = m).  If that serves every query still active, the `reuse` turn is not run at all:
+      // one round of the teams and one turn's bookkeeping less per packet.  If not (a query with hardly any others yet, a
+      // speculation at the step's own level that failed) the turn runs for the queries left over, `served` keeping the
+      // others out of its passes.  (`reuse` is set here exactly when this turn's gather has an extension.)
+      const bool speculate = m == 1 && active && !served && level > 0 && prev_others * 8u >= (uint32_t)(a.k + a.k / 2);
+      const bool count_first = active && !served && !speculate;
+      served = false;  // (set only on the way into a `reuse` turn)
       // The four teams of a pass step through their lists in lockstep, so a group of four queries
       // costs the longest of its lists: the pass lists are ordered by list length (buckets of 4
       // blocks), which lifts the teams' occupancy from ~77 % to ~95 % on uniform data.
-      auto build_qlist = [&](bool sel) -> int {
-        const int bucket = my_nblk >> 2;  // <= kMaxPerQuery / 4 < 32
+      auto build_qlist = [&](bool sel, int nblk) -> int {
+        const int bucket = nblk >> 2;  // <= kMaxPerQuery / 4 < 32
         if (lane == 0) qlist[64] = 0;
         t_wave_sync();
         if (sel) __hip_atomic_fetch_or((uint32_t *)&qlist[64], 1u << bucket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -941,7 +951,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         return base;
       };
       {
-        const int n_count = build_qlist(count_first);
+        const int n_count = build_qlist(count_first, my_nblk);
         if (!(TKNN_DIAG_BUILD && (a.diag & 4))) {
           if (m > 1)
             team_pass<false, HALO, NREG, false, true>(a, L, n_count, g * 64, own_pts, halo_pts, lane);
@@ -951,7 +961,8 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         t_wave_sync();
       }
       PHASE_END(2);
-      // first level of the step at which I have >= k others (deviceCode.cu:118), -1 if none
+      // first level of the step at which I have >= k others (deviceCode.cu:118), -1 if none; m: none, and the SELECT pass
+      // serves me at the extension level
       uint32_t c0 = 0, c1 = 0, selfc = 0;
       int fin_at = -1;
       if (count_first) {
@@ -964,37 +975,58 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         else if (m > 1 && c1 - selfc >= (uint32_t)a.k)
           fin_at = 1;
       }
+      int sel_nblk = my_nblk;
+      if (reuse && a.merge_ext && count_first && fin_at < 0 && ((m > 1 ? c1 : c0) - selfc) * 8u >= (uint32_t)(a.k + a.k / 2)) {  // the rule of `speculate`, a turn early
+        // my whole list, as the `reuse` turn would have it: front + back | own position | front length << 16 (bits 24..31
+        // keep the back part's length until the statistics below have read it), and that level's radius
+        fin_at = m;
+        const int pk = __float_as_int(qrec[lane * kQrecStride + 5]);
+        sel_nblk = (pk & 0xff) + ((pk >> 24) & 0xff);
+        qrec[lane * kQrecStride + 4] = qrec[lane * kQrecStride + 4] * 2.0f;
+        qrec[lane * kQrecStride + 5] = __int_as_float(sel_nblk | (pk & 0xff00) | ((pk & 0xff) << 16) | (pk & (int)0xff000000u));
+      }
       const bool select_now = speculate || fin_at >= 0;
       if (m > 1 && fin_at == 0) qrec[lane * kQrecStride + 4] = r_in0;  // finishing inside the step: SELECT works in the inner box
       {
         t_wave_sync();
-        const int n_select = build_qlist(select_now);
+        const int n_select = build_qlist(select_now, sel_nblk);
         if (!(TKNN_DIAG_BUILD && (a.diag & 2))) team_pass<true, HALO, NREG, FULL, false>(a, L, n_select, g * 64, own_pts, halo_pts, lane);
         t_wave_sync();
       }
       PHASE_END(3);
-      bool finished = fin_at >= 0;
-      uint32_t last_others = 0;
+      const bool ext_sel = fin_at == m;  // served at the extension level
+      bool finished = fin_at >= 0 && !ext_sel;
+      uint32_t last_others = prev_others;  // (a query served a turn ago keeps its count)
       if (speculate) {
         c0 = qcnt[lane * 2 + 0];
         selfc = qcnt[lane * 2 + 1] >> 31;
         finished = c0 - selfc >= (uint32_t)a.k;
         fin_at = finished ? 0 : -1;
       }
+      uint32_t c_ext = 0, n_back = 0;  // candidates in my box at the extension level; blocks of my list it alone needs
+      if (ext_sel) {
+        c_ext = qcnt[lane * 2 + 0];
+        finished = c_ext - selfc >= (uint32_t)a.k;
+        // (should the `reuse` turn run for others, it reads a list without a back part for me)
+        const int pk = __float_as_int(qrec[lane * kQrecStride + 5]);
+        n_back = ((uint32_t)pk >> 24) & 0xffu;
+        qrec[lane * kQrecStride + 5] = __int_as_float(pk & 0x00ffffff);
+      }
       int levels_run = 0;
-      if (active) {
-        levels_run = finished ? fin_at + 1 : m;
+      if (count_first || speculate) {  // (every active query but those served a turn ago)
+        levels_run = finished || ext_sel ? fin_at + 1 : m;
         isect += c0;
-        if (levels_run > 1) isect += c1;
+        if (levels_run > 1) isect += c1;  // (0 in a one-level step)
+        isect += c_ext;
         my_levels += (uint32_t)levels_run;
-        last_others = (m > 1 ? c1 : c0) - selfc;
+        last_others = ext_sel ? c_ext - selfc : (m > 1 ? c1 : c0) - selfc;
         prev_others = last_others;
       }
       wave_levels = max(wave_levels, (int)t_wave_max((float)(active ? level + levels_run : 0)));
       {
         // exact box tests executed for my query: LBVH_BLOCK per listed block and pass
         const unsigned long long passes = (count_first ? 1ull : 0ull) + (select_now ? 1ull : 0ull);
-        wave_point_tests += t_wave_sum(active ? (unsigned long long)my_nblk * LBVH_BLOCK * passes : 0ull);
+        wave_point_tests += t_wave_sum(((unsigned long long)my_nblk * passes + n_back) * LBVH_BLOCK);
       }
       if (finished) {
         // the team wrote the row (SELECT pass); the counter and the level come from the query's lane
@@ -1006,14 +1038,23 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         if ((qcnt[lane * 2 + 1] >> 30) & 1u) knn_flag_tie(a.tie, a.tie_list, a.counters, slot, fin_level, 2);  // SELECT saw exact-distance ties
       }
       active = active && !finished;
-      level += m;
+      int m_done = m;  // levels behind the packet after this turn
+      if (reuse && a.merge_ext) {
+        if (__ballot(active && !ext_sel) == 0ull) {
+          m_done = m + 1;  // the extension level is served: no turn of its own
+          reuse = false;
+        } else {
+          served = ext_sel;
+        }
+      }
+      level += m_done;
       t_wave_sync();
       if (__ballot(active) == 0ull) break;
       if (level >= a.max_rounds) {
         if (!a.allow_unfinished) wave_err |= 1;
         break;
       }
-      for (int j = 0; j < m; j++) r = r * 2.0f;  // hostCode.cpp:321
+      for (int j = 0; j < m_done; j++) r = r * 2.0f;  // hostCode.cpp:321
       // how many levels the next gather should serve: the box grows 8x per level; group levels as
       // long as even the best-off unfinished query is unlikely to collect k others
       {
@@ -1110,6 +1151,8 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     for (int t = 1; t < std::min(a.first_step, kMaxStep); t++) radius *= 2.0f;
     a.first_ext = !sa.d_start_radii && expected_box_population(radius) < 2.5 * sa.k ? 1 : 0;
     if (const char *e = getenv("TKNN_TEAM_EXT")) a.first_ext = atoi(e) > 0 ? a.first_ext : -1;  // measurements: 0 = no extended gathers at all
+    a.merge_ext = 1;
+    if (const char *e = getenv("TKNN_TEAM_MERGE")) a.merge_ext = atoi(e) > 0 ? 1 : 0;  // measurements and tests: 0 = the extension level in a turn of its own
   }
   {
     // axes along which the built points differ at all (2-D inputs carry z = 0, hostCode.cpp:115-118);
