@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h and include/owlknn_batch.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h and include/owlknn_emst.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -411,6 +411,19 @@ int tknnBatchKnn(tknnEngine e, const tknnBatchKnnOptions *options, tknnBatchKnnI
     zero(info);
     if (o.m > 0) e->impl.batch_knn(o, info, (hipStream_t)stream);
   });
+}
+
+int tknnEmst(tknnEngine e, const tknnEmstOptions *options, tknnEmstInfo *info, void *stream) {
+  const int rc = api("tknnEmst", e, [&](const Call &c) {
+    const tknnEmstOptions &o = c.record(options);
+    if (e->impl.built() && e->impl.size() > 1) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v");
+    c.built();
+    c.count(e->impl.size(), "n", 1);
+    zero(info);
+    e->impl.emst(o, info, (hipStream_t)stream);
+  });
+  if (rc == TKNN_E_ROUNDS) g_last_error = "tknnEmst: max_rounds reached with components still merging (nothing was written)";
+  return rc;
 }
 
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,

@@ -10,6 +10,7 @@
 #include "lbvh.h"
 #include "owlknn.h"
 #include "owlknn_batch.h"
+#include "owlknn_emst.h"
 #include "owlknn_knn.h"
 #include "owlknn_periodic.h"
 
@@ -159,6 +160,9 @@ class Engine {
   // batch_knn.hip: at most k nearest points of the query's own batch, with or without a radius, of m labelled points that are
   // not in the tree or (d_queries null) of the tree's own points (tknnBatchKnn); m > 0, the tree a batched one
   void batch_knn(const tknnBatchKnnOptions &o, tknnBatchKnnInfo *info, hipStream_t s);
+  // emst.hip: the minimum spanning forest of the tree's own points, Euclidean or under the caller's core distances, in Boruvka
+  // rounds (tknnEmst); throws RoundsExceeded, with info filled and nothing written, when max_rounds rounds do not finish it
+  void emst(const tknnEmstOptions &o, tknnEmstInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _knn_lib, _lib, _periodic_lib
+from . import _batch_lib, _emst_lib, _knn_lib, _lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -554,6 +554,47 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def emst(self, core_dist=None, want_components=False, max_rounds=0):
+        """The minimum spanning forest of the built set (tknnEmst): Euclidean, or with ``core_dist`` ((n,) float32 by row, numpy or
+        a contiguous tensor on the engine's device) under the mutual-reachability distance max(d, core[i], core[j]).  Edges are
+        ordered by (bits of the fp32 weight, smaller name, larger name) -- names are ids on trees built with ids, rows otherwise
+        --, which makes the forest unique; a point with a NaN coordinate, or whose core distance is not finite and >= 0, is in
+        no edge.  Returns dict(u, v (edges,) int32 with u < v, w (edges,) float32, ascending by that key, edges, info[,
+        components (n,) int32: the smallest row of the point's component, -1 for a point left out]).  ``max_rounds`` > 0 ends the
+        Boruvka rounds early with TknnError (TKNN_E_ROUNDS); the default, and the most that is taken, is ceil(log2 n) + 1."""
+        torch = self._torch
+        n = self.n
+        with torch.cuda.device(self.device):
+            if core_dist is not None:
+                if isinstance(core_dist, np.ndarray):
+                    core_dist = torch.from_numpy(np.ascontiguousarray(core_dist, dtype=np.float32)).to(self.device)
+                if not isinstance(core_dist, torch.Tensor):
+                    raise ValueError("emst: core_dist must be a numpy array or a torch tensor")
+                if core_dist.dtype != torch.float32 or tuple(core_dist.shape) != (n,):
+                    raise ValueError("emst: core_dist must be float32 (n,), got %s %s" % (core_dist.dtype, tuple(core_dist.shape)))
+                if core_dist.device != self.device:
+                    raise ValueError("emst: core_dist is on %s, the engine on %s" % (core_dist.device, self.device))
+                if not core_dist.is_contiguous():
+                    raise ValueError("emst: core_dist must be contiguous")
+            rows = max(n - 1, 0)
+            u = torch.empty((rows,), dtype=torch.int32, device=self.device)
+            v = torch.empty((rows,), dtype=torch.int32, device=self.device)
+            w = torch.empty((rows,), dtype=torch.float32, device=self.device)
+            comp = torch.empty((n,), dtype=torch.int32, device=self.device) if want_components else None
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _emst_lib.EmstOptions()
+            opt.d_core_dist = _address(core_dist, spare)
+            opt.d_u, opt.d_v, opt.d_w = _address(u, spare), _address(v, spare), _address(w, spare)
+            opt.d_component = _address(comp, spare)
+            opt.max_rounds = int(max_rounds)
+            info = _emst_lib.EmstInfo()
+            _lib.check(_emst_lib.load().tknnEmst(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        edges = int(info.edges)
+        out = {"u": u[:edges], "v": v[:edges], "w": w[:edges], "edges": edges, "info": info.as_dict()}
+        if want_components:
+            out["components"] = comp
+        return out
+
     def periodic_knn(self, queries=None, k=1, lo=(0, 0, 0), period=None, radius=None, radii=None, skip_ids=None, want_dist=True):
         """At most ``k`` nearest points of the built set in a periodic cell, as dense rows (tknnPeriodicKnn): ``knn`` and
         ``radius_knn`` under the wrapped distance.  The cell is ``lo`` and ``period`` (three values each; 2-D data: two, z stays
@@ -823,6 +864,30 @@ def knn_graph(points, k, loop=False):
     numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
     points = pad_to_3d(np.asarray(points, np.float32))
     return knn(points, points if loop else None, k)
+
+
+def emst(points, **kw):
+    """One-shot helper: build over ``points``, their Euclidean minimum spanning tree (TrueKNN.emst), results as numpy arrays."""
+    return _one_shot(points, lambda eng: eng.emst(**kw))
+
+
+def mutual_reachability_mst(points, min_samples, **kw):
+    """One-shot helper: the minimum spanning tree of ``points`` under the mutual-reachability distance, the input of HDBSCAN's
+    linkage step.  A point's core distance is the distance to its ``(min_samples - 1)``-th nearest OTHER point, the last
+    column of TrueKNN.knn(k = min_samples - 1) -- sklearn's convention, where a point counts itself; ``min_samples`` = 1 is
+    the plain Euclidean tree.  A point with fewer than min_samples - 1 other points in reach has an infinite core distance and
+    is in no edge.  Results as numpy arrays, ``core_dist`` among them."""
+    min_samples = int(min_samples)
+    if min_samples < 1:
+        raise ValueError("mutual_reachability_mst: min_samples must be >= 1")
+
+    def call(eng):
+        if min_samples == 1:
+            return eng.emst(**kw)
+        core = eng.knn(k=min_samples - 1)["dist"][:, -1].contiguous()
+        return dict(eng.emst(core_dist=core, **kw), core_dist=core)
+
+    return _one_shot(points, call)
 
 
 def batch_knn(points, batch_x, queries, batch_y, k, **kw):
