@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h and include/owlknn_emst.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -424,6 +424,50 @@ int tknnEmst(tknnEngine e, const tknnEmstOptions *options, tknnEmstInfo *info, v
   });
   if (rc == TKNN_E_ROUNDS) g_last_error = "tknnEmst: max_rounds reached with components still merging (nothing was written)";
   return rc;
+}
+
+// the forest of tknnLinkage and tknnHdbscanLabels
+static void need_forest(const Call &c, int64_t n, int64_t edges) {
+  c.require(n >= 1 && n < (1ll << 30), "need 1 <= n < 2^30");
+  c.require(edges >= 0 && edges <= n - 1, "need 0 <= edges <= n - 1 (a forest)");
+}
+
+int tknnLinkage(tknnEngine e, const tknnLinkageOptions *options, tknnLinkageInfo *info, void *stream) {
+  return api("tknnLinkage", e, [&](const Call &c) {
+    const tknnLinkageOptions &o = c.record(options);
+    if (o.edges > 0) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v");
+    c.require(o.d_parent || o.d_left || o.d_right || o.d_size, "need one of d_parent, d_left, d_right, d_size");
+    need_forest(c, o.n, o.edges);
+    zero(info);
+    e->impl.linkage(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnHdbscanLabels(tknnEngine e, const tknnHdbscanLabelsOptions *options, tknnHdbscanLabelsInfo *info, void *stream) {
+  return api("tknnHdbscanLabels", e, [&](const Call &c) {
+    const tknnHdbscanLabelsOptions &o = c.record(options);
+    c.need(o.d_labels, "d_labels");
+    if (o.edges > 0) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v"), c.need(o.d_w, "d_w");
+    need_forest(c, o.n, o.edges);
+    c.require(o.min_cluster_size >= 2, "min_cluster_size must be >= 2");
+    zero(info);
+    e->impl.hdbscan_labels(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnHdbscan(tknnEngine e, const tknnHdbscanOptions *options, tknnHdbscanInfo *info, void *stream) {
+  return api("tknnHdbscan", e, [&](const Call &c) {
+    const tknnHdbscanOptions &o = c.record(options);
+    c.need(o.d_labels, "d_labels");
+    c.built();
+    c.require(e->impl.size() < (1ll << 30), "need n < 2^30");
+    c.require(o.min_cluster_size >= 2, "min_cluster_size must be >= 2");
+    c.require(o.min_samples >= 1, "min_samples must be >= 1");
+    if (o.min_samples - 1 > TKNN_MAX_K_REGISTERS)
+      c.refuse(TKNN_E_UNSUPPORTED, "min_samples out of range (1 .. " + std::to_string(TKNN_MAX_K_REGISTERS + 1) + ": the core distances are tknnKnn's)");
+    zero(info);
+    e->impl.hdbscan(o, info, (hipStream_t)stream);
+  });
 }
 
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,

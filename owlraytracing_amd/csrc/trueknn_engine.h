@@ -11,6 +11,7 @@
 #include "owlknn.h"
 #include "owlknn_batch.h"
 #include "owlknn_emst.h"
+#include "owlknn_hdbscan.h"
 #include "owlknn_knn.h"
 #include "owlknn_periodic.h"
 
@@ -163,6 +164,12 @@ class Engine {
   // emst.hip: the minimum spanning forest of the tree's own points, Euclidean or under the caller's core distances, in Boruvka
   // rounds (tknnEmst); throws RoundsExceeded, with info filled and nothing written, when max_rounds rounds do not finish it
   void emst(const tknnEmstOptions &o, tknnEmstInfo *info, hipStream_t s);
+  // linkage.hip: the single-linkage dendrogram of a sorted forest, in contraction rounds (tknnLinkage); needs no tree
+  void linkage(const tknnLinkageOptions &o, tknnLinkageInfo *info, hipStream_t s);
+  // hdbscan.hip: HDBSCAN's labels of a sorted forest (tknnHdbscanLabels; needs no tree), and the pipeline on the built set: knn for
+  // the core distances, emst under them, the labels of its records (tknnHdbscan)
+  void hdbscan_labels(const tknnHdbscanLabelsOptions &o, tknnHdbscanLabelsInfo *info, hipStream_t s);
+  void hdbscan(const tknnHdbscanOptions &o, tknnHdbscanInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _knn_lib, _lib, _periodic_lib
+from . import _batch_lib, _emst_lib, _hdbscan_lib, _knn_lib, _lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -595,6 +595,140 @@ class TrueKNN:
             out["components"] = comp
         return out
 
+    def _records(self, who, u, v, w, n, need_w):
+        """The records (u, v, w) of ``who`` as the library takes them: contiguous int32 / int32 / float32 tensors of one length on
+        the engine's device (numpy is uploaded); at most n - 1 of them."""
+        torch = self._torch
+        out = []
+        for name, t, dtype in (("u", u, torch.int32), ("v", v, torch.int32), ("w", w, torch.float32)):
+            if t is None and name == "w" and not need_w:
+                out.append(None)
+                continue
+            if isinstance(t, np.ndarray):
+                t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32 if dtype == torch.int32 else np.float32)).to(self.device)
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s: %s must be a numpy array or a torch tensor" % (who, name))
+            if t.dtype != dtype or t.dim() != 1 or (out and t.shape != out[0].shape):
+                raise ValueError("%s: u, v must be int32 and w float32, all (edges,); got %s %s %s" % (who, name, t.dtype, tuple(t.shape)))
+            if t.device != self.device:
+                raise ValueError("%s: %s is on %s, the engine on %s" % (who, name, t.device, self.device))
+            if not t.is_contiguous():
+                raise ValueError("%s: %s must be contiguous" % (who, name))
+            out.append(t)
+        n = int(n)
+        if n < 1 or out[0].shape[0] > n - 1:
+            raise ValueError("%s: a forest over n >= 1 vertices has at most n - 1 records" % who)
+        return out[0], out[1], out[2], n
+
+    def _linkage_arrays(self, n, edges):
+        torch = self._torch
+        return {"parent": torch.empty((n + edges,), dtype=torch.int32, device=self.device),
+                "left": torch.empty((edges,), dtype=torch.int32, device=self.device),
+                "right": torch.empty((edges,), dtype=torch.int32, device=self.device),
+                "size": torch.empty((edges,), dtype=torch.int32, device=self.device)}
+
+    def linkage(self, u, v, w=None, n=None, max_rounds=0):
+        """The single-linkage dendrogram of a sorted forest (tknnLinkage): the records (u[i], v[i]) over the vertices 0 .. n-1 in
+        the order ``emst`` returns them (``n`` defaults to the built set's size; no tree is needed).  The nodes are the leaves and
+        n + i for record i.  Returns dict(parent (n + edges,), left, right, size (edges,) int32, info[, w]): parent -1 at roots,
+        left < right the children of node n + i, size its leaves; with the weights of a spanning tree ``linkage_matrix`` turns the
+        result into scipy's Z.  After ``max_rounds`` contraction rounds (default 64) the rest is finished on the host, with the
+        same result (info["host_edges"])."""
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            u, v, w, n = self._records("linkage", u, v, w, self.n if n is None else n, False)
+            edges = int(u.shape[0])
+            out = self._linkage_arrays(n, edges)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _hdbscan_lib.LinkageOptions()
+            opt.n, opt.edges, opt.max_rounds = n, edges, int(max_rounds)
+            opt.d_u, opt.d_v, opt.d_w = _address(u, spare), _address(v, spare), _address(w, spare)
+            opt.d_parent = _address(out["parent"], spare)
+            opt.d_left, opt.d_right, opt.d_size = _address(out["left"], spare), _address(out["right"], spare), _address(out["size"], spare)
+            info = _hdbscan_lib.LinkageInfo()
+            _lib.check(_hdbscan_lib.load().tknnLinkage(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        if w is not None:
+            out["w"] = w
+        return out
+
+    def hdbscan_labels(self, u, v, w, n=None, min_cluster_size=5, max_rounds=0, want_linkage=False, want_lambda=False, want_stability=False):
+        """HDBSCAN's labels of a sorted forest (tknnHdbscanLabels): excess-of-mass selection over the condensed tree of the records
+        (u, v, w) as ``emst`` returns them (with rows for names), sklearn's ``cluster_selection_method="eom"`` without
+        ``allow_single_cluster``; lambda = 1 / w in float64 with w = 0 taken as FLT_MIN, a tie between a cluster and its children
+        goes to the cluster.  Returns dict(labels (n,) int32, -1 for noise, clusters numbered by their smallest vertex; info[,
+        parent, left, right, size with ``want_linkage``; lam (n,) float64, the lambda at which a point leaves its cluster, with
+        ``want_lambda``; stability (edges,) float64, at the node that heads a cluster, with ``want_stability``])."""
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            u, v, w, n = self._records("hdbscan_labels", u, v, w, self.n if n is None else n, True)
+            edges = int(u.shape[0])
+            out = {"labels": torch.empty((n,), dtype=torch.int32, device=self.device)}
+            if want_linkage:
+                out.update(self._linkage_arrays(n, edges))
+            if want_lambda:
+                out["lam"] = torch.empty((n,), dtype=torch.float64, device=self.device)
+            if want_stability:
+                out["stability"] = torch.empty((edges,), dtype=torch.float64, device=self.device)
+            spare = torch.empty((2,), dtype=torch.int32, device=self.device)
+            opt = _hdbscan_lib.HdbscanLabelsOptions()
+            opt.n, opt.edges, opt.min_cluster_size, opt.max_rounds = n, edges, int(min_cluster_size), int(max_rounds)
+            opt.d_u, opt.d_v, opt.d_w = _address(u, spare), _address(v, spare), _address(w, spare)
+            opt.d_labels = _address(out["labels"], spare)
+            for field, name in (("d_parent", "parent"), ("d_left", "left"), ("d_right", "right"), ("d_size", "size"), ("d_lambda", "lam"),
+                                ("d_stability", "stability")):
+                setattr(opt, field, _address(out.get(name), spare))
+            info = _hdbscan_lib.HdbscanLabelsInfo()
+            _lib.check(_hdbscan_lib.load().tknnHdbscanLabels(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, max_rounds=0, want_tree=False, want_linkage=False, want_lambda=False,
+                want_core_dist=False, want_stability=False):
+        """HDBSCAN of the built set in one call (tknnHdbscan): ``knn`` for the core distances -- the distance to the
+        (min_samples - 1)-th nearest other point, sklearn's convention; ``min_samples`` None means ``min_cluster_size``, sklearn's
+        default, 1 the plain Euclidean tree --, ``emst`` under them, ``hdbscan_labels`` of its records.  A point that is in no
+        record (a NaN coordinate, fewer than min_samples - 1 other points in reach) is noise and counted in info["excluded"].
+        Returns dict(labels (n,) int32 by row, info[, u, v, w: ``emst``'s records, by name, with ``want_tree``; parent, left,
+        right, size with ``want_linkage`` (leaves are rows); lam with ``want_lambda``; core_dist with ``want_core_dist`` and
+        min_samples > 1; stability with ``want_stability``])."""
+        torch = self._torch
+        n = self.n
+        min_cluster_size = int(min_cluster_size)
+        min_samples = min_cluster_size if min_samples is None else int(min_samples)
+        rows = max(n - 1, 0)
+        with torch.cuda.device(self.device):
+            out = {"labels": torch.empty((n,), dtype=torch.int32, device=self.device)}
+            if want_tree:
+                out["u"] = torch.empty((rows,), dtype=torch.int32, device=self.device)
+                out["v"] = torch.empty((rows,), dtype=torch.int32, device=self.device)
+                out["w"] = torch.empty((rows,), dtype=torch.float32, device=self.device)
+            if want_linkage:
+                out.update(self._linkage_arrays(n, rows))
+            if want_lambda:
+                out["lam"] = torch.empty((n,), dtype=torch.float64, device=self.device)
+            if want_core_dist and min_samples > 1:
+                out["core_dist"] = torch.empty((n,), dtype=torch.float32, device=self.device)
+            if want_stability:
+                out["stability"] = torch.empty((rows,), dtype=torch.float64, device=self.device)
+            spare = torch.empty((2,), dtype=torch.int32, device=self.device)
+            opt = _hdbscan_lib.HdbscanOptions()
+            opt.min_cluster_size, opt.min_samples, opt.max_rounds = min_cluster_size, min_samples, int(max_rounds)
+            for field, name in (("d_labels", "labels"), ("d_core_dist", "core_dist"), ("d_u", "u"), ("d_v", "v"), ("d_w", "w"), ("d_parent", "parent"),
+                                ("d_left", "left"), ("d_right", "right"), ("d_size", "size"), ("d_lambda", "lam"), ("d_stability", "stability")):
+                setattr(opt, field, _address(out.get(name), spare))
+            info = _hdbscan_lib.HdbscanInfo()
+            _lib.check(_hdbscan_lib.load().tknnHdbscan(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        edges = int(info.edges)
+        for name in ("u", "v", "w", "left", "right", "size", "stability"):
+            if name in out:
+                out[name] = out[name][:edges]
+        if "parent" in out:
+            out["parent"] = out["parent"][:n + edges]
+        out["edges"] = edges
+        out["info"] = info.as_dict()
+        return out
+
     def periodic_knn(self, queries=None, k=1, lo=(0, 0, 0), period=None, radius=None, radii=None, skip_ids=None, want_dist=True):
         """At most ``k`` nearest points of the built set in a periodic cell, as dense rows (tknnPeriodicKnn): ``knn`` and
         ``radius_knn`` under the wrapped distance.  The cell is ``lo`` and ``period`` (three values each; 2-D data: two, z stays
@@ -888,6 +1022,30 @@ def mutual_reachability_mst(points, min_samples, **kw):
         return dict(eng.emst(core_dist=core, **kw), core_dist=core)
 
     return _one_shot(points, call)
+
+
+def hdbscan(points, min_cluster_size=5, min_samples=None, **kw):
+    """One-shot helper: build over ``points`` and cluster them (TrueKNN.hdbscan), results as numpy arrays."""
+    return _one_shot(points, lambda eng: eng.hdbscan(min_cluster_size, min_samples, **kw))
+
+
+def linkage(u, v, w=None, n=None, **kw):
+    """One-shot helper: the single-linkage dendrogram of the sorted forest (u, v[, w]) over ``n`` vertices (TrueKNN.linkage; ``n``
+    defaults to edges + 1, a spanning tree), results as numpy arrays.  No point set is needed."""
+    eng = TrueKNN()
+    try:
+        res = eng.linkage(np.asarray(u), np.asarray(v), None if w is None else np.asarray(w), len(u) + 1 if n is None else n, **kw)
+        return {name: (t.cpu().numpy() if hasattr(t, "cpu") else t) for name, t in res.items()}
+    finally:
+        eng.close()
+
+
+def linkage_matrix(result, w=None):
+    """scipy's linkage matrix Z of a spanning tree: (left, right, w, size) of ``TrueKNN.linkage`` / ``hdbscan(want_linkage=True,
+    want_tree=True)`` stacked as float64 rows; ``w`` defaults to the result's own."""
+    w = result["w"] if w is None else w
+    cols = [result["left"], result["right"], w, result["size"]]
+    return np.stack([np.asarray(c.cpu().numpy() if hasattr(c, "cpu") else c, np.float64) for c in cols], axis=1)
 
 
 def batch_knn(points, batch_x, queries, batch_y, k, **kw):
