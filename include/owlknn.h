@@ -138,7 +138,9 @@ TKNN_API int tknnSolve(tknnEngine e, int k, float start_radius, int kernel, int 
  *   them (the caller widens the halo and solves again).
  * tknnHaloSelect: the send side of the exchange.  d_boxes: nboxes x {lo xyz, hi xyz} fp32 closed
  *   boxes (the peers' tile cells widened by the halo radius, rounded outward by the caller);
- *   d_box_peer: the peer (0 <= peer < npeers <= 64) each box belongs to.  Count pass (d_rows NULL):
+ *   d_box_peer: the peer (0 <= peer < npeers <= 64) each box belongs to -- the caller's responsibility: the
+ *   entries live on the device and are not checked, the kernels shift a 64-bit mask by them, and an entry
+ *   outside that range gives unspecified counts and rows.  Count pass (d_rows NULL):
  *   d_counts[npeers] = my points inside at least one box of each peer.  Write pass: d_rows receives
  *   16-byte rows {x, y, z, id bits}, peer p's rows contiguous from row d_offsets[p] (the caller's
  *   exclusive scan of the counts); the order inside a segment is unspecified. */
@@ -177,8 +179,9 @@ TKNN_API int tknnHaloSelect(tknnEngine e, const float *d_boxes, const int32_t *d
 
 /* The same in ONE pass, for a caller that knows how many rows each peer's segment may hold (both ends of a pair agree on the
  * size of their message from the pair's last exchange): rows are written at d_offsets[peer] .. + d_caps[peer], rows that do not fit
- * are dropped, d_counts[peer] receives the exact number of rows selected (> d_caps[peer]: the caller must fall back to
- * tknnHaloSelect for that peer).  No count pass, no host round trip before the rows exist.  Marks the boundary queries like the
+ * are dropped (which ones is unspecified), d_counts[peer] receives the exact number of rows selected (> d_caps[peer]: the caller
+ * must fall back to tknnHaloSelect for that peer).  The rows of a segment past min(d_counts[peer], d_caps[peer]) are left
+ * untouched, as is everything outside the segments.  No count pass, no host round trip before the rows exist.  Marks the boundary queries like the
  * count pass of tknnHaloSelect. */
 TKNN_API int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
                                  const int64_t *d_caps, const int64_t *d_offsets, float *d_rows, int64_t *d_counts, void *stream);

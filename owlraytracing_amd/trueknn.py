@@ -203,7 +203,7 @@ class TrueKNN:
         """The one-pass form of ``halo_select`` for the fixed-capacity exchange (tknnHaloSelectFixed): ``caps[p]`` rows per peer.
         Returns (messages, starts, counts): ``messages`` a (sum(caps) + npeers, 4) float32 buffer in which peer p's message is
         rows starts[p] .. starts[p] + caps[p] -- a header row (the count, as two float32 cells that hold integers below 2**24
-        exactly) and caps[p] wire rows, those past the count unspecified --, ``counts`` the exact per-peer counts as an int64
+        exactly) and caps[p] wire rows, those past the count left untouched (``messages`` is not initialised) --, ``counts`` the exact per-peer counts as an int64
         DEVICE tensor (a count above its capacity: rows were dropped, the caller falls back to ``halo_select``).  Nothing in
         here waits for the device."""
         torch = self._torch

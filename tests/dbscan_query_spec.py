@@ -27,8 +27,9 @@ def query_labels(P, core_label, eps, Q, block=256):
     eps = np.float32(eps)
     m = len(Q)
     labels, counts = np.full(m, -1, np.int32), np.zeros(m, np.int32)
-    none = np.iinfo(np.int32).max
+    none = np.int64(2) ** 31  # (above every int32: 2**31 - 1 is a label like any other)
     core = core_label >= 0
+    core_label = core_label.astype(np.int64)
     for s in range(0, m, block):
         with np.errstate(invalid="ignore", over="ignore"):
             near = distance32(P[None, :, :], Q[s:s + block, None, :]) <= eps  # (NaN <= eps is False)
