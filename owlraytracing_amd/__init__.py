@@ -5,3 +5,10 @@ package is the thin host side above its C-ABI.  Importing the package does not l
 the first call that needs it does, and raises if it has not been built.
 """
 __version__ = "0.1.0"
+
+
+def fps(points, batch=None, ratio=0.5, **kw):
+    """Farthest point sampling per cloud, torch-cluster's ``fps(x, batch, ratio)`` (trueknn.fps; loads the library)."""
+    from .trueknn import fps as _fps
+
+    return _fps(points, batch=batch, ratio=ratio, **kw)

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -410,6 +410,18 @@ int tknnBatchKnn(tknnEngine e, const tknnBatchKnnOptions *options, tknnBatchKnnI
     if (!o.d_radii) c.positive(o.radius, "radius (FLT_MAX: none; or give d_radii)");
     zero(info);
     if (o.m > 0) e->impl.batch_knn(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnFps(tknnEngine e, const tknnFpsOptions *options, tknnFpsInfo *info, void *stream) {
+  return api("tknnFps", e, [&](const Call &c) {
+    const tknnFpsOptions &o = c.record(options);
+    c.need(o.d_idx, "d_idx");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.require(o.num_samples >= 1, "num_samples must be positive");
+    c.require((int64_t)e->impl.num_clouds() * o.num_samples < (1ll << 31), "need clouds * num_samples < 2^31");
+    zero(info);
+    e->impl.fps(o, info, (hipStream_t)stream);
   });
 }
 

@@ -11,6 +11,7 @@
 #include "owlknn.h"
 #include "owlknn_batch.h"
 #include "owlknn_emst.h"
+#include "owlknn_fps.h"
 #include "owlknn_hdbscan.h"
 #include "owlknn_knn.h"
 #include "owlknn_periodic.h"
@@ -170,7 +171,11 @@ class Engine {
   // the core distances, emst under them, the labels of its records (tknnHdbscan)
   void hdbscan_labels(const tknnHdbscanLabelsOptions &o, tknnHdbscanLabelsInfo *info, hipStream_t s);
   void hdbscan(const tknnHdbscanOptions &o, tknnHdbscanInfo *info, hipStream_t s);
+  // fps.hip: farthest point sampling inside each cloud of the tree -- the batches of a batched tree, one cloud otherwise --,
+  // one workgroup per cloud, pruned by the box pyramid (tknnFps); the tree a point tree
+  void fps(const tknnFpsOptions &o, tknnFpsInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
+  int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _hdbscan_lib, _knn_lib, _lib, _periodic_lib
+from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -40,6 +40,7 @@ class TrueKNN:
             _lib.check(lib.tknnCreate(ctypes.byref(self._h)))
         self.n = 0
         self.halo_n = 0
+        self.num_clouds = 1  # the batches of a batched tree (fps samples each), 1 for a plain one
         self.build_info = None
         self.last_info = None
 
@@ -133,6 +134,7 @@ class TrueKNN:
                                                               ctypes.c_void_p(batch.data_ptr()), int(num_batches), points.shape[0],
                                                               ctypes.byref(info), self._stream()))
         self.n = int(points.shape[0])
+        self.num_clouds = 1 if batch is None else int(num_batches)
         self.halo_n = 0  # a build drops the halo tree
         self.build_info = info.as_dict()
         return self.build_info
@@ -854,6 +856,78 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def fps(self, num_samples=None, ratio=None, num=None, start_rows=None, want_dist=True, prune=True):
+        """Farthest point sampling inside each cloud of the built tree (tknnFps; torch-cluster's ``fps(x, batch, ratio)``): the
+        B batches of a tree built with ``build(points, batch=...)``, one cloud otherwise.  Row b starts with the cloud's point
+        of the smallest name (id, or row without ids) -- or with row ``start_rows[b]`` of the built buffer where that is a
+        point of cloud b without a NaN; negative: the default -- and goes on with the unchosen point farthest from those
+        chosen, fp32 squared distance (dx*dx + dy*dy) + dz*dz, equal distances decided by the smaller name.  ``num_samples``
+        (S): at most that many per cloud; ``num`` ((B,) int32): the samples wanted of each cloud, clipped to 0 .. min(S, n_b);
+        ``ratio`` instead of both: ceil(ratio * n_b) of every cloud, computed on the host in float64 from ``batch_layout()``'s
+        starts.  ``prune=False`` visits every block of a cloud for every sample (the A/B switch; same results).  Returns
+        dict(idx (B,S) int32 padded with -1, dist (B,S) float32 [with ``want_dist``]: the distance to the nearest earlier
+        sample, +inf first and in the padding, counts (B,) int32, info)."""
+        torch = self._torch
+        B = self.num_clouds
+        if ratio is not None:
+            if num_samples is not None or num is not None:
+                raise ValueError("fps: give ratio, or num_samples and/or num")
+            if B > 1 or self._is_batched():
+                starts = self.batch_layout()["starts"].cpu().numpy().astype(np.int64)
+                sizes = starts[1:] - starts[:-1]
+            else:
+                sizes = np.array([self.n - self._nan_count()], np.int64)
+            num = np.ceil(np.float64(ratio) * sizes.astype(np.float64)).astype(np.int64).clip(0, sizes).astype(np.int32)
+            num_samples = max(int(num.max()) if len(num) else 1, 1)
+        elif num_samples is None:
+            if num is None:
+                raise ValueError("fps: give num_samples, ratio or num")
+            num_samples = max(int(torch.as_tensor(num).max()), 1)
+
+        def column(values, name):
+            if isinstance(values, torch.Tensor) and values.device != self.device:
+                raise ValueError("fps: %s is on %s, the engine on %s" % (name, values.device, self.device))
+            values = torch.as_tensor(values, device=self.device).to(torch.int32).contiguous()
+            if values.shape != (B,):
+                raise ValueError("fps: %s must have one entry per cloud" % name)
+            return values
+
+        S = int(num_samples)
+        with torch.cuda.device(self.device):
+            num = None if num is None else column(num, "num")
+            start_rows = None if start_rows is None else column(start_rows, "start_rows")
+            rows = max(S, 0)
+            out = {"idx": torch.empty((B, rows), dtype=torch.int32, device=self.device)}
+            if want_dist:
+                out["dist"] = torch.empty((B, rows), dtype=torch.float32, device=self.device)
+            out["counts"] = torch.empty((B,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _fps_lib.FpsOptions()
+            opt.num_samples = S
+            opt.flags = 0 if prune else _fps_lib.FPS_NO_PRUNE
+            opt.d_num = _address(num)
+            opt.d_start_rows = _address(start_rows)
+            opt.d_idx = _address(out["idx"], spare)
+            opt.d_dist = _address(out.get("dist"), spare)
+            opt.d_counts = _address(out["counts"])
+            info = _fps_lib.FpsInfo()
+            _lib.check(_fps_lib.load().tknnFps(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
+    def _is_batched(self):
+        """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
+        nb = ctypes.c_int32(0)
+        with self._torch.cuda.device(self.device):
+            return _batch_lib.load().tknnBatchLayout(self._h, ctypes.byref(nb), None, None, self._stream()) == 0
+
+    def _nan_count(self):
+        """The built points with a NaN coordinate (tknnExportTreeEx with no array asked for)."""
+        x = _lib.TreeExport()
+        with self._torch.cuda.device(self.device):
+            _lib.check(self._lib.tknnExportTreeEx(self._h, ctypes.byref(x), self._stream()))
+        return int(x.nan_count)
+
     def segment_min(self, segment, value, out):
         """out[segment[i]] = min(out[segment[i]], value[i]) for segment[i] >= 0, in place (tknnSegmentMin): ``segment`` (n,)
         int32, ``value`` (n,) int64, ``out`` (m,) int64 preset by the caller, all on the engine's device."""
@@ -1068,6 +1142,21 @@ def batch_knn_graph(points, batch, k, loop=False):
     distance 0.  Results as numpy arrays; entry (i, t) is the edge from idx[i, t] to i."""
     points = pad_to_3d(np.asarray(points, np.float32))
     return batch_knn(points, batch, points if loop else None, batch if loop else None, k)
+
+
+def fps(points, batch=None, ratio=0.5, **kw):
+    """One-shot helper: farthest point sampling of ``points``, inside each cloud of the labels ``batch`` where given
+    (TrueKNN.fps; torch-cluster's ``fps(x, batch, ratio)``): the sampled rows of ``points`` as one flat int64 numpy array, the
+    clouds in label order, each cloud's samples in the order chosen.  ``num_samples`` / ``num`` instead of ``ratio``: pass
+    ``ratio=None``."""
+    eng = TrueKNN()
+    try:
+        eng.build(points, batch=batch)
+        res = eng.fps(ratio=ratio, **kw)
+        idx, counts = res["idx"].cpu().numpy(), res["counts"].cpu().numpy()
+        return np.concatenate([idx[b, : counts[b]] for b in range(len(counts))] + [np.zeros(0, np.int32)]).astype(np.int64)
+    finally:
+        eng.close()
 
 
 def dbscan_query(points, queries, eps, min_pts):
