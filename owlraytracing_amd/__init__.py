@@ -12,3 +12,10 @@ def fps(points, batch=None, ratio=0.5, **kw):
     from .trueknn import fps as _fps
 
     return _fps(points, batch=batch, ratio=ratio, **kw)
+
+
+def radius_nms(points, radius, scores=None, batch=None, **kw):
+    """Greedy suppression within a radius per cloud: no two kept points within ``radius`` (trueknn.radius_nms; loads the library)."""
+    from .trueknn import radius_nms as _radius_nms
+
+    return _radius_nms(points, radius, scores=scores, batch=batch, **kw)

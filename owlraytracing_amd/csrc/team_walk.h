@@ -84,10 +84,15 @@ __device__ __forceinline__ bool walk_count_box(const LbvhBox &bx, const LbvhPoin
 // have four times).  `overflow` is set if the stack overflowed for my team: its walk then is incomplete.  (A reference, not the
 // return value: one flag over both trees of a halo walk instead of two that are or-ed saves these kernels, which sit at the
 // 128-register cap, up to 48 bytes of scratch per lane.)
-template <bool ROLLED, class BoxRule, class BlockVisitor, class ChunkEnd>
+// stop() is asked after every node; a team for which it holds (the same in its 16 lanes) drops what is left on its stack and is
+// through -- the early exit of a walk that looks for one witness (nms.hip).  The default never stops.
+struct WalkNoStop {
+  __device__ __forceinline__ bool operator()() const { return false; }
+};
+template <bool ROLLED, class BoxRule, class BlockVisitor, class ChunkEnd, class Stop = WalkNoStop>
 __device__ __forceinline__ void walk_tree(const WalkLevel *levels, const LbvhWideView &wv, int32_t *stack, int capacity, bool active,
                                           const LbvhPoint &q, const WalkBox &qb, int team, int tl, unsigned long long &node_tests,
-                                          BoxRule keep_box, BlockVisitor visit_block, ChunkEnd after_chunk, bool &overflow) {
+                                          BoxRule keep_box, BlockVisitor visit_block, ChunkEnd after_chunk, bool &overflow, Stop stop = Stop{}) {
   const int top = wv.levels;
   int sp = 0;
   if (active) {
@@ -151,6 +156,7 @@ __device__ __forceinline__ void walk_tree(const WalkLevel *levels, const LbvhWid
 #pragma unroll
       for (int chunk = 0; chunk < 4; chunk++) one_chunk(chunk, bx4[chunk]);
     }
+    if (stop()) sp = 0;
     t_wave_sync();
   }
 }

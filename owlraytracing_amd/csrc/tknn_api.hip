@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -422,6 +422,20 @@ int tknnFps(tknnEngine e, const tknnFpsOptions *options, tknnFpsInfo *info, void
     c.require((int64_t)e->impl.num_clouds() * o.num_samples < (1ll << 31), "need clouds * num_samples < 2^31");
     zero(info);
     e->impl.fps(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnRadiusNms(tknnEngine e, const tknnRadiusNmsOptions *options, tknnRadiusNmsInfo *info, void *stream) {
+  return api("tknnRadiusNms", e, [&](const Call &c) {
+    const tknnRadiusNmsOptions &o = c.record(options);
+    c.need(o.d_keep, "d_keep");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.positive(o.radius, "radius");
+    c.require(!(o.d_scores && (o.flags & TKNN_NMS_BY_NAME)), "d_scores and TKNN_NMS_BY_NAME exclude each other");
+    c.require((o.flags & ~TKNN_NMS_BY_NAME) == 0u, "flags has a bit no flag of this call has");
+    c.require(o.max_rounds >= 0, "max_rounds must not be negative (0: no limit)");
+    zero(info);
+    e->impl.radius_nms(o, info, (hipStream_t)stream);
   });
 }
 

@@ -14,6 +14,7 @@
 #include "owlknn_fps.h"
 #include "owlknn_hdbscan.h"
 #include "owlknn_knn.h"
+#include "owlknn_nms.h"
 #include "owlknn_periodic.h"
 
 namespace owlmi {
@@ -174,6 +175,9 @@ class Engine {
   // fps.hip: farthest point sampling inside each cloud of the tree -- the batches of a batched tree, one cloud otherwise --,
   // one workgroup per cloud, pruned by the box pyramid (tknnFps); the tree a point tree
   void fps(const tknnFpsOptions &o, tknnFpsInfo *info, hipStream_t s);
+  // nms.hip: greedy suppression within a radius inside each cloud of the tree, in rounds of early-exit walks (tknnRadiusNms); the
+  // tree a point tree.  An ArgError of TKNN_E_STATE, with info->rounds set and no output written, when max_rounds do not finish it
+  void radius_nms(const tknnRadiusNmsOptions &o, tknnRadiusNmsInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _periodic_lib
+from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _periodic_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -41,6 +41,7 @@ class TrueKNN:
         self.n = 0
         self.halo_n = 0
         self.num_clouds = 1  # the batches of a batched tree (fps samples each), 1 for a plain one
+        self._row_names = None
         self.build_info = None
         self.last_info = None
 
@@ -135,6 +136,7 @@ class TrueKNN:
                                                               ctypes.byref(info), self._stream()))
         self.n = int(points.shape[0])
         self.num_clouds = 1 if batch is None else int(num_batches)
+        self._row_names = ids  # the names of the rows (radius_nms turns kept rows into names), None: the rows themselves
         self.halo_n = 0  # a build drops the halo tree
         self.build_info = info.as_dict()
         return self.build_info
@@ -915,6 +917,44 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def radius_nms(self, radius, scores=None, by_name=False, want_cover=True, max_rounds=0):
+        """Greedy suppression within ``radius`` inside each cloud of the built tree (tknnRadiusNms): the kept points are those
+        that no stronger kept point of their own cloud has within ``radius`` (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius) --
+        non-maximum suppression, a maximal Poisson-disk subset, radius thinning.  A point's strength is ``scores[row]``
+        ((n,) float32, numpy or a tensor on the engine's device; a NaN score takes the point out), without scores a hash of
+        its name (id, or row without ids), with ``by_name`` nothing: the smallest name wins, which is also what decides among
+        equal strengths.  Returns dict(keep (n,) bool by row, idx: the kept names ascending by row (int64, from nonzero on the
+        device), cover (n,) int32 [with ``want_cover``]: the name of the nearest kept point within ``radius`` of the point's
+        cloud, its own for a kept point, -1 for a point with a NaN, counts (B,) int32: the kept points per cloud, info)."""
+        torch = self._torch
+        n, B = self.n, self.num_clouds
+        with torch.cuda.device(self.device):
+            if scores is not None:
+                if isinstance(scores, torch.Tensor) and scores.device != self.device:
+                    raise ValueError("radius_nms: scores are on %s, the engine on %s" % (scores.device, self.device))
+                scores = torch.as_tensor(scores, device=self.device).to(torch.float32).contiguous()
+                if tuple(scores.shape) != (n,):
+                    raise ValueError("radius_nms: scores must have one entry per built point")
+            keep = torch.empty((n,), dtype=torch.uint8, device=self.device)
+            out = {"cover": torch.empty((n,), dtype=torch.int32, device=self.device)} if want_cover else {}
+            out["counts"] = torch.empty((B,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((1,), dtype=torch.int32, device=self.device)
+            opt = _nms_lib.RadiusNmsOptions()
+            opt.radius = float(radius)
+            opt.flags = _nms_lib.NMS_BY_NAME if by_name else 0
+            opt.max_rounds = int(max_rounds)
+            opt.d_scores = _address(scores, spare)
+            opt.d_keep = _address(keep, spare)
+            opt.d_cover = _address(out.get("cover"), spare)
+            opt.d_counts = _address(out["counts"])
+            info = _nms_lib.RadiusNmsInfo()
+            _lib.check(_nms_lib.load().tknnRadiusNms(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+            out["keep"] = keep.to(torch.bool)
+            rows = torch.nonzero(out["keep"]).reshape(-1)
+            out["idx"] = rows if self._row_names is None else self._row_names[rows].to(torch.int64)
+        out["info"] = info.as_dict()
+        return out
+
     def _is_batched(self):
         """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
         nb = ctypes.c_int32(0)
@@ -1155,6 +1195,17 @@ def fps(points, batch=None, ratio=0.5, **kw):
         res = eng.fps(ratio=ratio, **kw)
         idx, counts = res["idx"].cpu().numpy(), res["counts"].cpu().numpy()
         return np.concatenate([idx[b, : counts[b]] for b in range(len(counts))] + [np.zeros(0, np.int32)]).astype(np.int64)
+    finally:
+        eng.close()
+
+
+def radius_nms(points, radius, scores=None, batch=None, **kw):
+    """One-shot helper: build over ``points`` -- with the labels ``batch`` where given, one cloud each -- and keep the points that
+    no stronger kept point of their cloud has within ``radius`` (TrueKNN.radius_nms), results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points, batch=batch)
+        return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in eng.radius_nms(radius, scores=scores, **kw).items()}
     finally:
         eng.close()
 
