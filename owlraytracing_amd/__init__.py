@@ -19,3 +19,11 @@ def radius_nms(points, radius, scores=None, batch=None, **kw):
     from .trueknn import radius_nms as _radius_nms
 
     return _radius_nms(points, radius, scores=scores, batch=batch, **kw)
+
+
+def radius_reduce(points, queries, radius, **kw):
+    """Counts, kernel-weight sums and weighted value sums over the points within ``radius`` of each query, no neighbour lists
+    written (trueknn.radius_reduce; loads the library)."""
+    from .trueknn import radius_reduce as _radius_reduce
+
+    return _radius_reduce(points, queries, radius, **kw)

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -436,6 +436,26 @@ int tknnRadiusNms(tknnEngine e, const tknnRadiusNmsOptions *options, tknnRadiusN
     c.require(o.max_rounds >= 0, "max_rounds must not be negative (0: no limit)");
     zero(info);
     e->impl.radius_nms(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnRadiusReduce(tknnEngine e, const tknnRadiusReduceOptions *options, tknnRadiusReduceInfo *info, void *stream) {
+  return api("tknnRadiusReduce", e, [&](const Call &c) {
+    const tknnRadiusReduceOptions &o = c.record(options);
+    c.require(o.d_counts || o.d_wsum || o.d_out, "no output: give d_counts, d_wsum or d_out");
+    if (!o.d_queries) c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.positive(o.radius, "radius");
+    c.require(o.weight >= TKNN_W_ONE && o.weight <= TKNN_W_CUBIC_SPLINE, "weight must be one of TKNN_W_ONE, TKNN_W_GAUSS, TKNN_W_EPANECHNIKOV, TKNN_W_CUBIC_SPLINE");
+    c.require((o.flags & ~(TKNN_REDUCE_NORMALIZE | TKNN_REDUCE_SKIP_SELF)) == 0u, "flags has a bit no flag of this call has");
+    if (o.weight == TKNN_W_GAUSS) c.positive(o.bandwidth, "bandwidth (TKNN_W_GAUSS)");
+    c.require(o.channels >= 0 && o.channels <= TKNN_REDUCE_MAX_CHANNELS, "channels must be 0 .. 16");
+    if (o.channels > 0) c.need(o.d_values, "d_values (channels > 0)"), c.need(o.d_out, "d_out (channels > 0)");
+    c.require(o.channels > 0 || o.d_counts || o.d_wsum, "channels = 0 writes no d_out: give d_counts or d_wsum");
+    c.require(!((o.flags & TKNN_REDUCE_SKIP_SELF) && o.d_queries), "TKNN_REDUCE_SKIP_SELF goes with d_queries = NULL (the set's own points) only");
+    c.count(o.m, "m");
+    zero(info);
+    if (o.m > 0) e->impl.radius_reduce(o, info, (hipStream_t)stream);
   });
 }
 

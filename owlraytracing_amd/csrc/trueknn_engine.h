@@ -16,6 +16,7 @@
 #include "owlknn_knn.h"
 #include "owlknn_nms.h"
 #include "owlknn_periodic.h"
+#include "owlknn_reduce.h"
 
 namespace owlmi {
 
@@ -178,6 +179,9 @@ class Engine {
   // nms.hip: greedy suppression within a radius inside each cloud of the tree, in rounds of early-exit walks (tknnRadiusNms); the
   // tree a point tree.  An ArgError of TKNN_E_STATE, with info->rounds set and no output written, when max_rounds do not finish it
   void radius_nms(const tknnRadiusNmsOptions &o, tknnRadiusNmsInfo *info, hipStream_t s);
+  // radius_reduce.hip: counts, weight sums and weighted value sums over the points within a radius of m points that are not in the
+  // tree or (d_queries null) of the tree's own points, no lists written (tknnRadiusReduce); m > 0, the tree a point tree
+  void radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }

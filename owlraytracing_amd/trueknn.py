@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _periodic_lib
+from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _periodic_lib, _reduce_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -955,6 +955,57 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def radius_reduce(self, radius, queries=None, values=None, weight="one", bandwidth=None, normalize=False, skip_self=False, want_wsum=True,
+                      want_counts=True):
+        """Sums over the points of the built set within ``radius`` of each query, without the lists (tknnRadiusReduce): the
+        neighbours are ``radius_query``'s (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius; nothing is "self").  ``queries``: numpy
+        (m,2|3) or a contiguous float32 tensor (m,3) on the engine's device; None: the set's own points, results by row, and
+        ``skip_self`` leaves each point out of its own sums.  ``weight``: "one", "gauss" (exp(-d^2 / (2 bandwidth^2)), truncated at
+        the radius), "epanechnikov" (1 - d^2 / r^2) or "cubic_spline" (the SPH M4 spline on support r), all unnormalised.
+        ``values``: (n,) or (n, C <= 16) float32 by the caller's row -- also on trees built with ids --, numpy or a tensor on the
+        engine's device.  ``normalize``: out is divided by the weight sum (0 where that is 0): a kernel-weighted mean.
+        Returns dict(out (m, C) float32 -- (m,) for (n,) values, None without values --, wsum (m,) float32 [``want_wsum``],
+        counts (m,) int32 [``want_counts``], info)."""
+        torch = self._torch
+        if weight not in _reduce_lib.WEIGHTS:
+            raise ValueError("radius_reduce: weight must be one of %s" % ", ".join(sorted(_reduce_lib.WEIGHTS)))
+        if weight == "gauss" and bandwidth is None:
+            raise ValueError("radius_reduce: the gauss weight needs a bandwidth")
+        if queries is not None:
+            queries = self._queries(queries, "radius_reduce")
+        m = self.n if queries is None else int(queries.shape[0])
+        with torch.cuda.device(self.device):
+            flat, C = False, 0
+            if values is not None:
+                if isinstance(values, torch.Tensor) and values.device != self.device:
+                    raise ValueError("radius_reduce: values are on %s, the engine on %s" % (values.device, self.device))
+                values = torch.as_tensor(values, device=self.device).to(torch.float32).contiguous()
+                flat = values.dim() == 1
+                if flat:
+                    values = values.reshape(-1, 1)
+                if values.dim() != 2 or values.shape[0] != self.n or not 1 <= values.shape[1] <= _reduce_lib.MAX_CHANNELS:
+                    raise ValueError("radius_reduce: values must be (n,) or (n, C) with 1 <= C <= %d, one row per built point" % _reduce_lib.MAX_CHANNELS)
+                C = int(values.shape[1])
+            out = torch.empty((m, C), dtype=torch.float32, device=self.device) if C else None
+            wsum = torch.empty((m,), dtype=torch.float32, device=self.device) if want_wsum else None
+            counts = torch.empty((m,), dtype=torch.int32, device=self.device) if want_counts else None
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            opt = _reduce_lib.RadiusReduceOptions()
+            opt.m, opt.radius, opt.bandwidth = m, float(radius), 0.0 if bandwidth is None else float(bandwidth)
+            opt.weight, opt.channels = _reduce_lib.WEIGHTS[weight], C
+            opt.flags = (_reduce_lib.REDUCE_NORMALIZE if normalize else 0) | (_reduce_lib.REDUCE_SKIP_SELF if skip_self else 0)
+            opt.d_queries = None if queries is None else _address(queries, spare)
+            opt.d_values = _address(values, spare)
+            opt.d_counts, opt.d_wsum, opt.d_out = _address(counts, spare), _address(wsum, spare), _address(out, spare)
+            info = _reduce_lib.RadiusReduceInfo()
+            _lib.check(_reduce_lib.load().tknnRadiusReduce(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        res = {"out": out.reshape(-1) if (flat and out is not None) else out, "info": info.as_dict()}
+        if want_wsum:
+            res["wsum"] = wsum
+        if want_counts:
+            res["counts"] = counts
+        return res
+
     def _is_batched(self):
         """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
         nb = ctypes.c_int32(0)
@@ -1206,6 +1257,18 @@ def radius_nms(points, radius, scores=None, batch=None, **kw):
     try:
         eng.build(points, batch=batch)
         return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in eng.radius_nms(radius, scores=scores, **kw).items()}
+    finally:
+        eng.close()
+
+
+def radius_reduce(points, queries, radius, ids=None, batch=None, **kw):
+    """One-shot helper: build over ``points`` and sum over the points within ``radius`` of each of ``queries`` (None: the points
+    themselves) what TrueKNN.radius_reduce sums, results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points, ids=ids, batch=batch)
+        res = eng.radius_reduce(radius, queries=queries, **kw)
+        return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
     finally:
         eng.close()
 
