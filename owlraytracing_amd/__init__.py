@@ -27,3 +27,11 @@ def radius_reduce(points, queries, radius, **kw):
     from .trueknn import radius_reduce as _radius_reduce
 
     return _radius_reduce(points, queries, radius, **kw)
+
+
+def local_pca(points, queries, radius=None, k=None, **kw):
+    """Count, centroid, covariance, eigenvalues, eigenvectors, normal and surface variation of each query's neighbourhood (a
+    radius, the k nearest, or both), no neighbour lists written (trueknn.local_pca; loads the library)."""
+    from .trueknn import local_pca as _local_pca
+
+    return _local_pca(points, queries, radius=radius, k=k, **kw)

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -456,6 +456,30 @@ int tknnRadiusReduce(tknnEngine e, const tknnRadiusReduceOptions *options, tknnR
     c.count(o.m, "m");
     zero(info);
     if (o.m > 0) e->impl.radius_reduce(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnLocalPca(tknnEngine e, const tknnLocalPcaOptions *options, tknnLocalPcaInfo *info, void *stream) {
+  return api("tknnLocalPca", e, [&](const Call &c) {
+    const tknnLocalPcaOptions &o = c.record(options);
+    c.require(o.d_counts || o.d_centroid || o.d_cov || o.d_eigenvalues || o.d_eigenvectors || o.d_normals || o.d_curvature,
+              "no output: give d_counts, d_centroid, d_cov, d_eigenvalues, d_eigenvectors, d_normals or d_curvature");
+    if (!o.d_queries) c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.require(o.radius != 0.f || o.k != 0, "give a radius, k or both (radius = 0 and k = 0: no neighbourhood)");
+    c.require(o.radius >= 0.f && std::isfinite(o.radius), "radius must be finite and > 0 (0: none)");
+    c.require(o.k >= 0, "k must not be negative (0: none)");
+    c.require(!(!o.d_queries && !(o.flags & TKNN_PCA_SKIP_SELF) && o.k == 1),
+              "k = 1 with the set's own points is the point alone: k counts the point itself, give k >= 2 or TKNN_PCA_SKIP_SELF");
+    c.require((o.flags & ~(TKNN_PCA_SKIP_SELF | TKNN_PCA_ORIENT)) == 0u, "flags has a bit no flag of this call has");
+    c.require(!((o.flags & TKNN_PCA_SKIP_SELF) && o.d_queries), "TKNN_PCA_SKIP_SELF goes with d_queries = NULL (the set's own points) only");
+    if (o.flags & TKNN_PCA_ORIENT)
+      c.require(std::isfinite(o.viewpoint[0]) && std::isfinite(o.viewpoint[1]) && std::isfinite(o.viewpoint[2]), "viewpoint must be finite (TKNN_PCA_ORIENT)");
+    c.require(o.min_points >= 0, "min_points must not be negative (0: 3)");
+    c.count(o.m, "m");
+    if (o.k > TKNN_MAX_K_REGISTERS) c.refuse(TKNN_E_UNSUPPORTED, "k out of range (1 .. " + std::to_string(TKNN_MAX_K_REGISTERS) + ")");
+    zero(info);
+    if (o.m > 0) e->impl.local_pca(o, info, (hipStream_t)stream);
   });
 }
 

@@ -15,6 +15,7 @@
 #include "owlknn_hdbscan.h"
 #include "owlknn_knn.h"
 #include "owlknn_nms.h"
+#include "owlknn_pca.h"
 #include "owlknn_periodic.h"
 #include "owlknn_reduce.h"
 
@@ -182,6 +183,10 @@ class Engine {
   // radius_reduce.hip: counts, weight sums and weighted value sums over the points within a radius of m points that are not in the
   // tree or (d_queries null) of the tree's own points, no lists written (tknnRadiusReduce); m > 0, the tree a point tree
   void radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInfo *info, hipStream_t s);
+  // local_pca.hip: count, centroid, covariance, eigenvalues, eigenvectors, normal and surface variation of the neighbourhood -- a
+  // radius row, a kNN row or both -- of m points that are not in the tree or (d_queries null) of the tree's own points, no lists
+  // written (tknnLocalPca); m > 0, the tree a point tree
+  void local_pca(const tknnLocalPcaOptions &o, tknnLocalPcaInfo *info, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _periodic_lib, _reduce_lib
+from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _pca_lib, _periodic_lib, _reduce_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -1006,6 +1006,52 @@ class TrueKNN:
             res["counts"] = counts
         return res
 
+    def local_pca(self, radius=None, k=None, queries=None, skip_self=False, viewpoint=None, min_points=3,
+                  want=("counts", "centroid", "cov", "eigenvalues", "eigenvectors", "normals", "curvature")):
+        """The plane fitted to each query's neighbourhood among the built points, without the lists (tknnLocalPca): the
+        neighbourhood is ``radius_query``'s row at ``radius``, ``knn``'s row at ``k``, or with both the entries of the kNN row within
+        the radius.  ``queries``: numpy (m,2|3) or a contiguous float32 tensor (m,3) on the engine's device; None: the set's own
+        points, results by row -- the point itself is then in its neighbourhood (``k`` counts it: the k nearest including itself)
+        unless ``skip_self``.  The moments are sums of the offsets p - q in fp32: counts (m,) int32, centroid (m,3), cov (m,6: xx, xy,
+        xz, yy, yz, zz; the population covariance), eigenvalues (m,3) ascending, eigenvectors (m,3,3), row i belonging to
+        eigenvalue i, normals (m,3) -- the eigenvector of the smallest eigenvalue, turned towards ``viewpoint`` (three floats) where
+        one is given, else so that its largest component is positive --, curvature (m,) = l0 / (l0 + l1 + l2).  Rows with fewer than
+        ``min_points`` neighbours have zero eigenvalues, eigenvectors, normal and curvature.
+        Returns dict(the outputs named in ``want``, info)."""
+        torch = self._torch
+        want = tuple(want)
+        for name in want:
+            if name not in _pca_lib.OUTPUTS:
+                raise ValueError("local_pca: want names %r; the outputs are %s" % (name, ", ".join(_pca_lib.OUTPUTS)))
+        if viewpoint is not None and len(tuple(viewpoint)) != 3:
+            raise ValueError("local_pca: viewpoint must be three floats")
+        if queries is not None:
+            queries = self._queries(queries, "local_pca")
+        m = self.n if queries is None else int(queries.shape[0])
+        with torch.cuda.device(self.device):
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            opt = _pca_lib.LocalPcaOptions()
+            opt.m, opt.radius, opt.k, opt.min_points = m, 0.0 if radius is None else float(radius), 0 if k is None else int(k), int(min_points)
+            opt.flags = (_pca_lib.PCA_SKIP_SELF if skip_self else 0) | (_pca_lib.PCA_ORIENT if viewpoint is not None else 0)
+            if viewpoint is not None:
+                opt.viewpoint[0], opt.viewpoint[1], opt.viewpoint[2] = (float(v) for v in viewpoint)
+            opt.d_queries = None if queries is None else _address(queries, spare)
+            out = {}
+            for name in want:
+                field, width = _pca_lib.OUTPUTS[name]
+                shape = (m,) if width == 1 else (m, 3, 3) if width == 9 else (m, width)
+                out[name] = torch.empty(shape, dtype=torch.int32 if name == "counts" else torch.float32, device=self.device)
+                setattr(opt, field, _address(out[name], spare))
+            info = _pca_lib.LocalPcaInfo()
+            _lib.check(_pca_lib.load().tknnLocalPca(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
+    def normals(self, radius=None, k=None, queries=None, skip_self=False, viewpoint=None, min_points=3):
+        """``local_pca`` asking for normals, curvature and counts only: dict(normals (m,3), curvature (m,), counts (m,), info)."""
+        return self.local_pca(radius=radius, k=k, queries=queries, skip_self=skip_self, viewpoint=viewpoint, min_points=min_points,
+                              want=("normals", "curvature", "counts"))
+
     def _is_batched(self):
         """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
         nb = ctypes.c_int32(0)
@@ -1268,6 +1314,18 @@ def radius_reduce(points, queries, radius, ids=None, batch=None, **kw):
     try:
         eng.build(points, ids=ids, batch=batch)
         res = eng.radius_reduce(radius, queries=queries, **kw)
+        return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
+    finally:
+        eng.close()
+
+
+def local_pca(points, queries, radius=None, k=None, ids=None, batch=None, **kw):
+    """One-shot helper: build over ``points`` and fit a plane to the neighbourhood of each of ``queries`` (None: the points
+    themselves) as TrueKNN.local_pca does, results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points, ids=ids, batch=batch)
+        res = eng.local_pca(radius=radius, k=k, queries=queries, **kw)
         return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
     finally:
         eng.close()
