@@ -246,11 +246,11 @@ def check(rc):
 # before team_): a committed profile of the packet kernel stays valid when only the tie pass, the k > 64 walk or the
 # clustering kernels change, and the other way round; one of the label pass when only the union pass changes; every one when
 # only the C ABI's argument checks and messages (tknn_api.hip, which holds no kernel) change
-_NOT_TEAM = ("dbscan.hip", "dbscan_core.hip", "dbscan_union.hip", "dbscan_label.hip", "db_device.h", "db_call.h", "halo_select.hip", "radius_query.hip",
+_NOT_TEAM = ("dbscan.hip", "dbscan_core.hip", "dbscan_union.hip", "dbscan_label.hip", "db_device.h", "db_call.h", "halo_select.hip", "radius_query.hip", "radius_walk.h",
              "radius_knn.hip", "radius_knn_walk.h", "knn_seed.hip", "owlknn_knn.h", "periodic_knn.hip", "periodic_metric.h", "owlknn_periodic.h", "batch_knn.hip", "owlknn_batch.h",
              "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp")
 # RT-DBSCAN's kernels are in three files by pass; dbscan.hip, the host side that decides their grids and arguments, counts for all
-_NOT_DB = ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_knn.hip",
+_NOT_DB = ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_walk.h", "radius_knn.hip",
            "radius_knn_walk.h", "knn_seed.hip", "owlknn_knn.h", "periodic_knn.hip", "periodic_metric.h", "owlknn_periodic.h", "batch_knn.hip",
            "owlknn_batch.h", "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp")
 _NOT_DB_CORE, _NOT_DB_UNION = _NOT_DB + ("dbscan_union.hip", "dbscan_label.hip"), _NOT_DB + ("dbscan_core.hip", "dbscan_label.hip")

@@ -3,35 +3,27 @@
 //
 // Row j sums, over the points p of its neighbourhood N_j, 1, the offset d = p - q_j and the six products of d: ten words.  The
 // offsets are bounded by the neighbourhood's radius, so the covariance S2 / len - mean mean^T is a difference of numbers of the
-// size r^2, never |p|^2; nothing is staged.  N_j is a radius row, a kNN row or their intersection (the header); the walk is
-// reduce_walk_kernel's (radius_reduce.hip) with one bound per query:
+// size r^2, never |p|^2; nothing is staged.  N_j is a radius row, a kNN row or their intersection (the header):
 //   1. the bound (only with k): Engine::knn inside, its rows in DeviceBuffers (the inner call takes the workspace);
 //      pca_bound_kernel turns each row into (R_j, last_j), the distance and the name of its last entry, R_j clipped to the radius
 //      where one is given and smaller -- the name rule is then off for the row: every point within the radius is in it.  N_j is
 //      "the own slot if it is in, plus every other point with (d, name) <= (R_j, last_j) lexicographically": the kNN row is never
 //      gathered, no id is mapped back to a slot.  Without k: R_j = radius, the name rule off.
 //   2. query_order (query_order.h): external queries along the tree's own curve; the own points in sorted-slot order.
-//   3. pca_walk_kernel: persistent, one 16-lane team per query, four teams per wave, walk_tree (team_walk.h) with the query's box
-//      of half-width R_j (1 + 1e-6).  Lane tl tests point tl of a leaf block and, under the predicate, adds 1, d and the six
-//      products into its OWN ten registers.  A child box above the leaf level wholly inside the sphere of 0.999995 R_j^2
-//      (reduce_inside2's rule) holds only points strictly nearer than R_j -- the name rule cannot apply to it --: it is noted in
-//      the team's range list and streamed after the walk without further box tests; a full list means the box is walked.  One
-//      DPP reduction per row; the team's lane 0 writes the row's ten words into the workspace and does NOT solve it (fifteen idle
-//      lanes per eigen-solve otherwise).  Stack overflows go to a redo list.
-//   4. pca_lane_kernel: one query per lane on the rope walk (lane_walk.h), for the redo list and for trees too small for a
-//      pyramid; the same ten words.
-//   5. pca_finish_kernel: flat, one row per lane: centroid, covariance, the eigen-solver (pca_eig3, the one place it exists), the
+//   3. rad_walks (radius_walk.h: the walk, the box rule, the lane kernel for what the walk left) with PcaRule: one bound R_j per
+//      query; a lane adds, under the predicate, 1, d and the six products into its OWN ten registers.  A child box above the leaf
+//      level wholly inside the sphere (radius_inside2(R_j)) holds only points strictly nearer than R_j -- the name rule cannot apply
+//      to it --: its slots are streamed.  One DPP reduction per row; the team's lane 0 writes the row's ten words into the
+//      workspace and does NOT solve it (fifteen idle lanes per eigen-solve otherwise).
+//   4. pca_finish_kernel: flat, one row per lane: centroid, covariance, the eigen-solver (pca_eig3, the one place it exists), the
 //      normal's sign, the curvature, the degenerate rows; only the outputs asked for, no solve where none of them needs one.
 // The call's workspace (Engine::workspace, one layout):
-//      counters (kPcaWords) | codes, sorted codes, order in, order (m + 1 each; external queries only) | redo list, m |
+//      counters (kRadWords) | codes, sorted codes, order in, order (m + 1 each; external queries only) | redo list, m |
 //      moments, 10 columns of m words (external: by query, own points: by sorted slot) | the sort's temporary
 #include "owlknn_pca.h"
-#include "lane_walk.h"
 #include "linkage.h"  // DeviceBuffer
 #include "query_order.h"
-#include "team_lanes.h"
-#include "team_walk.h"
-#include "trueknn_engine.h"
+#include "radius_walk.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -43,16 +35,9 @@ namespace owlmi {
 
 namespace {
 
-constexpr int kPcaBlock = 64;        // one wave per workgroup, four teams
-constexpr int kPcaBlocksPerCu = 16;  // 6.3 KB of LDS each
-constexpr int kPcaLaneBlock = 256;
 constexpr int kPcaFlatBlock = 256;
-constexpr int kPcaRanges = 16;  // inside boxes above the leaf level a team notes for streaming; a 17th is walked
 constexpr int kPcaMoments = 10;  // count, S1 (x y z), S2 (xx xy xz yy yz zz)
 constexpr int kPcaSweeps = 6;    // cyclic Jacobi sweeps of the 3 x 3 solve
-
-// words of the call's own counters (in the workspace, zeroed per call)
-enum { kPcaCursor = 0, kPcaRedo = 1, kPcaTotal = 2, kPcaMaxRow = 3, kPcaFallback = 4, kPcaNodeTests = 5, kPcaPointTests = 6, kPcaDegenerate = 7, kPcaWords = 8 };
 
 struct PcaArgs {
   LbvhView bvh;
@@ -75,65 +60,39 @@ struct PcaArgs {
   int32_t *counts;        // the caller's outputs, any may be null
   float *centroid, *cov, *eigenvalues, *eigenvectors, *normals, *curvature;
   int32_t *redo;          // m: positions left to the lane kernel
-  unsigned long long *ws; // kPcaWords counters
+  unsigned long long *ws; // kRadWords counters
 };
-
-__device__ __forceinline__ float pca_nan() { return __uint_as_float(0x7fc00000u); }
-
-// R^2 * 0.999995 in double, rounded DOWN to fp32 (radius_query.hip's box rule, reduce_inside2)
-__device__ __forceinline__ float pca_inside2(float r) {
-  const double want = (double)r * (double)r * 0.999995;
-  float f = (float)want;
-  if ((double)f > want) f = __uint_as_float(__float_as_uint(f) - 1u);  // (f > 0 here: want > 0)
-  return f;
-}
-
-// sum over the 16 lanes of my team (lane 0 of the team reads it; the order of the additions differs by lane)
-__device__ __forceinline__ float pca_team_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128 /*row_ror:8*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124 /*row_ror:4*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122 /*row_ror:2*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121 /*row_ror:1*/, 0xf, 0xf, false));
-  return v;
-}
 
 // the query at position `pos` and how its neighbourhood is told
 struct PcaQuery {
   LbvhPoint q;
   int32_t row;        // where the caller's results go
   int32_t at;         // where the moments go
-  int32_t self_slot;  // the query's own slot where it is treated apart (-1: no slot is)
+  int32_t self;       // the query's own slot where it is treated apart (-1: no slot is)
   int32_t skip_name;  // the name no other neighbour may have (-1: none)
   float r;            // R_j
-  float r_walk;       // max(R_j, 0): the query's box still holds the query
+  float r_wide;       // max(R_j, 0) (1 + 1e-6): the query's box still holds the query
+  float in2;          // radius_inside2(R_j) (-1: no box is inside)
   uint32_t last;
 };
 __device__ __forceinline__ PcaQuery pca_query(const PcaArgs &a, int32_t pos, bool has_q) {
   PcaQuery s;
-  s.self_slot = -1, s.skip_name = -1;
-  if (a.queries) {
-    s.row = has_q ? (int32_t)a.order[pos] : 0;
-    s.at = s.row;
-    s.q.x = a.queries[3 * (int64_t)s.row], s.q.y = a.queries[3 * (int64_t)s.row + 1], s.q.z = a.queries[3 * (int64_t)s.row + 2];
-  } else {
-    const int32_t slot = has_q ? pos : 0;
-    s.q = a.bvh.points[slot];
-    s.row = a.bvh.prim_id[slot];
-    s.at = slot;
-    if (has_q && (a.skip_self || a.by_name)) s.self_slot = slot;
-    if (has_q && a.by_name) s.skip_name = s.q.id;
-  }
+  const int32_t slot = rad_point(a, pos, has_q, s.q, s.row);
+  s.at = a.queries ? s.row : slot;
+  s.self = has_q && (a.skip_self || a.by_name) ? slot : -1;
+  s.skip_name = has_q && a.by_name ? s.q.id : -1;
   s.q.id = -1;
   s.r = a.bound_r ? a.bound_r[s.row] : a.radius;
   s.last = a.bound_last ? a.bound_last[s.row] : 0xffffffffu;
-  s.r_walk = fmaxf(s.r, 0.f);
+  s.r_wide = fmaxf(s.r, 0.f) * 1.000001f;
+  s.in2 = s.r > 0.f ? radius_inside2(s.r) : -1.f;
   return s;
 }
 
 // Is the point p at sorted slot `slot`, at offset (dx, dy, dz) from the query, in N_j?  d: the literal fp32 distance.  A NaN on
 // either side fails every compare.
 __device__ __forceinline__ bool pca_member(const PcaArgs &a, const PcaQuery &s, int32_t slot, const LbvhPoint &p, float d) {
-  if (slot == s.self_slot) return a.self_in && d <= FLT_MAX;
+  if (slot == s.self) return a.self_in && d <= FLT_MAX;
   return p.id != s.skip_name && (d < s.r || (d == s.r && (uint32_t)p.id <= s.last));
 }
 
@@ -150,23 +109,6 @@ __device__ __forceinline__ void pca_store(const PcaArgs &a, int32_t at, uint32_t
   a.moments[at] = cnt;
 #pragma unroll
   for (int c = 0; c < 9; c++) a.moments[(int64_t)(c + 1) * a.m + at] = __float_as_uint(acc[c]);
-}
-
-__device__ __forceinline__ void pca_add_stats(unsigned long long *ws, int lane, unsigned long long total, unsigned int max_row, unsigned long long fallback,
-                                              unsigned long long degenerate, unsigned long long node_tests, unsigned long long point_tests) {
-  const unsigned long long tsum = t_wave_sum(total), fb = t_wave_sum(fallback), dg = t_wave_sum(degenerate), nt = t_wave_sum(node_tests),
-                           pt = t_wave_sum(point_tests);
-  unsigned int mx = max_row;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned int)__shfl_xor((int)mx, off));
-  if (lane == 0) {
-    if (tsum) atomicAdd(&ws[kPcaTotal], tsum);
-    if (mx) atomicMax(&ws[kPcaMaxRow], (unsigned long long)mx);
-    if (fb) atomicAdd(&ws[kPcaFallback], fb);
-    if (dg) atomicAdd(&ws[kPcaDegenerate], dg);
-    if (nt) atomicAdd(&ws[kPcaNodeTests], nt);
-    if (pt) atomicAdd(&ws[kPcaPointTests], pt);
-  }
 }
 
 // ---- 1. the bound --------------------------------------------------------------------------------------------------------------------
@@ -187,138 +129,43 @@ __global__ void __launch_bounds__(kPcaFlatBlock) pca_bound_kernel(const int32_t 
   bound_last[j] = last;
 }
 
-// ---- 3. the walk ---------------------------------------------------------------------------------------------------------------------
-// Teams of a wave loop in lock step: no __syncthreads, only t_wave_sync.
-__global__ void __launch_bounds__(kPcaBlock) __attribute__((amdgpu_waves_per_eu(4))) pca_walk_kernel(PcaArgs a) {
-  __shared__ int32_t stack_mem[4 * kWalkStack];
-  __shared__ WalkLevel levels[LBVH_WIDE_LEVELS];
-  __shared__ int32_t range_mem[4 * kPcaRanges];
-  __shared__ uint32_t range_n_mem[4];
-  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kWalkStack;
-  int32_t *range = range_mem + team * kPcaRanges;
-  uint32_t *range_n = range_n_mem + team;
-  walk_fill_levels<1>(levels, &a.wide, lane);
-  if (tl == 0) *range_n = 0u;
-  t_wave_sync();
-  const LbvhWideView &wv = a.wide;
-  const int32_t clean_end = lane_clean_end(a.bvh);
-  unsigned long long node_tests = 0, point_tests = 0, total = 0, degenerate = 0;
-  unsigned int max_row = 0;
-  for (;;) {
-    int got = 0;
-    if (lane == 0) got = (int)atomicAdd(&a.ws[kPcaCursor], 4ull);
-    const int base = __builtin_amdgcn_readfirstlane(got);
-    if (base >= a.m) break;
-    const int32_t pos = base + team;
-    const bool has_q = pos < a.m;
-    const PcaQuery s = pca_query(a, pos, has_q);
-    const LbvhPoint &q = s.q;
-    const bool active = has_q && !a.force_redo;
-    const WalkBox qb(q, s.r_walk * 1.000001f);  // the box prefilter must not cut what the rounded sphere test accepts
-    const float radius_in2 = s.r > 0.f ? pca_inside2(s.r) : -1.f;
-    uint32_t part = 0;  // my lane's share of the count
-    float acc[9];       // ... of S1 and S2
+// ---- 3. the rule ---------------------------------------------------------------------------------------------------------------------
+struct PcaRule {
+  using Args = PcaArgs;
+  using Query = PcaQuery;
+  static constexpr bool kArith = false, kRolled = true;
+  static constexpr int kTeamLds = 0;
+  struct Lane {
+    float acc[9];  // my lane's share of S1 and S2
+  };
+  static __device__ __forceinline__ Query query(const Args &a, int32_t pos, bool has_q) { return pca_query(a, pos, has_q); }
+  static __device__ __forceinline__ void start(Lane &st, unsigned long long *) {
 #pragma unroll
-    for (int c = 0; c < 9; c++) acc[c] = 0.f;
-    // lane tl takes point tl of the sixteen slots from `slot0` (the sorted arrays are padded with NaN sentinels to whole blocks)
-    auto test_points = [&](int64_t slot0, bool has_b) __attribute__((always_inline)) {
-      const int64_t slot = slot0 + tl;
-      LbvhPoint p = LbvhPoint{pca_nan(), 0.f, 0.f, -1};
-      if (has_b) p = a.bvh.points[slot];
-      const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-      const float d = knn_sqrt(t_dist2(dx, dy, dz));
-      const bool hit = has_b && pca_member(a, s, (int32_t)slot, p, d);
-      point_tests += has_b ? 1u : 0u;
-      part = t_count(part, __ballot(hit));
-      if (hit) pca_add(acc, dx, dy, dz);
-    };
-    bool overflow = wv.levels <= 0;
-    if (wv.levels > 0)
-      walk_tree<true>(
-          levels, wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
-          [&](const LbvhBox &bx, int32_t c, int lvl) {
-            if (lvl == 0) return true;
-            const float ax = fmaxf(fabsf(q.x - bx.lo[0]), fabsf(q.x - bx.hi[0])), ay = fmaxf(fabsf(q.y - bx.lo[1]), fabsf(q.y - bx.hi[1])),
-                        az = fmaxf(fabsf(q.z - bx.lo[2]), fabsf(q.z - bx.hi[2]));
-            const float far2 = t_dist2(ax, ay, az);
-            const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
-            if (!(far2 <= radius_in2 && ((int64_t)c + 1) * span <= (int64_t)clean_end)) return true;
-            const uint32_t at = atomicAdd(range_n, 1u);
-            if (at >= (uint32_t)kPcaRanges) return true;
-            range[at] = (lvl << 26) | c;
-            return false;
-          },
-          [&](int32_t b, bool has_b) { test_points((int64_t)b * LBVH_BLOCK, has_b); }, [] {}, overflow);
-    // the noted inside boxes, sixteen slots a step (every point but the query's own passes; the literal test decides all the same)
-    t_wave_sync();
-    const uint32_t nr = min(*range_n, (uint32_t)kPcaRanges);
-    for (uint32_t i = 0; __ballot(i < nr) != 0ull; i++) {
-      const bool has_r = i < nr;
-      const int32_t e = has_r ? range[i] : 0;
-      const int64_t span = has_r ? (int64_t)LBVH_BLOCK << (6 * (e >> 26)) : 0;
-      const int64_t first = (int64_t)(e & 0x3ffffff) * span;
-#pragma unroll 1
-      for (int64_t t = 0; __ballot(t < span) != 0ull; t += LBVH_BLOCK) test_points(first + t, t < span);
-    }
-    t_wave_sync();
-    if (tl == 0) *range_n = 0u;
-    t_wave_sync();
-    // the one reduction of the row
-    const uint32_t cnt = t_team_sum(part);
-#pragma unroll
-    for (int c = 0; c < 9; c++) acc[c] = pca_team_sum(acc[c]);
-    if (has_q && tl == 0) {
-      if (overflow || a.force_redo) {
-        // left to the lane kernel, which starts the row again: nothing of it is counted here
-        a.redo[atomicAdd(&a.ws[kPcaRedo], 1ull)] = pos;
-      } else {
-        pca_store(a, s.at, cnt, acc);
-        total += cnt;
-        max_row = max(max_row, cnt);
-        degenerate += cnt < (uint32_t)a.min_points ? 1u : 0u;
-      }
-    }
+    for (int c = 0; c < 9; c++) st.acc[c] = 0.f;
   }
-  pca_add_stats(a.ws, lane, total, max_row, 0ull, degenerate, node_tests, point_tests);
-}
-
-// ---- 4. one query per lane: the queries of the redo list ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(kPcaLaneBlock) pca_lane_kernel(PcaArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * kPcaLaneBlock + threadIdx.x;
-  const bool has_q = t < (int64_t)a.ws[kPcaRedo];
-  const int32_t pos = has_q ? a.redo[t] : 0;
-  const PcaQuery s = pca_query(a, pos, has_q);
-  const LbvhPoint &q = s.q;
-  const float r_wide = s.r_walk * 1.000001f;
-  uint32_t cnt = 0;
-  float acc[9];
+  static __device__ __forceinline__ bool member(const Args &a, const Query &s, int32_t slot, const LbvhPoint &p, float d) { return pca_member(a, s, slot, p, d); }
+  static __device__ __forceinline__ void lane_take(const Args &, const Query &, Lane &st, uint32_t, int64_t, const LbvhPoint &, float dx, float dy, float dz, float,
+                                                   float) {
+    pca_add(st.acc, dx, dy, dz);
+  }
+  static __device__ __forceinline__ void take(const Args &, const Query &, Lane &st, uint32_t &part, bool hit, int64_t, const LbvhPoint &, float dx, float dy,
+                                              float dz, float, float, int, int) {
+    part = t_count(part, __ballot(hit));
+    if (hit) pca_add(st.acc, dx, dy, dz);
+  }
+  static __device__ __forceinline__ uint32_t row_end(const Args &, const Query &, Lane &st, uint32_t part, int, int) {
 #pragma unroll
-  for (int c = 0; c < 9; c++) acc[c] = 0.f;
-  unsigned long long node_tests = 0, point_tests = 0;
-  if (has_q)
-    lane_walk<LaneRope::kWithNode>(a.bvh,
-        [&](int32_t, const LbvhNode &nd, int32_t) {
-          node_tests++;
-          return lane_box_hit(nd, q, r_wide) ? lane_descend() : lane_rope();
-        },
-        [&](int32_t slot, const LbvhPoint &p) {
-          point_tests++;
-          const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-          const float d = knn_sqrt(t_dist2(dx, dy, dz));
-          if (pca_member(a, s, slot, p, d)) {
-            cnt++;
-            pca_add(acc, dx, dy, dz);
-          }
-          return lane_rope();
-        });
-  if (has_q) pca_store(a, s.at, cnt, acc);
-  // (all lanes of the wave are here)
-  pca_add_stats(a.ws, threadIdx.x & 63, has_q ? cnt : 0u, has_q ? cnt : 0u, has_q ? 1u : 0u, has_q && cnt < (uint32_t)a.min_points ? 1u : 0u, node_tests,
-                point_tests);
-}
+    for (int c = 0; c < 9; c++) st.acc[c] = t_team_sum(st.acc[c]);
+    return t_team_sum(part);
+  }
+  static __device__ __forceinline__ unsigned long long row_write(const Args &a, const Query &s, const Lane &st, uint32_t cnt) {
+    pca_store(a, s.at, cnt, st.acc);
+    return cnt < (uint32_t)a.min_points ? 1u : 0u;  // a degenerate row
+  }
+  static __device__ __forceinline__ bool lane_arith(const Args &) { return false; }
+};
 
-// ---- 5. the finish -------------------------------------------------------------------------------------------------------------------
+// ---- 4. the finish -------------------------------------------------------------------------------------------------------------------
 // One Jacobi rotation of the pair (p, q) of a symmetric 3 x 3, r the third index: app, aqq, apq the pair's entries, arp, arq the
 // third row's; the columns p and q of V turn with it.  Every operation fp32 and rounded on its own (tests/pca_spec.py jacobi32
 // restates it operation for operation).
@@ -475,7 +322,7 @@ void Engine::local_pca(const tknnLocalPcaOptions &o, tknnLocalPcaInfo *info, hip
   // the call's workspace (the layout: the file head)
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t order_bytes = own ? 0 : query_order_sort_bytes(m, s);
-  const size_t words_b = align(kPcaWords * sizeof(unsigned long long)), col_b = align(((size_t)m + 1) * sizeof(uint32_t)), order_cols = own ? 0 : 4 * col_b,
+  const size_t words_b = align(kRadWords * sizeof(unsigned long long)), col_b = align(((size_t)m + 1) * sizeof(uint32_t)), order_cols = own ? 0 : 4 * col_b,
                mom_b = align((size_t)m * kPcaMoments * sizeof(uint32_t)), tmp_b = align(order_bytes);
   char *ws = (char *)workspace(words_b + order_cols + col_b + mom_b + tmp_b);
   uint32_t *codes = (uint32_t *)(ws + words_b), *codes_alt = (uint32_t *)(ws + words_b + col_b), *order_in = (uint32_t *)(ws + words_b + 2 * col_b),
@@ -507,34 +354,24 @@ void Engine::local_pca(const tknnLocalPcaOptions &o, tknnLocalPcaInfo *info, hip
   a.redo = (int32_t *)(ws + words_b + order_cols);
   a.ws = (unsigned long long *)ws;
 
-  OWLMI_HIP(hipMemsetAsync(a.ws, 0, kPcaWords * sizeof(unsigned long long), s));
+  OWLMI_HIP(hipMemsetAsync(a.ws, 0, kRadWords * sizeof(unsigned long long), s));
   if (!own) query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, tmp, order_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_g_, s));
   // the walk, then the lane kernel for what the walk left
-  const int blocks = (int)std::min<int64_t>((m + 3) / 4, (int64_t)cu_count_ * kPcaBlocksPerCu);
-  hipLaunchKernelGGL(pca_walk_kernel, dim3(blocks), dim3(kPcaBlock), 0, s, a);
-  OWLMI_HIP(hipGetLastError());
   unsigned long long *h_words = h_counters_;
-  OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kPcaWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipStreamSynchronize(s));
-  if (const unsigned long long n_redo = h_words[kPcaRedo]) {
-    const unsigned lane_blocks = (unsigned)((n_redo + kPcaLaneBlock - 1) / kPcaLaneBlock);
-    hipLaunchKernelGGL(pca_lane_kernel, dim3(lane_blocks), dim3(kPcaLaneBlock), 0, s, a);
-    OWLMI_HIP(hipGetLastError());
-    OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kPcaWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  }
+  rad_walks<PcaRule>(a, cu_count_, h_words, s);
   OWLMI_HIP(hipEventRecord(ev_h_, s));
   hipLaunchKernelGGL(pca_finish_kernel, dim3(flat_blocks), dim3(kPcaFlatBlock), 0, s, a);
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   OWLMI_HIP(hipStreamSynchronize(s));
   if (info) {
-    info->total = (int64_t)h_words[kPcaTotal];
-    info->max_row = (int64_t)h_words[kPcaMaxRow];
-    info->degenerate_rows = (int64_t)h_words[kPcaDegenerate];
-    info->fallback_items = (int64_t)h_words[kPcaFallback];
-    info->node_tests = (int64_t)h_words[kPcaNodeTests];
-    info->point_tests = (int64_t)h_words[kPcaPointTests];
+    info->total = (int64_t)h_words[kRadTotal];
+    info->max_row = (int64_t)h_words[kRadMaxRow];
+    info->degenerate_rows = (int64_t)h_words[kRadOwn];
+    info->fallback_items = (int64_t)h_words[kRadLaneRows];
+    info->node_tests = (int64_t)h_words[kRadNodeTests];
+    info->point_tests = (int64_t)h_words[kRadPointTests];
     OWLMI_HIP(hipEventElapsedTime(&info->solve_ms, ev_e_, ev_a_));
     if (with_k) OWLMI_HIP(hipEventElapsedTime(&info->bound_ms, ev_e_, ev_f_));
     if (!own) OWLMI_HIP(hipEventElapsedTime(&info->order_ms, ev_f_, ev_g_));

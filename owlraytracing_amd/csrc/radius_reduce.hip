@@ -2,32 +2,24 @@
 // include/owlknn_reduce.h).
 //
 // Row j is a count, a sum of weights w and C sums of w * v_c over the points p of the built set with sqrt((dx*dx + dy*dy) + dz*dz)
-// <= radius: knn_sqrt(knn_dist2(..)) <= r, radius_query.hip's predicate, so the count is that call's row length.  The walk is the
-// count pass of radius_query.hip with accumulators: no (query, neighbour) pair leaves the chip.
+// <= radius: knn_sqrt(knn_dist2(..)) <= r, radius_query.hip's predicate, so the count is that call's row length.  No (query,
+// neighbour) pair leaves the chip.
 //   1. query_order (query_order.h): external queries along the tree's own curve.  The set's own points (d_queries NULL) are taken
 //      in sorted-slot order: position i is slot i, its row prim_id[i]; nothing is ordered.
 //   2. reduce_stage_kernel: d_values, n x C by the caller's row, gathered through prim_id into sorted-slot order in the workspace:
 //      NC floats per slot, NC the channel tier (4, 8, 16: a lane fetches its point's channels as NC / 4 128-bit loads), the slots
 //      padded to whole leaf blocks; padding channels and padding slots are 0.  C = 0: no stage.
-//   3. reduce_walk_kernel<WEIGHT, NC>: persistent, one 16-lane team per query, four teams per wave, walk_tree (team_walk.h) with the
-//      query's box of half-width r (1 + 1e-6).  Lane tl tests point tl of a leaf block with the literal predicate and adds w and
-//      w * v_c into its OWN registers, under the predicate: a lane that has no hit loads no value and multiplies nothing, so what
-//      the values of other points hold (NaN, inf) cannot reach a sum.  One team reduction (DPP row rotations) per query at the
-//      end.  A child box wholly inside the sphere (radius_query.hip's box rule: radius_in2, clean_end): with TKNN_W_ONE and C = 0
-//      its slots are added arithmetically; otherwise a box above the leaf level is noted in the team's range list and its slots
-//      are streamed after the walk without further box tests, a leaf block is tested in place, and a full list means the box is
-//      walked.
-//   4. reduce_lane_kernel<NC>: one query per lane on the rope walk (lane_walk.h), the weight a run-time switch, for the queries
-//      whose team stack overflowed (a redo list whose length lives on the device) -- the result is complete on any tree.
+//   3. rad_walks (radius_walk.h: the walk, the box rule, the lane kernel for what the walk left) with ReduceRule<WEIGHT, NC>: a
+//      lane adds w and w * v_c into its OWN registers, under the predicate: a lane that has no hit loads no value and multiplies
+//      nothing, so what the values of other points hold (NaN, inf) cannot reach a sum.  One team reduction (DPP row rotations)
+//      per query at the end.  With TKNN_W_ONE and C = 0 an inside box is a number of slots; otherwise its slots are streamed.
+//      The lane kernel has the weight as a run-time switch: ReduceRule<kAnyWeight, NC>.
 // The call's workspace (Engine::workspace, one layout):
-//      counters (kRdWords) | codes, sorted codes, order in, order (m + 1 each; external queries only) | redo list, m |
+//      counters (kRadWords) | codes, sorted codes, order in, order (m + 1 each; external queries only) | redo list, m |
 //      staged values, padded n x NC | the sort's temporary
 #include "owlknn_reduce.h"
-#include "lane_walk.h"
 #include "query_order.h"
-#include "team_lanes.h"
-#include "team_walk.h"
-#include "trueknn_engine.h"
+#include "radius_walk.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,14 +31,8 @@ namespace owlmi {
 
 namespace {
 
-constexpr int kReduceBlock = 64;        // one wave per workgroup, four teams
-constexpr int kReduceBlocksPerCu = 16;  // 6.3 KB of LDS each
-constexpr int kReduceLaneBlock = 256;
 constexpr int kReduceFlatBlock = 256;
-constexpr int kReduceRanges = 16;  // inside boxes above the leaf level a team notes for streaming; a 17th is walked
-
-// words of the call's own counters (in the workspace, zeroed per call)
-enum { kRdCursor = 0, kRdRedo = 1, kRdTotal = 2, kRdMaxRow = 3, kRdFallback = 4, kRdNodeTests = 5, kRdPointTests = 6, kRdWords = 8 };
+constexpr int kAnyWeight = -1;  // ReduceRule's WEIGHT where the weight is Args::weight (the lane kernel)
 
 struct ReduceArgs {
   LbvhView bvh;
@@ -56,7 +42,7 @@ struct ReduceArgs {
   int32_t m;
   float radius;
   float radius_wide;  // radius * (1 + 1e-6): the box prefilter must not cut what the rounded sphere test accepts
-  float radius_in2;   // radius^2 * 0.999995, rounded down: a box whose far corner is within it lies inside the sphere
+  float radius_in2;   // radius_inside2(radius): a box whose far corner is within it lies inside the sphere
   float coef;         // GAUSS: -1 / (2 h^2); EPANECHNIKOV: 1 / r^2; CUBIC_SPLINE: 2 / r
   int weight;         // TKNN_W_* (the lane kernel's switch)
   int channels;       // C
@@ -70,10 +56,8 @@ struct ReduceArgs {
   float *wsum;               // m, may be null
   float *out;                // m x C, null with C = 0
   int32_t *redo;             // m: positions left to the lane kernel
-  unsigned long long *ws;    // kRdWords counters
+  unsigned long long *ws;    // kRadWords counters
 };
-
-__device__ __forceinline__ float rd_nan() { return __uint_as_float(0x7fc00000u); }
 
 // ---- the weights ---------------------------------------------------------------------------------------------------------------------
 // of a point that passed the predicate: d2 = knn_dist2, d = knn_sqrt(d2), every operation rounded on its own
@@ -118,30 +102,6 @@ __device__ __forceinline__ void rd_add(const float *values, int64_t slot, float 
   }
 }
 
-// sum over the 16 lanes of my team (lane 0 of the team reads it; the order of the additions differs by lane)
-__device__ __forceinline__ float rd_team_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128 /*row_ror:8*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124 /*row_ror:4*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122 /*row_ror:2*/, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121 /*row_ror:1*/, 0xf, 0xf, false));
-  return v;
-}
-
-// the query at position `pos`: its coordinates, the row its results go to, and the slot to leave out (-1: none)
-__device__ __forceinline__ void rd_query(const ReduceArgs &a, int32_t pos, bool has_q, LbvhPoint &q, int32_t &row, int32_t &self) {
-  self = -1;
-  if (a.queries) {
-    row = has_q ? (int32_t)a.order[pos] : 0;
-    q.x = a.queries[3 * (int64_t)row], q.y = a.queries[3 * (int64_t)row + 1], q.z = a.queries[3 * (int64_t)row + 2];
-  } else {
-    const int32_t slot = has_q ? pos : 0;
-    q = a.bvh.points[slot];
-    row = a.bvh.prim_id[slot];
-    if (a.skip_self && has_q) self = slot;
-  }
-  q.id = -1;
-}
-
 // one finished row, by the one lane that holds its sums
 template <int NC>
 __device__ __forceinline__ void rd_write(const ReduceArgs &a, int32_t row, uint32_t cnt, float wsum, const float (&acc)[NC > 0 ? NC : 1]) {
@@ -158,21 +118,6 @@ __device__ __forceinline__ void rd_write(const ReduceArgs &a, int32_t row, uint3
   }
 }
 
-__device__ __forceinline__ void rd_add_stats(unsigned long long *ws, int lane, unsigned long long total, unsigned int max_row, unsigned long long fallback,
-                                             unsigned long long node_tests, unsigned long long point_tests) {
-  const unsigned long long tsum = t_wave_sum(total), fb = t_wave_sum(fallback), nt = t_wave_sum(node_tests), pt = t_wave_sum(point_tests);
-  unsigned int mx = max_row;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned int)__shfl_xor((int)mx, off));
-  if (lane == 0) {
-    if (tsum) atomicAdd(&ws[kRdTotal], tsum);
-    if (mx) atomicMax(&ws[kRdMaxRow], (unsigned long long)mx);
-    if (fb) atomicAdd(&ws[kRdFallback], fb);
-    if (nt) atomicAdd(&ws[kRdNodeTests], nt);
-    if (pt) atomicAdd(&ws[kRdPointTests], pt);
-  }
-}
-
 // ---- 2. the stage ----------------------------------------------------------------------------------------------------------------------
 template <int NC>
 __global__ void __launch_bounds__(kReduceFlatBlock) reduce_stage_kernel(ReduceArgs a) {
@@ -185,174 +130,63 @@ __global__ void __launch_bounds__(kReduceFlatBlock) reduce_stage_kernel(ReduceAr
   a.values[t] = v;
 }
 
-// ---- 3. the walk -----------------------------------------------------------------------------------------------------------------------
-// The box rule is radius_query.hip's: a child box whose far corner is within radius_in2 and whose slots end before clean_end holds
-// only points that pass the literal test.  Teams of a wave loop in lock step: no __syncthreads, only t_wave_sync.
+// ---- 3. the rule -----------------------------------------------------------------------------------------------------------------------
+// WEIGHT: a TKNN_W_* the walk is compiled for, or kAnyWeight: Args::weight decides (then ONE's sums are 1 * v, which is v).
 template <int WEIGHT, int NC>
-__global__ void __launch_bounds__(kReduceBlock) __attribute__((amdgpu_waves_per_eu(4))) reduce_walk_kernel(ReduceArgs a) {
-  constexpr bool kOne = WEIGHT == TKNN_W_ONE;
-  constexpr bool kArith = kOne && NC == 0;  // an inside box is a number of slots, nothing of it is read
-  __shared__ int32_t stack_mem[4 * kWalkStack];
-  __shared__ WalkLevel levels[LBVH_WIDE_LEVELS];
-  __shared__ int32_t range_mem[kArith ? 1 : 4 * kReduceRanges];
-  __shared__ uint32_t range_n_mem[4];
-  const int lane = threadIdx.x & 63, team = lane >> 4, tl = lane & 15;
-  int32_t *stack = stack_mem + team * kWalkStack;
-  int32_t *range = range_mem + (kArith ? 0 : team * kReduceRanges);
-  uint32_t *range_n = range_n_mem + team;
-  walk_fill_levels<1>(levels, &a.wide, lane);
-  if (tl == 0) *range_n = 0u;
-  t_wave_sync();
-  const LbvhWideView &wv = a.wide;
-  const int32_t clean_end = lane_clean_end(a.bvh);
-  unsigned long long node_tests = 0, point_tests = 0, total = 0;
-  unsigned int max_row = 0;
-  for (;;) {
-    int got = 0;
-    if (lane == 0) got = (int)atomicAdd(&a.ws[kRdCursor], 4ull);
-    const int base = __builtin_amdgcn_readfirstlane(got);
-    if (base >= a.m) break;
-    const int32_t pos = base + team;
-    const bool has_q = pos < a.m;
+struct ReduceRule {
+  using Args = ReduceArgs;
+  static constexpr bool kOne = WEIGHT == TKNN_W_ONE;
+  static constexpr bool kArith = kOne && NC == 0, kRolled = NC >= 8;
+  static constexpr int kTeamLds = 0;
+  struct Query {
     LbvhPoint q;
-    int32_t row, self;
-    rd_query(a, pos, has_q, q, row, self);
-    const bool active = has_q && !a.force_redo;
-    const WalkBox qb(q, a.radius_wide);
-    uint32_t part = 0;  // my lane's share of the count
-    float wacc = 0.f;   // ... of the sum of weights
+    int32_t row, self;  // self: the query's own slot where it is left out
+    float r, r_wide, in2;
+  };
+  struct Lane {
+    float wacc;                  // my lane's share of the sum of weights
     float acc[NC > 0 ? NC : 1];  // ... of the sums of w * v_c
+  };
+  static __device__ __forceinline__ Query query(const Args &a, int32_t pos, bool has_q) {
+    Query s;
+    const int32_t slot = rad_point(a, pos, has_q, s.q, s.row);
+    s.q.id = -1;
+    s.self = a.skip_self && has_q ? slot : -1;
+    s.r = a.radius, s.r_wide = a.radius_wide, s.in2 = a.radius_in2;
+    return s;
+  }
+  static __device__ __forceinline__ void start(Lane &st, unsigned long long *) {
+    st.wacc = 0.f;
 #pragma unroll
-    for (int c = 0; c < (NC > 0 ? NC : 1); c++) acc[c] = 0.f;
-    // lane tl takes point tl of the sixteen slots from `slot0` (the sorted arrays are padded with NaN sentinels to whole blocks)
-    auto test_points = [&](int64_t slot0, bool has_b) __attribute__((always_inline)) {
-      const int64_t slot = slot0 + tl;
-      LbvhPoint p = LbvhPoint{rd_nan(), 0.f, 0.f, -1};
-      if (has_b) p = a.bvh.points[slot];
-      const float d2 = knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z);
-      const float d = knn_sqrt(d2);
-      const bool hit = has_b && d <= a.radius && slot != (int64_t)self;  // (a NaN on either side: not a neighbour)
-      point_tests += has_b ? 1u : 0u;
-      part = t_count(part, __ballot(hit));
-      if constexpr (!kArith) {
-        if (hit) rd_add<NC, kOne>(a.values, slot, rd_weight<WEIGHT>(d2, d, a.coef), wacc, acc);
-      }
-    };
-    bool overflow = wv.levels <= 0;
-    if (wv.levels > 0)
-      walk_tree<(NC >= 8)>(
-          levels, wv, stack, kWalkStack, active, q, qb, team, tl, node_tests,
-          [&](const LbvhBox &bx, int32_t c, int lvl) {
-            const float ax = fmaxf(fabsf(q.x - bx.lo[0]), fabsf(q.x - bx.hi[0])), ay = fmaxf(fabsf(q.y - bx.lo[1]), fabsf(q.y - bx.hi[1])),
-                        az = fmaxf(fabsf(q.z - bx.lo[2]), fabsf(q.z - bx.hi[2]));
-            const float far2 = t_dist2(ax, ay, az);
-            const int64_t span = (int64_t)LBVH_BLOCK << (6 * lvl);  // points under one child of this level
-            if (!(far2 <= a.radius_in2 && ((int64_t)c + 1) * span <= (int64_t)clean_end)) return true;
-            if constexpr (kArith) {
-              const bool mine = (int64_t)self >= (int64_t)c * span && (int64_t)self < ((int64_t)c + 1) * span;  // (self = -1: never)
-              part += (uint32_t)span - (mine ? 1u : 0u);
-              return false;
-            } else {
-              if (lvl == 0) return true;
-              const uint32_t at = atomicAdd(range_n, 1u);
-              if (at >= (uint32_t)kReduceRanges) return true;
-              range[at] = (lvl << 26) | c;
-              return false;
-            }
-          },
-          [&](int32_t b, bool has_b) { test_points((int64_t)b * LBVH_BLOCK, has_b); }, [] {}, overflow);
-    if constexpr (!kArith) {
-      // the noted inside boxes, sixteen slots a step (every point passes; the literal test costs one compare and decides)
-      t_wave_sync();
-      const uint32_t nr = min(*range_n, (uint32_t)kReduceRanges);
-      for (uint32_t i = 0; __ballot(i < nr) != 0ull; i++) {
-        const bool has_r = i < nr;
-        const int32_t e = has_r ? range[i] : 0;
-        const int64_t span = has_r ? (int64_t)LBVH_BLOCK << (6 * (e >> 26)) : 0;
-        const int64_t first = (int64_t)(e & 0x3ffffff) * span;
-#pragma unroll 1
-        for (int64_t s = 0; __ballot(s < span) != 0ull; s += LBVH_BLOCK) test_points(first + s, s < span);
-      }
-      t_wave_sync();
-      if (tl == 0) *range_n = 0u;
-      t_wave_sync();
-    }
-    // the one reduction of the row
-    const uint32_t cnt = t_team_sum(part);
-    const float wsum = kOne ? (float)cnt : rd_team_sum(wacc);
+    for (int c = 0; c < (NC > 0 ? NC : 1); c++) st.acc[c] = 0.f;
+  }
+  static __device__ __forceinline__ bool one(const Args &a) { return WEIGHT == kAnyWeight ? a.weight == TKNN_W_ONE : kOne; }
+  static __device__ __forceinline__ bool member(const Args &, const Query &s, int32_t slot, const LbvhPoint &, float d) { return d <= s.r && slot != s.self; }
+  static __device__ __forceinline__ void lane_take(const Args &a, const Query &, Lane &st, uint32_t, int64_t slot, const LbvhPoint &, float, float, float, float d2,
+                                                   float d) {
+    const float w = WEIGHT == kAnyWeight ? rd_weight_of(a.weight, d2, d, a.coef) : rd_weight<WEIGHT>(d2, d, a.coef);
+    rd_add<NC, kOne>(a.values, slot, w, st.wacc, st.acc);
+  }
+  static __device__ __forceinline__ void take(const Args &a, const Query &s, Lane &st, uint32_t &part, bool hit, int64_t slot, const LbvhPoint &p, float dx,
+                                              float dy, float dz, float d2, float d, int, int) {
+    part = t_count(part, __ballot(hit));
+    if constexpr (!kArith)
+      if (hit) lane_take(a, s, st, 0u, slot, p, dx, dy, dz, d2, d);
+  }
+  static __device__ __forceinline__ uint32_t row_end(const Args &, const Query &, Lane &st, uint32_t part, int, int) {
+    if constexpr (!kOne) st.wacc = t_team_sum(st.wacc);
     if constexpr (NC > 0) {
 #pragma unroll
-      for (int c = 0; c < NC; c++) acc[c] = rd_team_sum(acc[c]);
+      for (int c = 0; c < NC; c++) st.acc[c] = t_team_sum(st.acc[c]);
     }
-    if (has_q && tl == 0) {
-      if (overflow || a.force_redo) {
-        // left to the lane kernel, which starts the row again: nothing of it is counted here
-        a.redo[atomicAdd(&a.ws[kRdRedo], 1ull)] = pos;
-      } else {
-        rd_write<NC>(a, row, cnt, wsum, acc);
-        total += cnt;
-        max_row = max(max_row, cnt);
-      }
-    }
+    return t_team_sum(part);
   }
-  rd_add_stats(a.ws, lane, total, max_row, 0ull, node_tests, point_tests);
-}
-
-// ---- 4. one query per lane: the queries of the redo list -----------------------------------------------------------------------------
-template <int NC>
-__global__ void __launch_bounds__(kReduceLaneBlock) reduce_lane_kernel(ReduceArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * kReduceLaneBlock + threadIdx.x;
-  const bool has_q = t < (int64_t)a.ws[kRdRedo];
-  const int32_t pos = has_q ? a.redo[t] : 0;
-  const int32_t clean_end = lane_clean_end(a.bvh);
-  const bool arith = a.weight == TKNN_W_ONE && NC == 0;
-  LbvhPoint q;
-  int32_t row, self;
-  rd_query(a, pos, has_q, q, row, self);
-  uint32_t cnt = 0;
-  float wacc = 0.f;
-  float acc[NC > 0 ? NC : 1];
-#pragma unroll
-  for (int c = 0; c < (NC > 0 ? NC : 1); c++) acc[c] = 0.f;
-  unsigned long long node_tests = 0, point_tests = 0;
-  if (has_q)
-    lane_walk<LaneRope::kWithNode>(a.bvh,
-        [&](int32_t ref, const LbvhNode &nd, int32_t) {
-          node_tests++;
-          if (!lane_box_hit(nd, q, a.radius_wide)) return lane_rope();
-          if (arith) {  // a node inside the sphere is counted, not walked (radius_lane_kernel; the margin: radius_in2)
-            float far2, near2;
-            lane_box_dist2(nd, q, far2, near2);
-            const int32_t first = lbvh_first(ref, nd.other), last = lbvh_last(ref, nd.other);
-            if (far2 <= a.radius_in2 && last < clean_end) {
-              cnt += (uint32_t)(last - first + 1) - (self >= first && self <= last ? 1u : 0u);
-              return lane_rope();
-            }
-          }
-          return lane_descend();
-        },
-        [&](int32_t slot, const LbvhPoint &p) {
-          point_tests++;
-          const float d2 = knn_dist2(p.x, p.y, p.z, q.x, q.y, q.z);
-          const float d = knn_sqrt(d2);
-          if (d <= a.radius && slot != self) {
-            cnt++;
-            if (!arith) rd_add<NC, false>(a.values, slot, rd_weight_of(a.weight, d2, d, a.coef), wacc, acc);  // (ONE: 1 * v is v)
-          }
-          return lane_rope();
-        });
-  if (has_q) rd_write<NC>(a, row, cnt, a.weight == TKNN_W_ONE ? (float)cnt : wacc, acc);
-  // (all lanes of the wave are here)
-  rd_add_stats(a.ws, threadIdx.x & 63, has_q ? cnt : 0u, has_q ? cnt : 0u, has_q ? 1u : 0u, node_tests, point_tests);
-}
-
-// r^2 * 0.999995 in double, rounded DOWN to fp32 (radius_query.hip's box rule)
-inline float reduce_inside2(float r) {
-  const double want = (double)r * (double)r * 0.999995;
-  float f = (float)want;
-  if ((double)f > want) f = std::nextafterf(f, 0.f);
-  return f;
-}
+  static __device__ __forceinline__ unsigned long long row_write(const Args &a, const Query &s, const Lane &st, uint32_t cnt) {
+    rd_write<NC>(a, s.row, cnt, one(a) ? (float)cnt : st.wacc, st.acc);
+    return 0ull;
+  }
+  static __device__ __forceinline__ bool lane_arith(const Args &a) { return one(a) && NC == 0; }
+};
 
 // f(std::integral_constant<int, NC>{}) for the channel tier that serves C channels
 template <class F>
@@ -388,7 +222,7 @@ void Engine::radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInf
   // the call's workspace (the layout: the file head)
   auto align = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t order_bytes = own ? 0 : query_order_sort_bytes(m, s);
-  const size_t words_b = align(kRdWords * sizeof(unsigned long long)), col_b = align(((size_t)m + 1) * sizeof(uint32_t)), order_cols = own ? 0 : 4 * col_b,
+  const size_t words_b = align(kRadWords * sizeof(unsigned long long)), col_b = align(((size_t)m + 1) * sizeof(uint32_t)), order_cols = own ? 0 : 4 * col_b,
                stage_b = align((size_t)padded * (size_t)nc * sizeof(float)), tmp_b = align(order_bytes);
   char *ws = (char *)workspace(words_b + order_cols + col_b + stage_b + tmp_b);
   uint32_t *codes = (uint32_t *)(ws + words_b), *codes_alt = (uint32_t *)(ws + words_b + col_b), *order_in = (uint32_t *)(ws + words_b + 2 * col_b),
@@ -404,7 +238,7 @@ void Engine::radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInf
   a.m = (int32_t)m;
   a.radius = o.radius;
   a.radius_wide = o.radius * 1.000001f;
-  a.radius_in2 = reduce_inside2(o.radius);
+  a.radius_in2 = radius_inside2(o.radius);
   a.weight = o.weight;
   if (o.weight == TKNN_W_GAUSS) a.coef = (float)(-0.5 / ((double)o.bandwidth * (double)o.bandwidth));
   if (o.weight == TKNN_W_EPANECHNIKOV) a.coef = (float)(1.0 / ((double)o.radius * (double)o.radius));
@@ -423,7 +257,7 @@ void Engine::radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInf
   a.ws = (unsigned long long *)ws;
 
   OWLMI_HIP(hipEventRecord(ev_a_, s));
-  OWLMI_HIP(hipMemsetAsync(a.ws, 0, kRdWords * sizeof(unsigned long long), s));
+  OWLMI_HIP(hipMemsetAsync(a.ws, 0, kRadWords * sizeof(unsigned long long), s));
   if (!own) query_order(o.d_queries, m, bvh_.scene_device(), bvh_.curve(), codes, codes_alt, order_in, order, tmp, order_bytes, s);
   OWLMI_HIP(hipEventRecord(ev_b_, s));
   if (nc > 0) {
@@ -436,30 +270,21 @@ void Engine::radius_reduce(const tknnRadiusReduceOptions &o, tknnRadiusReduceInf
   }
   OWLMI_HIP(hipEventRecord(ev_c_, s));
   // the walk, then the lane kernel for what the walk left
-  const int blocks = (int)std::min<int64_t>((m + 3) / 4, (int64_t)cu_count_ * kReduceBlocksPerCu);
+  unsigned long long *h_words = h_counters_;
   reduce_weight_case(o.weight, [&](auto weight) {
     reduce_tier(C, [&](auto tier) {
-      hipLaunchKernelGGL((reduce_walk_kernel<decltype(weight)::value, decltype(tier)::value>), dim3(blocks), dim3(kReduceBlock), 0, s, a);
+      constexpr int NC = decltype(tier)::value;
+      rad_walks<ReduceRule<decltype(weight)::value, NC>, ReduceRule<kAnyWeight, NC>>(a, cu_count_, h_words, s);
     });
   });
-  OWLMI_HIP(hipGetLastError());
-  unsigned long long *h_words = h_counters_;
-  OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kRdWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  OWLMI_HIP(hipStreamSynchronize(s));
-  if (const unsigned long long n_redo = h_words[kRdRedo]) {
-    const unsigned lane_blocks = (unsigned)((n_redo + kReduceLaneBlock - 1) / kReduceLaneBlock);
-    reduce_tier(C, [&](auto tier) { hipLaunchKernelGGL(reduce_lane_kernel<decltype(tier)::value>, dim3(lane_blocks), dim3(kReduceLaneBlock), 0, s, a); });
-    OWLMI_HIP(hipGetLastError());
-    OWLMI_HIP(hipMemcpyAsync(h_words, a.ws, kRdWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  }
   OWLMI_HIP(hipEventRecord(ev_d_, s));
   OWLMI_HIP(hipStreamSynchronize(s));
   if (info) {
-    info->total = (int64_t)h_words[kRdTotal];
-    info->max_row = (int64_t)h_words[kRdMaxRow];
-    info->fallback_items = (int64_t)h_words[kRdFallback];
-    info->node_tests = (int64_t)h_words[kRdNodeTests];
-    info->point_tests = (int64_t)h_words[kRdPointTests];
+    info->total = (int64_t)h_words[kRadTotal];
+    info->max_row = (int64_t)h_words[kRadMaxRow];
+    info->fallback_items = (int64_t)h_words[kRadLaneRows];
+    info->node_tests = (int64_t)h_words[kRadNodeTests];
+    info->point_tests = (int64_t)h_words[kRadPointTests];
     OWLMI_HIP(hipEventElapsedTime(&info->solve_ms, ev_a_, ev_d_));
     if (!own) OWLMI_HIP(hipEventElapsedTime(&info->order_ms, ev_a_, ev_b_));
     if (nc > 0) OWLMI_HIP(hipEventElapsedTime(&info->stage_ms, ev_b_, ev_c_));

@@ -152,6 +152,27 @@ def test_every_output_alone_gives_the_same_bits(eng, monkeypatch):
             assert pair["cov"].tobytes() == everything["cov"].tobytes() and np.array_equal(np.abs(pair["normals"]), np.abs(everything["normals"]))
 
 
+@pytest.mark.parametrize("name", ("n17", "n1025"))
+def test_radius_counts_are_the_lists_lengths_and_the_sums_counts(eng, name, monkeypatch):
+    """With a radius only, a row's count is radius_query's row length for external queries and radius_reduce's count for the own
+    points without themselves: the three calls walk alike (radius_walk.h) and differ in their rules.  At the `half` radius of
+    reduce_spec's sets more boxes lie inside the sphere than a team's range list holds."""
+    c = ps.rd.case(name)
+    r = c["radii"]["half"]
+    eng.build(c["P"])
+    lengths = np.diff(eng.radius_query(c["Q"], r, sort=False, want_dist=False)["offsets"].cpu().numpy())
+    sums = eng.radius_reduce(r, skip_self=True, want_wsum=False)["counts"].cpu().numpy()
+    for fallback in (False, True):
+        if fallback:
+            monkeypatch.setenv(FALLBACK, "1")
+        ext = eng.local_pca(radius=r, queries=c["Q"], want=("counts",))
+        own = eng.local_pca(radius=r, skip_self=True, want=("counts",))
+        assert np.array_equal(ext["counts"].cpu().numpy(), lengths), "external queries%s" % (" (lane kernel)" if fallback else "")
+        assert np.array_equal(own["counts"].cpu().numpy(), sums), "own points, skip_self%s" % (" (lane kernel)" if fallback else "")
+        assert ext["info"]["total"] == lengths.sum() and own["info"]["total"] == sums.sum()
+        assert not fallback or (ext["info"]["fallback_items"] == len(c["Q"]) and own["info"]["fallback_items"] == len(c["P"]))
+
+
 def test_normals_is_local_pca_with_three_outputs(eng):
     c = ps.case("sphere1025")
     eng.build(c["P"])
