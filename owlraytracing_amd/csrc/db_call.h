@@ -63,7 +63,6 @@ struct Engine::DbCall {
   void exclusive_sum(const int32_t *in, int32_t *out, int count);  // the library's, over at most n words (scan_tmp, scan_bytes)
   void probe_setup();
   void cluster_setup(float eps, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, bool with_side, bool by_point, bool groups_wanted);
-  void join_side();
   void read_back();
   void cluster(float eps, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts, bool by_point);
   void assign(float eps, int32_t *d_labels, const int32_t *core_label, tknnDbscanInfo *info);

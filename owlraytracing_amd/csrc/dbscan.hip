@@ -106,16 +106,8 @@ void Engine::DbCall::cluster_setup(float eps, int32_t *d_labels, uint8_t *d_core
   // every point's group, for the union pass; kept in the caller's label array, which is written last
   a.group_of = groups_wanted ? d_labels : nullptr;
   a.diag_out = e.counters_ + kDbDiag;
-  join_side();
   reset_counters();
   OWLMI_HIP(hipEventRecord(e.ev_a_, s));
-}
-void Engine::DbCall::join_side() {
-  if (!e.db_side_pending_) return;
-  // a call that threw between its side launch and its rejoin has left db_border_walk_kernel running on the workspace
-  // and the counters this call is about to reset: nothing of this call before that kernel has ended
-  OWLMI_HIP(hipStreamWaitEvent(s, e.ev_side_b_, 0));
-  e.db_side_pending_ = false;
 }
 // the counters to the host; returns when the stream has run dry
 void Engine::DbCall::read_back() {
@@ -167,7 +159,6 @@ void Engine::DbCall::query(float eps, const float *d_queries, int64_t m, const i
   a.rank = db_at<int32_t>(ws, w.pos), a.next_core = next_core = db_at<int32_t>(ws, w.next_core);
   a.core_sorted = db_at<uint8_t>(ws, w.core_sorted), block_places = db_at<int32_t>(ws, w.block_places);
   uint32_t *order = db_at<uint32_t>(ws, w.order);
-  join_side();
   reset_counters();
   OWLMI_HIP(hipEventRecord(e.ev_a_, s));
   core_from_labels(core_label);

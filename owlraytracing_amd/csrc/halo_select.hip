@@ -106,6 +106,8 @@ __global__ void __launch_bounds__(kSelBlock) point_select_kernel(SelectArgs a) {
 
 }  // namespace
 
+size_t Engine::halo_mask_bytes(int64_t blocks) { return ((size_t)blocks + kMaxPeers) * sizeof(unsigned long long); }
+
 void Engine::halo_select(const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
                          int64_t *d_counts, const int64_t *d_offsets, float *d_rows, hipStream_t s, const int64_t *d_caps) {
   if (npeers < 1 || npeers > kMaxPeers) throw ArgError{TKNN_E_ARG, "tknnHaloSelect: 1 <= npeers <= 64"};
@@ -125,7 +127,7 @@ void Engine::halo_select(const float *d_boxes, const int32_t *d_box_peer, int32_
   if ((int64_t)a.nblocks > halo_mask_cap_) {
     if (halo_mask_) (void)hipFree(halo_mask_);
     halo_mask_ = nullptr;
-    OWLMI_HIP(hipMalloc((void **)&halo_mask_, (size_t)a.nblocks * sizeof(unsigned long long) + kMaxPeers * sizeof(unsigned long long)));
+    OWLMI_HIP(hipMalloc((void **)&halo_mask_, halo_mask_bytes(a.nblocks)));
     halo_mask_cap_ = a.nblocks;
   }
   a.block_mask = halo_mask_;

@@ -79,6 +79,7 @@ constexpr int kCounterWords = kStatBase + kStatStripes * kStatStride;
 // the host's copy (Engine::h_counters_): folded words first, the stripes as fetched from kHostStripes on; an RT-DBSCAN call
 // also keeps the group list's length, the stack overflows and the not-core list's length in the words named here
 constexpr int kHostStripes = 16, kHostDbGroups = 8, kHostDbOverflows = 9, kHostDbNotCore = 10;
+constexpr int kHostCounterWords = kHostStripes + (kDbStripes * kDbStripeWords > kStatStripes * kStatStride ? kDbStripes * kDbStripeWords : kStatStripes * kStatStride);
 // edge: one of the tied candidates may be the best one LEFT OUT of the row (or the kernel cannot tell): only a walk finds it.
 // Without it every tie lies between two written entries, and tie_fix_kernel first looks whether the pairs' candidates became
 // candidates at the same level (coincident points -- duplicates of a data set -- always do): then the row stands as it is.

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h and include/owlknn_hdbscan.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -94,13 +94,16 @@ int guarded(F &&f) {
   }
 }
 
-// One call on an engine: a NULL engine is refused before any device is touched, `f(call)` runs on the engine's device.
+// One call on an engine: a NULL engine is refused before any device is touched, `f(call)` runs on the engine's device.  The
+// call's stream first waits for a DBSCAN side launch that an earlier call left without a rejoin (Engine::join_side): whatever
+// the call is, it is about to lay its own columns over the workspace that kernel works on.
 template <typename F>
-int api(const char *fn, tknnEngine e, F &&f) {
+int api(const char *fn, tknnEngine e, void *stream, F &&f) {
   return guarded([&] {
     const Call c{fn, e};
     c.need(e, "the engine");
     DeviceScope scope(e->impl.device());
+    e->impl.join_side((hipStream_t)stream);
     f(c);
   });
 }
@@ -144,7 +147,7 @@ void tknnDestroy(tknnEngine e) {
 }
 
 int tknnBuildIds(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t n, tknnBuildInfo *info, void *stream) {
-  return api("tknnBuild", e, [&](const Call &c) {
+  return api("tknnBuild", e, stream, [&](const Call &c) {
     c.need(d_xyz, "d_xyz");
     c.count(n, "n", 1);
     e->impl.build(d_xyz, d_ids, n, info, (hipStream_t)stream);
@@ -156,7 +159,7 @@ int tknnBuild(tknnEngine e, const float *d_xyz, int64_t n, tknnBuildInfo *info, 
 }
 
 int tknnSetHalo(tknnEngine e, const float *d_xyz, const int32_t *d_ids, int64_t m, void *stream) {
-  return api("tknnSetHalo", e, [&](const Call &c) {
+  return api("tknnSetHalo", e, stream, [&](const Call &c) {
     c.count(m, "m");
     if (m > 0) c.need(d_xyz, "d_xyz"), c.need(d_ids, "d_ids");
     c.built();
@@ -172,7 +175,7 @@ static void need_boxes(const Call &c, const float *d_boxes, const int32_t *d_box
 
 int tknnHaloSelect(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
                    int64_t *d_counts, const int64_t *d_offsets, float *d_rows, void *stream) {
-  return api("tknnHaloSelect", e, [&](const Call &c) {
+  return api("tknnHaloSelect", e, stream, [&](const Call &c) {
     need_boxes(c, d_boxes, d_box_peer, nboxes);
     c.require(d_rows || d_counts, "need d_counts (count pass) or d_offsets + d_rows (write pass)");
     if (d_rows) c.need(d_offsets, "d_offsets");
@@ -183,7 +186,7 @@ int tknnHaloSelect(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer
 
 int tknnHaloSelectFixed(tknnEngine e, const float *d_boxes, const int32_t *d_box_peer, int32_t nboxes, int32_t npeers,
                         const int64_t *d_caps, const int64_t *d_offsets, float *d_rows, int64_t *d_counts, void *stream) {
-  return api("tknnHaloSelectFixed", e, [&](const Call &c) {
+  return api("tknnHaloSelectFixed", e, stream, [&](const Call &c) {
     need_boxes(c, d_boxes, d_box_peer, nboxes);
     c.need(d_caps, "d_caps"), c.need(d_offsets, "d_offsets"), c.need(d_rows, "d_rows"), c.need(d_counts, "d_counts");
     c.built();
@@ -206,7 +209,7 @@ int tknnSolve(tknnEngine e, int k, float start_radius, int kernel, int max_round
 }
 
 int tknnSolveEx(tknnEngine e, const tknnSolveOptions *options, tknnSolveInfo *info, void *stream) {
-  return api("tknnSolve", e, [&](const Call &c) {
+  return api("tknnSolve", e, stream, [&](const Call &c) {
     const tknnSolveOptions &o = c.record(options);
     c.built();
     c.k_up_to(o.k, TKNN_MAX_K, TKNN_E_UNSUPPORTED);
@@ -234,7 +237,7 @@ int tknnSolveEx(tknnEngine e, const tknnSolveOptions *options, tknnSolveInfo *in
 
 int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_levels, int32_t *d_idx,
                     float *d_dist, int64_t *repaired, void *stream) {
-  return api("tknnRepairExact", e, [&](const Call &c) {
+  return api("tknnRepairExact", e, stream, [&](const Call &c) {
     c.need(d_levels, "d_levels"), c.need(d_idx, "d_idx"), c.need(d_dist, "d_dist");
     c.built();
     c.k_up_to(k, TKNN_MAX_K_REGISTERS, TKNN_E_ARG);  // (the repair pass keeps its lists in registers)
@@ -245,7 +248,7 @@ int tknnRepairExact(tknnEngine e, int k, float start_radius, const int32_t *d_le
 }
 
 int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info, void *stream) {
-  return api("tknnQuery", e, [&](const Call &c) {
+  return api("tknnQuery", e, stream, [&](const Call &c) {
     const tknnQueryOptions &o = c.record(options);
     if (o.m > 0) c.need(o.d_queries, "d_queries");
     c.built();
@@ -263,7 +266,7 @@ int tknnQuery(tknnEngine e, const tknnQueryOptions *options, tknnSolveInfo *info
 
 int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels, uint8_t *d_core, int32_t *d_counts,
                tknnDbscanInfo *info, void *stream) {
-  return api("tknnDbscan", e, [&](const Call &c) {
+  return api("tknnDbscan", e, stream, [&](const Call &c) {
     c.need(d_labels, "d_labels");
     c.built();
     c.positive(eps, "eps");
@@ -274,7 +277,7 @@ int tknnDbscan(tknnEngine e, float eps, int min_pts, int32_t *d_labels, uint8_t 
 
 int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32_t *d_labels, tknnDbscanInfo *info,
                      void *stream) {
-  return api("tknnDbscanAssign", e, [&](const Call &c) {
+  return api("tknnDbscanAssign", e, stream, [&](const Call &c) {
     c.need(d_labels, "d_labels"), c.need(d_core_label, "d_core_label");
     c.built();
     c.positive(eps, "eps");
@@ -283,7 +286,7 @@ int tknnDbscanAssign(tknnEngine e, float eps, const int32_t *d_core_label, int32
 }
 
 int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbscanInfo *info, void *stream) {
-  return api("tknnDbscanQuery", e, [&](const Call &c) {
+  return api("tknnDbscanQuery", e, stream, [&](const Call &c) {
     const tknnDbscanQueryOptions &o = c.record(options);
     c.need(o.d_core_label, "d_core_label"), c.need(o.d_labels, "d_labels");
     if (o.m > 0) c.need(o.d_queries, "d_queries");
@@ -296,7 +299,7 @@ int tknnDbscanQuery(tknnEngine e, const tknnDbscanQueryOptions *options, tknnDbs
 }
 
 int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusInfo *info, void *stream) {
-  return api("tknnRadiusQuery", e, [&](const Call &c) {
+  return api("tknnRadiusQuery", e, stream, [&](const Call &c) {
     const tknnRadiusOptions &o = c.record(options);
     c.need(o.d_offsets, "d_offsets");
     if (o.m > 0) c.need(o.d_queries, "d_queries");
@@ -316,7 +319,7 @@ int tknnRadiusQuery(tknnEngine e, const tknnRadiusOptions *options, tknnRadiusIn
 }
 
 int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusKnnInfo *info, void *stream) {
-  return api("tknnRadiusKnn", e, [&](const Call &c) {
+  return api("tknnRadiusKnn", e, stream, [&](const Call &c) {
     const tknnRadiusKnnOptions &o = c.record(options);
     c.need(o.d_idx, "d_idx");
     if (o.m > 0) c.need(o.d_queries, "d_queries");
@@ -331,7 +334,7 @@ int tknnRadiusKnn(tknnEngine e, const tknnRadiusKnnOptions *options, tknnRadiusK
 }
 
 int tknnKnn(tknnEngine e, const tknnKnnOptions *options, tknnKnnInfo *info, void *stream) {
-  return api("tknnKnn", e, [&](const Call &c) {
+  return api("tknnKnn", e, stream, [&](const Call &c) {
     const tknnKnnOptions &o = c.record(options);
     c.need(o.d_idx, "d_idx");
     if (!o.d_queries) {  // the set's own points
@@ -348,7 +351,7 @@ int tknnKnn(tknnEngine e, const tknnKnnOptions *options, tknnKnnInfo *info, void
 }
 
 int tknnPeriodicKnn(tknnEngine e, const tknnPeriodicKnnOptions *options, tknnPeriodicKnnInfo *info, void *stream) {
-  return api("tknnPeriodicKnn", e, [&](const Call &c) {
+  return api("tknnPeriodicKnn", e, stream, [&](const Call &c) {
     const tknnPeriodicKnnOptions &o = c.record(options);
     c.need(o.d_idx, "d_idx");
     if (!o.d_queries) {  // the set's own points
@@ -378,7 +381,7 @@ int tknnPeriodicKnn(tknnEngine e, const tknnPeriodicKnnOptions *options, tknnPer
 
 int tknnBuildBatched(tknnEngine e, const float *d_xyz, const int32_t *d_ids, const int32_t *d_batch, int32_t num_batches, int64_t n, tknnBuildInfo *info,
                      void *stream) {
-  return api("tknnBuildBatched", e, [&](const Call &c) {
+  return api("tknnBuildBatched", e, stream, [&](const Call &c) {
     c.need(d_xyz, "d_xyz"), c.need(d_batch, "d_batch");
     c.count(n, "n", 1);
     c.require(num_batches >= 1, "num_batches must be positive");
@@ -388,14 +391,14 @@ int tknnBuildBatched(tknnEngine e, const float *d_xyz, const int32_t *d_ids, con
 }
 
 int tknnBatchLayout(tknnEngine e, int32_t *num_batches, int32_t *key_bits, int32_t *d_starts, void *stream) {
-  return api("tknnBatchLayout", e, [&](const Call &c) {
+  return api("tknnBatchLayout", e, stream, [&](const Call &c) {
     c.batched();
     e->impl.batch_layout(num_batches, key_bits, d_starts, (hipStream_t)stream);
   });
 }
 
 int tknnBatchKnn(tknnEngine e, const tknnBatchKnnOptions *options, tknnBatchKnnInfo *info, void *stream) {
-  return api("tknnBatchKnn", e, [&](const Call &c) {
+  return api("tknnBatchKnn", e, stream, [&](const Call &c) {
     const tknnBatchKnnOptions &o = c.record(options);
     c.need(o.d_idx, "d_idx");
     if (!o.d_queries) {  // the set's own points
@@ -414,7 +417,7 @@ int tknnBatchKnn(tknnEngine e, const tknnBatchKnnOptions *options, tknnBatchKnnI
 }
 
 int tknnFps(tknnEngine e, const tknnFpsOptions *options, tknnFpsInfo *info, void *stream) {
-  return api("tknnFps", e, [&](const Call &c) {
+  return api("tknnFps", e, stream, [&](const Call &c) {
     const tknnFpsOptions &o = c.record(options);
     c.need(o.d_idx, "d_idx");
     if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
@@ -426,7 +429,7 @@ int tknnFps(tknnEngine e, const tknnFpsOptions *options, tknnFpsInfo *info, void
 }
 
 int tknnRadiusNms(tknnEngine e, const tknnRadiusNmsOptions *options, tknnRadiusNmsInfo *info, void *stream) {
-  return api("tknnRadiusNms", e, [&](const Call &c) {
+  return api("tknnRadiusNms", e, stream, [&](const Call &c) {
     const tknnRadiusNmsOptions &o = c.record(options);
     c.need(o.d_keep, "d_keep");
     if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
@@ -440,7 +443,7 @@ int tknnRadiusNms(tknnEngine e, const tknnRadiusNmsOptions *options, tknnRadiusN
 }
 
 int tknnRadiusReduce(tknnEngine e, const tknnRadiusReduceOptions *options, tknnRadiusReduceInfo *info, void *stream) {
-  return api("tknnRadiusReduce", e, [&](const Call &c) {
+  return api("tknnRadiusReduce", e, stream, [&](const Call &c) {
     const tknnRadiusReduceOptions &o = c.record(options);
     c.require(o.d_counts || o.d_wsum || o.d_out, "no output: give d_counts, d_wsum or d_out");
     if (!o.d_queries) c.require(o.m == e->impl.size(), "d_queries is NULL (the set's own points): m must equal n");
@@ -460,7 +463,7 @@ int tknnRadiusReduce(tknnEngine e, const tknnRadiusReduceOptions *options, tknnR
 }
 
 int tknnLocalPca(tknnEngine e, const tknnLocalPcaOptions *options, tknnLocalPcaInfo *info, void *stream) {
-  return api("tknnLocalPca", e, [&](const Call &c) {
+  return api("tknnLocalPca", e, stream, [&](const Call &c) {
     const tknnLocalPcaOptions &o = c.record(options);
     c.require(o.d_counts || o.d_centroid || o.d_cov || o.d_eigenvalues || o.d_eigenvectors || o.d_normals || o.d_curvature,
               "no output: give d_counts, d_centroid, d_cov, d_eigenvalues, d_eigenvectors, d_normals or d_curvature");
@@ -484,7 +487,7 @@ int tknnLocalPca(tknnEngine e, const tknnLocalPcaOptions *options, tknnLocalPcaI
 }
 
 int tknnEmst(tknnEngine e, const tknnEmstOptions *options, tknnEmstInfo *info, void *stream) {
-  const int rc = api("tknnEmst", e, [&](const Call &c) {
+  const int rc = api("tknnEmst", e, stream, [&](const Call &c) {
     const tknnEmstOptions &o = c.record(options);
     if (e->impl.built() && e->impl.size() > 1) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v");
     c.built();
@@ -503,7 +506,7 @@ static void need_forest(const Call &c, int64_t n, int64_t edges) {
 }
 
 int tknnLinkage(tknnEngine e, const tknnLinkageOptions *options, tknnLinkageInfo *info, void *stream) {
-  return api("tknnLinkage", e, [&](const Call &c) {
+  return api("tknnLinkage", e, stream, [&](const Call &c) {
     const tknnLinkageOptions &o = c.record(options);
     if (o.edges > 0) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v");
     c.require(o.d_parent || o.d_left || o.d_right || o.d_size, "need one of d_parent, d_left, d_right, d_size");
@@ -514,7 +517,7 @@ int tknnLinkage(tknnEngine e, const tknnLinkageOptions *options, tknnLinkageInfo
 }
 
 int tknnHdbscanLabels(tknnEngine e, const tknnHdbscanLabelsOptions *options, tknnHdbscanLabelsInfo *info, void *stream) {
-  return api("tknnHdbscanLabels", e, [&](const Call &c) {
+  return api("tknnHdbscanLabels", e, stream, [&](const Call &c) {
     const tknnHdbscanLabelsOptions &o = c.record(options);
     c.need(o.d_labels, "d_labels");
     if (o.edges > 0) c.need(o.d_u, "d_u"), c.need(o.d_v, "d_v"), c.need(o.d_w, "d_w");
@@ -526,7 +529,7 @@ int tknnHdbscanLabels(tknnEngine e, const tknnHdbscanLabelsOptions *options, tkn
 }
 
 int tknnHdbscan(tknnEngine e, const tknnHdbscanOptions *options, tknnHdbscanInfo *info, void *stream) {
-  return api("tknnHdbscan", e, [&](const Call &c) {
+  return api("tknnHdbscan", e, stream, [&](const Call &c) {
     const tknnHdbscanOptions &o = c.record(options);
     c.need(o.d_labels, "d_labels");
     c.built();
@@ -542,7 +545,7 @@ int tknnHdbscan(tknnEngine e, const tknnHdbscanOptions *options, tknnHdbscanInfo
 
 int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int max_rounds, int32_t *d_labels, uint8_t *d_core,
                    tknnDbscanAutoInfo *info, void *stream) {
-  const int rc = api("tknnDbscanAuto", e, [&](const Call &c) {
+  const int rc = api("tknnDbscanAuto", e, stream, [&](const Call &c) {
     c.need(d_labels, "d_labels");
     c.built();
     c.positive(eps0, "eps0");
@@ -556,7 +559,7 @@ int tknnDbscanAuto(tknnEngine e, float eps0, int min_pts, double max_noise, int 
 }
 
 int tknnDbscanNoise(tknnEngine e, float eps, int min_pts, uint8_t *d_noise, int64_t *noise_count, void *stream) {
-  return api("tknnDbscanNoise", e, [&](const Call &c) {
+  return api("tknnDbscanNoise", e, stream, [&](const Call &c) {
     c.need(d_noise, "d_noise");
     c.built();
     c.positive(eps, "eps");
@@ -567,7 +570,7 @@ int tknnDbscanNoise(tknnEngine e, float eps, int min_pts, uint8_t *d_noise, int6
 }
 
 int tknnSegmentMin(tknnEngine e, const int32_t *d_segment, const int64_t *d_value, int64_t n, int64_t *d_out, void *stream) {
-  return api("tknnSegmentMin", e, [&](const Call &c) {
+  return api("tknnSegmentMin", e, stream, [&](const Call &c) {
     c.require(n >= 0, "n must not be negative");
     if (n > 0) c.need(d_segment, "d_segment"), c.need(d_value, "d_value"), c.need(d_out, "d_out");
     owlmi::db_segment_min(d_segment, d_value, n, d_out, (hipStream_t)stream);
@@ -576,21 +579,21 @@ int tknnSegmentMin(tknnEngine e, const int32_t *d_segment, const int64_t *d_valu
 
 int tknnExportTree(tknnEngine e, void *nodes, int32_t *rope_node, int32_t *rope_leaf, int32_t *prim_id,
                    void *stream) {
-  return api("tknnExportTree", e, [&](const Call &c) {
+  return api("tknnExportTree", e, stream, [&](const Call &c) {
     c.built();
     e->impl.tree().download((LbvhNode *)nodes, rope_node, rope_leaf, prim_id, (hipStream_t)stream);
   });
 }
 
 int tknnExportTreeTables(tknnEngine e, int32_t *split_owner, int32_t *block_paths, void *stream) {
-  return api("tknnExportTreeTables", e, [&](const Call &c) {
+  return api("tknnExportTreeTables", e, stream, [&](const Call &c) {
     c.built();
     e->impl.tree().download_tables(split_owner, block_paths, (hipStream_t)stream);
   });
 }
 
 int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream) {
-  return api("tknnExportTreeEx", e, [&](const Call &c) {
+  return api("tknnExportTreeEx", e, stream, [&](const Call &c) {
     c.need(x, "the export record");
     c.require(x->which == 0 || x->which == 1, "which must be 0 (own tree) or 1 (halo tree)");
     c.require(!x->wide_boxes || x->wide_capacity >= 0, "wide_capacity must not be negative");
@@ -611,7 +614,16 @@ int tknnExportTreeEx(tknnEngine e, tknnTreeExport *x, void *stream) {
   });
 }
 
-// the debug entry points need no engine
+int tknnDebugPoison(tknnEngine e, unsigned what, int byte, size_t min_workspace_bytes, int64_t *poisoned_bytes, void *stream) {
+  return api("tknnDebugPoison", e, stream, [&](const Call &c) {
+    c.require((what & ~TKNN_POISON_ALL) == 0u, "what has a bit no part of the scratch has");
+    c.require(byte >= 0 && byte <= 255, "byte must be 0 .. 255");
+    const int64_t filled = e->impl.debug_poison(what, byte, min_workspace_bytes, (hipStream_t)stream);
+    if (poisoned_bytes) *poisoned_bytes = filled;
+  });
+}
+
+// the debug entry points below need no engine
 
 int tknnDebugBoxTree(const float *d_boxes, int64_t n, const float *d_boxes_refit, int mode, void *nodes, int32_t *rope_node,
                      int32_t *rope_leaf, int32_t *prim_id, float *sorted_boxes, void *stream) {

@@ -287,7 +287,7 @@ Engine::Engine() {
   OWLMI_HIP(hipEventCreate(&ev_h_));
   OWLMI_HIP(hipMalloc((void **)&counters_, kCounterWords * sizeof(unsigned long long)));  // (the team kernel's per-XCD packet counters sit in the stripes' words, 32 words apart: trueknn_team.hip) [32]: tie rows
   OWLMI_HIP(hipMalloc((void **)&tie_list_, kTieListCap * sizeof(int32_t)));
-  OWLMI_HIP(hipHostMalloc((void **)&h_counters_, (kHostStripes + std::max(kDbStripes * kDbStripeWords, kStatStripes * kStatStride)) * sizeof(unsigned long long)));
+  OWLMI_HIP(hipHostMalloc((void **)&h_counters_, kHostCounterWords * sizeof(unsigned long long)));
   if (const char *e = getenv("TKNN_WAVE_FORCE_REDO")) wave_force_redo_ = atoi(e) != 0;
   if (const char *e = getenv("TKNN_LEAF_MAX")) {
     int v = atoi(e);
@@ -343,6 +343,47 @@ int32_t *Engine::slot_list(int64_t n) {
     slot_list_cap_ = n;
   }
   return slot_list_;
+}
+
+void Engine::join_side(hipStream_t s) {
+  if (!db_side_pending_) return;
+  OWLMI_HIP(hipStreamWaitEvent(s, ev_side_b_, 0));
+  db_side_pending_ = false;
+}
+
+// What is filled is scratch and nothing else: no call may read a word of it that it has not written itself ("State that
+// carries from one call to the next").  The trees, batch_starts_, boundary_ and the host's flags carry meaning and are left alone.
+int64_t Engine::debug_poison(unsigned what, int byte, size_t min_workspace_bytes, hipStream_t s) {
+  join_side(s);
+  int64_t filled = 0;
+  const auto fill = [&](void *p, size_t bytes) {
+    if (!p || bytes == 0) return;
+    OWLMI_HIP(hipMemsetAsync(p, byte, bytes, s));
+    filled += (int64_t)bytes;
+  };
+  if (what & TKNN_POISON_WORKSPACE) {
+    if (min_workspace_bytes > 0) workspace(min_workspace_bytes);
+    fill(wave_ws_, wave_ws_bytes_);
+  }
+  if (what & TKNN_POISON_COUNTERS) fill(counters_, kCounterWords * sizeof(unsigned long long));
+  if (what & TKNN_POISON_LISTS) {
+    fill(slot_list_, slot_list_ ? ((size_t)slot_list_cap_ + 1) * sizeof(int32_t) : 0);
+    fill(tie_list_, kTieListCap * sizeof(int32_t));
+    fill(halo_mask_, halo_mask_ ? halo_mask_bytes(halo_mask_cap_) : 0);
+  }
+  if (what & TKNN_POISON_SOLVE) {
+    const size_t cap = (size_t)state_cap_;
+    fill(done_, cap);
+    fill(isect_sorted_, cap * sizeof(int64_t));
+    fill(next_level_, cap * sizeof(int32_t));
+    fill(tie_, (cap + 3) & ~(size_t)3);
+  }
+  OWLMI_HIP(hipStreamSynchronize(s));
+  if (what & TKNN_POISON_COUNTERS) {
+    std::memset(h_counters_, byte, kHostCounterWords * sizeof(unsigned long long));
+    filled += (int64_t)(kHostCounterWords * sizeof(unsigned long long));
+  }
+  return filled;
 }
 
 void Engine::set_halo(const float *d_xyz, const int32_t *d_ids, int64_t m, hipStream_t s) {

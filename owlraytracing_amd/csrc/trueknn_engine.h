@@ -10,6 +10,7 @@
 #include "lbvh.h"
 #include "owlknn.h"
 #include "owlknn_batch.h"
+#include "owlknn_debug.h"
 #include "owlknn_emst.h"
 #include "owlknn_fps.h"
 #include "owlknn_hdbscan.h"
@@ -187,6 +188,11 @@ class Engine {
   // radius row, a kNN row or both -- of m points that are not in the tree or (d_queries null) of the tree's own points, no lists
   // written (tknnLocalPca); m > 0, the tree a point tree
   void local_pca(const tknnLocalPcaOptions &o, tknnLocalPcaInfo *info, hipStream_t s);
+  // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
+  // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
+  void join_side(hipStream_t s);
+  // test hook (tknnDebugPoison, include/owlknn_debug.h): fills the scratch named in `what` with `byte`; returns the bytes filled
+  int64_t debug_poison(unsigned what, int byte, size_t min_workspace_bytes, hipStream_t s);
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }
@@ -273,6 +279,7 @@ class Engine {
   int64_t slot_list_cap_ = 0;
   unsigned long long *halo_mask_ = nullptr;  // per leaf block: peers it may have points for (+ 64 cursors)
   int64_t halo_mask_cap_ = 0;
+  static size_t halo_mask_bytes(int64_t blocks);  // halo_select.hip: what halo_mask_ takes for that many leaf blocks
   hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr, ev_c_ = nullptr, ev_d_ = nullptr, ev_e_ = nullptr, ev_f_ = nullptr;
   // dbscan(): the walks of the points that are not core run beside the group unions on a stream of their own
   hipStream_t db_side_ = nullptr;
