@@ -35,3 +35,11 @@ def local_pca(points, queries, radius=None, k=None, **kw):
     from .trueknn import local_pca as _local_pca
 
     return _local_pca(points, queries, radius=radius, k=k, **kw)
+
+
+def icp(target, source, max_dist, **kw):
+    """Rigid registration of ``source`` to ``target`` by iterated closest points, point-to-point or point-to-plane, the loop and
+    its fp64 sums inside the library (trueknn.icp; loads the library)."""
+    from .trueknn import icp as _icp
+
+    return _icp(target, source, max_dist, **kw)

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_icp.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -483,6 +483,34 @@ int tknnLocalPca(tknnEngine e, const tknnLocalPcaOptions *options, tknnLocalPcaI
     if (o.k > TKNN_MAX_K_REGISTERS) c.refuse(TKNN_E_UNSUPPORTED, "k out of range (1 .. " + std::to_string(TKNN_MAX_K_REGISTERS) + ")");
     zero(info);
     if (o.m > 0) e->impl.local_pca(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnIcp(tknnEngine e, const tknnIcpOptions *options, tknnIcpInfo *info, void *stream) {
+  return api("tknnIcp", e, stream, [&](const Call &c) {
+    const tknnIcpOptions &o = c.record(options);
+    c.need(info, "info");
+    if (o.m > 0) c.need(o.d_source, "d_source");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    if (e->impl.ids_given()) c.refuse(TKNN_E_UNSUPPORTED, "the tree was built with ids: a partner is fetched by the caller's row, build with tknnBuild");
+    c.positive(o.max_dist, "max_dist");
+    c.require(o.method == TKNN_ICP_POINT_TO_POINT || o.method == TKNN_ICP_POINT_TO_PLANE, "method must be TKNN_ICP_POINT_TO_POINT or TKNN_ICP_POINT_TO_PLANE");
+    c.require(o.robust >= TKNN_ICP_L2 && o.robust <= TKNN_ICP_TUKEY, "robust must be one of TKNN_ICP_L2, TKNN_ICP_HUBER, TKNN_ICP_TUKEY");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    if (o.method == TKNN_ICP_POINT_TO_PLANE) c.need(o.d_target_normals, "d_target_normals (TKNN_ICP_POINT_TO_PLANE)");
+    if (o.robust != TKNN_ICP_L2) c.positive(o.robust_scale, "robust_scale (TKNN_ICP_HUBER, TKNN_ICP_TUKEY)");
+    c.require(o.max_iterations >= 0, "max_iterations must not be negative (0: evaluate at init)");
+    c.require(o.rel_fitness >= 0.0 && std::isfinite(o.rel_fitness), "rel_fitness must be finite and not negative");
+    c.require(o.rel_rmse >= 0.0 && std::isfinite(o.rel_rmse), "rel_rmse must be finite and not negative");
+    if (o.init)
+      for (int i = 0; i < 16; i++) c.require(std::isfinite(o.init[i]), "init has an entry that is not finite");
+    c.count(o.m, "m");
+    zero(info);
+    if (o.m > 0) {
+      e->impl.icp(o, info, (hipStream_t)stream);
+    } else {
+      for (int i = 0; i < 16; i++) info->transform[i] = o.init ? o.init[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    }
   });
 }
 

@@ -14,6 +14,7 @@
 #include "owlknn_emst.h"
 #include "owlknn_fps.h"
 #include "owlknn_hdbscan.h"
+#include "owlknn_icp.h"
 #include "owlknn_knn.h"
 #include "owlknn_nms.h"
 #include "owlknn_pca.h"
@@ -188,6 +189,10 @@ class Engine {
   // radius row, a kNN row or both -- of m points that are not in the tree or (d_queries null) of the tree's own points, no lists
   // written (tknnLocalPca); m > 0, the tree a point tree
   void local_pca(const tknnLocalPcaOptions &o, tknnLocalPcaInfo *info, hipStream_t s);
+  // icp.hip: rigid registration of m source points to the tree's points by iterated closest points -- tknnKnn's search at k = 1
+  // clipped to max_dist, fp64 moments of the pairs, the step solved on the host (icp_solve.h) -- with no list leaving the call
+  // (tknnIcp); m > 0, the tree a point tree without ids
+  void icp(const tknnIcpOptions &o, tknnIcpInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);
@@ -196,6 +201,7 @@ class Engine {
   bool batched() const { return bvh_.built() && num_batches_ > 0; }
   int32_t num_clouds() const { return batched() ? num_batches_ : 1; }  // the clouds tknnFps samples
   bool has_halo() const { return halo_n_ > 0; }
+  bool ids_given() const { return ids_given_; }  // the tree names its points by the caller's ids, not by row
   bool built() const { return bvh_.built(); }
   int device() const { return device_; }
   int64_t size() const { return bvh_.size(); }

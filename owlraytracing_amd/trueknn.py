@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _knn_lib, _lib, _nms_lib, _pca_lib, _periodic_lib, _reduce_lib
+from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _nms_lib, _pca_lib, _periodic_lib, _reduce_lib
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -1052,6 +1052,66 @@ class TrueKNN:
         return self.local_pca(radius=radius, k=k, queries=queries, skip_self=skip_self, viewpoint=viewpoint, min_points=min_points,
                               want=("normals", "curvature", "counts"))
 
+    def icp(self, source, max_dist, init=None, method="point_to_point", target_normals=None, max_iterations=30, rel_fitness=1e-6,
+            rel_rmse=1e-6, robust=None, robust_scale=None, want_correspondences=False, want_aligned=False):
+        """Rigid registration of ``source`` to the built points by iterated closest points, the loop inside the library (tknnIcp):
+        each iteration applies the transform to the source in fp32, finds every point's nearest built point within ``max_dist``
+        (``radius_knn`` at k = 1), sums the pairs' moments in fp64 and solves one step -- "point_to_point" (Kabsch / Horn) or
+        "point_to_plane" (Gauss-Newton on (s' - p) . n, Open3D's angles), with ``robust`` None / "l2", "huber" or "tukey" at
+        ``robust_scale``.  ``source``: numpy (m,2|3) or a contiguous float32 tensor (m,3) on the engine's device.  ``init``: a
+        4 x 4 transform (anything np.asarray takes), None: the identity.  ``target_normals``: (n,3) float32 by the caller's row,
+        numpy or a tensor on the engine's device (``normals(k=16)["normals"]``); point_to_plane needs them.  The loop stops when
+        fitness and inlier_rmse both change by less than ``rel_fitness`` / ``rel_rmse``, after ``max_iterations`` steps, or at a
+        degenerate system.  The tree must have been built without ids.
+        Returns dict(transform (4,4) float64 CPU tensor, fitness, inlier_rmse, correspondences, iterations, searches, converged,
+        degenerate, skipped_pairs, the work counters and times; corr (m,) int32 and corr_dist (m,) float32 of the last search
+        [``want_correspondences``]; aligned (m,3) float32 [``want_aligned``])."""
+        torch = self._torch
+        if method not in _icp_lib.METHODS:
+            raise ValueError("icp: method must be one of %s" % ", ".join(sorted(_icp_lib.METHODS)))
+        if robust not in _icp_lib.ROBUST:
+            raise ValueError("icp: robust must be None, 'l2', 'huber' or 'tukey'")
+        if _icp_lib.ROBUST[robust] and robust_scale is None:
+            raise ValueError("icp: robust=%r needs a robust_scale" % robust)
+        if method == "point_to_plane" and target_normals is None:
+            raise ValueError("icp: point_to_plane needs target_normals")
+        source = self._queries(source, "icp")
+        m = int(source.shape[0])
+        t0 = None
+        if init is not None:
+            t0 = np.ascontiguousarray(init.cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+            if t0.shape != (4, 4):
+                raise ValueError("icp: init must be a 4 x 4 transform, got %s" % (t0.shape,))
+        with torch.cuda.device(self.device):
+            if target_normals is not None:
+                if isinstance(target_normals, np.ndarray):
+                    target_normals = torch.from_numpy(np.ascontiguousarray(target_normals, dtype=np.float32)).to(self.device)
+                self._written_in_place("icp", "target_normals", target_normals, (self.n, 3), torch.float32)
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            corr = torch.empty((m,), dtype=torch.int32, device=self.device) if want_correspondences else None
+            corr_dist = torch.empty((m,), dtype=torch.float32, device=self.device) if want_correspondences else None
+            aligned = torch.empty((m, 3), dtype=torch.float32, device=self.device) if want_aligned else None
+            opt = _icp_lib.IcpOptions()
+            opt.m, opt.d_source, opt.d_target_normals = m, _address(source, spare), _address(target_normals, spare)
+            opt.init = None if t0 is None else t0.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+            opt.max_dist, opt.robust_scale = float(max_dist), 0.0 if robust_scale is None else float(robust_scale)
+            opt.method, opt.robust, opt.max_iterations = _icp_lib.METHODS[method], _icp_lib.ROBUST[robust], int(max_iterations)
+            opt.rel_fitness, opt.rel_rmse = float(rel_fitness), float(rel_rmse)
+            opt.d_corr, opt.d_corr_dist, opt.d_aligned = _address(corr, spare), _address(corr_dist, spare), _address(aligned, spare)
+            info = _icp_lib.IcpInfo()
+            _lib.check(_icp_lib.load().tknnIcp(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        res = info.as_dict()
+        res["transform"] = torch.tensor(list(info.transform), dtype=torch.float64).reshape(4, 4)
+        if want_correspondences:
+            res["corr"], res["corr_dist"] = corr, corr_dist
+        if want_aligned:
+            res["aligned"] = aligned
+        return res
+
+    def evaluate_registration(self, source, max_dist, init=None):
+        """``icp`` with no step taken: fitness, inlier_rmse and correspondences of ``source`` under ``init`` (None: as it is)."""
+        return self.icp(source, max_dist, init=init, max_iterations=0)
+
     def _is_batched(self):
         """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
         nb = ctypes.c_int32(0)
@@ -1329,6 +1389,11 @@ def local_pca(points, queries, radius=None, k=None, ids=None, batch=None, **kw):
         return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
     finally:
         eng.close()
+
+
+def icp(target, source, max_dist, **kw):
+    """One-shot helper: build over ``target`` and register ``source`` to it (TrueKNN.icp), results as numpy arrays."""
+    return _one_shot(target, lambda eng: eng.icp(source, max_dist, **kw))
 
 
 def dbscan_query(points, queries, eps, min_pts):
