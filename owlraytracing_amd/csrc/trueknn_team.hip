@@ -36,6 +36,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace owlmi {
 
@@ -101,6 +102,7 @@ constexpr int kTeamStack = 192;     // wide-pyramid stack entries per wave
 constexpr int kQrecStride = 6;      // floats per LDS query record (layout below)
 constexpr int kScanBudget = 16384;  // leaf blocks one packet-level may test against its queries before it is handed over
 constexpr int kMaxStep = 2;          // radius levels one gather may serve (the count slots and the inner-box test assume <= 2)
+constexpr int kCountFlatGroups = 3;  // groups of four blocks a COUNT round may have in flight at once (team_pass's flat path)
 // LDS per wave: query records | block list | per-query block lists | counts, query list / stack.
 // The pyramid stack is live only during the gather, the counts and the query list only during the
 // passes, so they share one region.  Every KB counts: LDS, not registers, limits residency.
@@ -379,47 +381,82 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
       tau2 = knn_gate_from_worst(kth_dist());  // k > 16: the second register is still empty, the gate stays open
     };
     TP_LAP(0);
-    t_point4 b0, b1, b2, b3;
-    {
-      // issued in ring order (the scheduler would reorder four independent loads, and the loop's
-      // s_waitcnt vmcnt(N) is the minimum over the orders it can be entered with)
-      const t_int4 g = my_groups[0];
-      b0 = fetch(g.x);
-      __builtin_amdgcn_sched_barrier(0);
-      b1 = fetch(g.y);
-      __builtin_amdgcn_sched_barrier(0);
-      b2 = fetch(g.z);
-      __builtin_amdgcn_sched_barrier(0);
-      b3 = fetch(g.w);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    for (int it = 0; it < steps; it += 4) {
-      const t_int4 g = my_groups[(it >> 2) + 1];  // entries it+4 .. it+7
-      if (SELECT && it == 0) {
-        // the query's own block meets an empty list.  k <= 16: its candidates simply are the first into the team's
-        // buffer, sorted by the first merge; larger k: sorted on the spot (sort_first), the other blocks insert one by one
-        if (NREG == 1 && TKNN_SORT_FIRST == 0)
-          process(unpack(b0), true);
-        else
-          sort_first(unpack(b0));
-      } else {
-        process(unpack(b0));
+    // A COUNT round of at most a.count_flat_max blocks (its longest list; 73 % of the benchmark's rounds have at most 8, 99 % at
+    // most 12) is no loop at all: the loads of ALL its whole groups are issued, then the blocks are tested in order.  A group's
+    // test is 60 to 90 instructions, far less than one trip to the L2, and the ring below keeps one group in flight ahead: a round
+    // of two or three groups waits two or three memory latencies one after the other where this path waits one.  Straight-line
+    // code per number of groups -- no back edge to carry buffers over, every s_waitcnt counts exactly, no group past the list's
+    // end is loaded -- and the pass has the registers: no list, no keys, no merge.  Whole 16-byte points as in the ring: loads
+    // of the three words the count reads measured the same mean and three times the spread (profiles/count_flat_ab.json).
+    if (!SELECT && steps <= a.count_flat_max) {
+      auto flat = [&](auto groups_c) {
+        constexpr int kBlocks = 4 * decltype(groups_c)::value;
+        LbvhPoint c[kBlocks];  // (indices are compile-time: registers)
+#pragma unroll
+        for (int j = 0; j < kBlocks; j += 4) {
+          const t_int4 g = my_groups[j >> 2];
+          c[j + 0] = load_block_point<HALO>(own_pts, halo_pts, g.x, own_base, lane_bytes);
+          c[j + 1] = load_block_point<HALO>(own_pts, halo_pts, g.y, own_base, lane_bytes);
+          c[j + 2] = load_block_point<HALO>(own_pts, halo_pts, g.z, own_base, lane_bytes);
+          c[j + 3] = load_block_point<HALO>(own_pts, halo_pts, g.w, own_base, lane_bytes);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (every load before the first test)
+#pragma unroll
+        for (int j = 0; j < kBlocks; j++) {
+          process(c[j]);
+          if (j == 3) TP_LAP(1);
+        }
+        if (kBlocks > 4) TP_LAP(2);
+      };
+      if (steps > 8)
+        flat(std::integral_constant<int, 3>{});
+      else if (steps > 4)
+        flat(std::integral_constant<int, 2>{});
+      else if (steps > 0)
+        flat(std::integral_constant<int, 1>{});
+    } else {
+      t_point4 b0, b1, b2, b3;
+      {
+        // issued in ring order (the scheduler would reorder four independent loads, and the loop's
+        // s_waitcnt vmcnt(N) is the minimum over the orders it can be entered with)
+        const t_int4 g = my_groups[0];
+        b0 = fetch(g.x);
+        __builtin_amdgcn_sched_barrier(0);
+        b1 = fetch(g.y);
+        __builtin_amdgcn_sched_barrier(0);
+        b2 = fetch(g.z);
+        __builtin_amdgcn_sched_barrier(0);
+        b3 = fetch(g.w);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      b0 = fetch(g.x);
-      process(unpack(b1));
-      b1 = fetch(g.y);
-      process(unpack(b2));
-      b2 = fetch(g.z);
-      process(unpack(b3));
-      b3 = fetch(g.w);
-      // a tighter gate for the next group as soon as a handful of candidates wait (the first groups, whose
-      // blocks lie next to the query, bring most of them)
-      if (SELECT && dirty && __ballot(fill_n >= (uint32_t)TKNN_MERGE_AT) != 0ull) {
-        if (TKNN_DIAG_BUILD && (a.diag & 16) && lane == 0) atomicAdd(&a.counters[27], 1ull);
-        merge_buffer();
+      for (int it = 0; it < steps; it += 4) {
+        const t_int4 g = my_groups[(it >> 2) + 1];  // entries it+4 .. it+7
+        if (SELECT && it == 0) {
+          // the query's own block meets an empty list.  k <= 16: its candidates simply are the first into the team's
+          // buffer, sorted by the first merge; larger k: sorted on the spot (sort_first), the other blocks insert one by one
+          if (NREG == 1 && TKNN_SORT_FIRST == 0)
+            process(unpack(b0), true);
+          else
+            sort_first(unpack(b0));
+        } else {
+          process(unpack(b0));
+        }
+        b0 = fetch(g.x);
+        process(unpack(b1));
+        b1 = fetch(g.y);
+        process(unpack(b2));
+        b2 = fetch(g.z);
+        process(unpack(b3));
+        b3 = fetch(g.w);
+        // a tighter gate for the next group as soon as a handful of candidates wait (the first groups, whose
+        // blocks lie next to the query, bring most of them)
+        if (SELECT && dirty && __ballot(fill_n >= (uint32_t)TKNN_MERGE_AT) != 0ull) {
+          if (TKNN_DIAG_BUILD && (a.diag & 16) && lane == 0) atomicAdd(&a.counters[27], 1ull);
+          merge_buffer();
+        }
+        TP_LAP(it == 0 ? 1 : 2);
       }
-      TP_LAP(it == 0 ? 1 : 2);
-    }
+    }  // the ring
     if (SELECT && dirty) {
       if (TKNN_DIAG_BUILD && (a.diag & 16) && lane == 0) atomicAdd(&a.counters[27], 1ull);
       merge_buffer();
@@ -721,14 +758,47 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       };
       // the largest per-axis gap between the child box in lane `src` and MY query point (<= 0: I am inside): the child is
       // needed at radius R iff gap <= R (+ the margin: reach_*).  One distance serves the walk's radius and the step's.
-      auto gap_to_me = [&](int src) -> float {
+      struct ChildBox {
+        float2 w0, w1, w2;
+      };
+      auto child_box = [&](int src) -> ChildBox {
         // (src is wave-uniform: its byte offset is a scalar product -- left to itself the compiler folds the product and
         // the address add into one v_mad_u64_u32, a quarter-rate instruction, for every block tested)
         int boff;
         asm("s_mul_i32 %0, %1, 24" : "=s"(boff) : "s"(src));
         const float2 *b = (const float2 *)((const char *)node_boxes + boff);
-        const float2 b0 = b[0], b1 = b[1], b2 = b[2];
-        return separation(b0.x, b0.y, b1.x, b1.y, b2.x, b2.y, q.x, q.y, q.z, q.x, q.y, q.z);
+        return ChildBox{b[0], b[1], b[2]};
+      };
+      auto gap_to_me = [&](const ChildBox &c) -> float {
+        return separation(c.w0.x, c.w0.y, c.w1.x, c.w1.y, c.w2.x, c.w2.y, q.x, q.y, q.z, q.x, q.y, q.z);
+      };
+      // The children named by `mask`, from the highest lane down or from the lowest up, one after the other through
+      // test(child, its box) -- false ends the walk -- with the NEXT child's box read from LDS before the child in hand is
+      // tested: three broadcast reads, their wait, a dozen vector instructions, a ballot, a branch and the list stores are
+      // one dependent chain per child, some seventy per packet, and the lists are bytes, so the compiler may not lift the
+      // next child's reads over this child's stores by itself.  Two boxes take turns (no copy at the back edge: it would
+      // wait for the read it copies); after the last child its own box is read once more -- a read that is not made
+      // would zero the wait count of the one before it where the two ways meet.
+      auto for_children_ahead = [&](unsigned long long mask, bool top_down, auto test) {
+        auto take = [&](int last) -> int {
+          if (!mask) return last;
+          const int src = top_down ? 63 - __builtin_clzll(mask) : __ffsll((long long)mask) - 1;
+          mask &= ~(1ull << src);
+          return src;
+        };
+        if (!mask) return;
+        int s0 = take(0), s1;
+        ChildBox c0 = child_box(s0), c1;
+        for (;;) {
+          bool more = mask != 0ull;
+          s1 = take(s0);
+          c1 = child_box(s1);
+          if (!test(s0, c0) || !more) break;
+          more = mask != 0ull;
+          s0 = take(s1);
+          c0 = child_box(s0);
+          if (!test(s1, c1) || !more) break;
+        }
       };
 
       PHASE_END(0);
@@ -780,15 +850,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
               // its 64 blocks from being tested one by one where only the group box, not a query,
               // overlapped.  Nodes are popped in descending curve order and taken here from the
               // highest lane down, so filling the list downwards keeps it ascending in memory.
-              unsigned long long rest = om;
-              if (rest) stash_boxes(bx);
-              while (rest) {
-                const int src = 63 - __builtin_clzll(rest);
-                rest &= ~(1ull << src);
-                if (__ballot(gap_to_me(src) <= reach_walk) == 0ull) continue;
+              if (om) stash_boxes(bx);
+              for_children_ahead(om, /*top_down=*/true, [&](int src, const ChildBox &box) -> bool {
+                if (__ballot(gap_to_me(box) <= reach_walk) == 0ull) return true;
                 if (lane == 0) stack[kTeamStack - 1 - nleaf] = (lvl << 26) | (first_child + src);
                 nleaf++;
-              }
+                return true;
+              });
             }
             t_wave_sync();
             continue;
@@ -822,16 +890,14 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
             }
             // leaf blocks: which of my 64 queries need block c?  (lanes = queries, box from LDS)
             if (om) stash_boxes(bx);
-            while (om) {
-              const int src = __ffsll((long long)om) - 1;
-              om &= om - 1;
-              const float gap = gap_to_me(src);
+            for_children_ahead(om, /*top_down=*/false, [&](int src, const ChildBox &box) -> bool {
+              const float gap = gap_to_me(box);
               bool need = gap <= reach_walk;
               if (TKNN_DIAG_BUILD && (a.diag & 8)) need = false;
-              if (__ballot(need) == 0ull) continue;
+              if (__ballot(need) == 0ull) return true;
               if (nb >= kMaxBlocks) {
                 too_big = true;  // more blocks than a byte slot can name
-                break;
+                return false;
               }
               const int32_t block = first_child + src;
               blk[nb] = (int32_t)((uint32_t)block | ((uint32_t)tree << 31));  // (every lane stores the same word: no exec mask to set up)
@@ -848,7 +914,8 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
                 cur += inner ? 1 : 0x10000;
               }
               nb++;
-            }
+              return true;
+            });
           }
           nleaf = 0;
           t_wave_sync();
@@ -1153,6 +1220,9 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     if (const char *e = getenv("TKNN_TEAM_EXT")) a.first_ext = atoi(e) > 0 ? a.first_ext : -1;  // measurements: 0 = no extended gathers at all
     a.merge_ext = 1;
     if (const char *e = getenv("TKNN_TEAM_MERGE")) a.merge_ext = atoi(e) > 0 ? 1 : 0;  // measurements and tests: 0 = the extension level in a turn of its own
+    // COUNT rounds of up to so many blocks take the pass's flat path; measurements and tests: 0 = the ring for every round
+    a.count_flat_max = 4 * kCountFlatGroups;
+    if (const char *e = getenv("TKNN_TEAM_COUNT_FLAT")) a.count_flat_max = std::max(0, std::min(atoi(e), 4 * kCountFlatGroups));
   }
   {
     // axes along which the built points differ at all (2-D inputs carry z = 0, hostCode.cpp:115-118);
