@@ -43,3 +43,19 @@ def icp(target, source, max_dist, **kw):
     from .trueknn import icp as _icp
 
     return _icp(target, source, max_dist, **kw)
+
+
+def mean_shift(points, bandwidth, seeds=None, **kw):
+    """Mean-shift clustering, sklearn's ``MeanShift``: the trajectories on the GPU inside the library, modes merged within a radius,
+    every point labelled by its nearest centre (trueknn.mean_shift; loads the library)."""
+    from .trueknn import mean_shift as _mean_shift
+
+    return _mean_shift(points, bandwidth, seeds=seeds, **kw)
+
+
+def bin_seeds(points, bin_size, min_bin_freq=1):
+    """sklearn's ``get_bin_seeds`` on the device: the grid cells of ``bin_size`` holding at least ``min_bin_freq`` points, as seeds
+    (trueknn.bin_seeds)."""
+    from .trueknn import bin_seeds as _bin_seeds
+
+    return _bin_seeds(points, bin_size, min_bin_freq)

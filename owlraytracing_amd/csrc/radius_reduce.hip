@@ -20,6 +20,7 @@
 #include "owlknn_reduce.h"
 #include "query_order.h"
 #include "radius_walk.h"
+#include "radius_weights.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,32 +59,6 @@ struct ReduceArgs {
   int32_t *redo;             // m: positions left to the lane kernel
   unsigned long long *ws;    // kRadWords counters
 };
-
-// ---- the weights ---------------------------------------------------------------------------------------------------------------------
-// of a point that passed the predicate: d2 = knn_dist2, d = knn_sqrt(d2), every operation rounded on its own
-template <int WEIGHT>
-__device__ __forceinline__ float rd_weight(float d2, float d, float coef) {
-#pragma clang fp contract(off)
-  if constexpr (WEIGHT == TKNN_W_GAUSS) {
-    return expf(d2 * coef);
-  } else if constexpr (WEIGHT == TKNN_W_EPANECHNIKOV) {
-    return fmaxf(0.f, 1.f - d2 * coef);
-  } else if constexpr (WEIGHT == TKNN_W_CUBIC_SPLINE) {
-    const float s = d * coef, s2 = s * s, t = 2.f - s;
-    const float inner = (1.f - 1.5f * s2) + 0.75f * (s2 * s), outer = fmaxf(0.f, 0.25f * ((t * t) * t));
-    return s <= 1.f ? inner : outer;
-  } else {
-    return 1.f;
-  }
-}
-__device__ __forceinline__ float rd_weight_of(int weight, float d2, float d, float coef) {
-  switch (weight) {
-    case TKNN_W_GAUSS: return rd_weight<TKNN_W_GAUSS>(d2, d, coef);
-    case TKNN_W_EPANECHNIKOV: return rd_weight<TKNN_W_EPANECHNIKOV>(d2, d, coef);
-    case TKNN_W_CUBIC_SPLINE: return rd_weight<TKNN_W_CUBIC_SPLINE>(d2, d, coef);
-    default: return 1.f;
-  }
-}
 
 // A neighbour's share: w into wacc, w * v_c into acc.  Only called for a point that passed the predicate.
 template <int NC, bool ONE>

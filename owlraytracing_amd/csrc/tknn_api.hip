@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_icp.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -511,6 +511,27 @@ int tknnIcp(tknnEngine e, const tknnIcpOptions *options, tknnIcpInfo *info, void
     } else {
       for (int i = 0; i < 16; i++) info->transform[i] = o.init ? o.init[i] : (i % 5 == 0 ? 1.0 : 0.0);
     }
+  });
+}
+
+int tknnMeanShift(tknnEngine e, const tknnMeanShiftOptions *options, tknnMeanShiftInfo *info, void *stream) {
+  return api("tknnMeanShift", e, stream, [&](const Call &c) {
+    const tknnMeanShiftOptions &o = c.record(options);
+    c.need(info, "info");
+    c.require(o.d_modes || o.d_counts || o.d_wsum || o.d_shift || o.d_iterations || o.d_status,
+              "no output: give d_modes, d_counts, d_wsum, d_shift, d_iterations or d_status");
+    if (!o.d_seeds) c.require(o.m == e->impl.size(), "d_seeds is NULL (the set's own points): m must equal n");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.positive(o.radius, "radius");
+    c.require(o.weight == TKNN_W_ONE || o.weight == TKNN_W_GAUSS || o.weight == TKNN_W_EPANECHNIKOV,
+              "weight must be one of TKNN_W_ONE, TKNN_W_GAUSS, TKNN_W_EPANECHNIKOV (TKNN_W_CUBIC_SPLINE is no mean-shift kernel)");
+    if (o.weight == TKNN_W_GAUSS) c.positive(o.bandwidth, "bandwidth (TKNN_W_GAUSS)");
+    c.require(o.tol >= 0.f && std::isfinite(o.tol), "tol must be finite and not negative");
+    c.require(o.max_iterations >= 1, "max_iterations must be at least 1");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    c.count(o.m, "m");
+    zero(info);
+    if (o.m > 0) e->impl.mean_shift(o, info, (hipStream_t)stream);
   });
 }
 

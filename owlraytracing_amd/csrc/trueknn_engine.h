@@ -16,6 +16,7 @@
 #include "owlknn_hdbscan.h"
 #include "owlknn_icp.h"
 #include "owlknn_knn.h"
+#include "owlknn_meanshift.h"
 #include "owlknn_nms.h"
 #include "owlknn_pca.h"
 #include "owlknn_periodic.h"
@@ -193,6 +194,10 @@ class Engine {
   // clipped to max_dist, fp64 moments of the pairs, the step solved on the host (icp_solve.h) -- with no list leaving the call
   // (tknnIcp); m > 0, the tree a point tree without ids
   void icp(const tknnIcpOptions &o, tknnIcpInfo *info, hipStream_t s);
+  // mean_shift.hip: every seed -- m points that are not in the tree, or (d_seeds null) the tree's own points -- moved to the
+  // kernel-weighted mean of the points within a radius of it until it stops, the loop and its shrinking work list on the device
+  // (tknnMeanShift); m > 0, the tree a point tree
+  void mean_shift(const tknnMeanShiftOptions &o, tknnMeanShiftInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

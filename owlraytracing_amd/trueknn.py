@@ -9,7 +9,8 @@ import ctypes
 
 import numpy as np
 
-from . import _batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _nms_lib, _pca_lib, _periodic_lib, _reduce_lib
+from . import (_batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
+               _reduce_lib)
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
@@ -1112,6 +1113,89 @@ class TrueKNN:
         """``icp`` with no step taken: fitness, inlier_rmse and correspondences of ``source`` under ``init`` (None: as it is)."""
         return self.icp(source, max_dist, init=init, max_iterations=0)
 
+    def mean_shift_modes(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300):
+        """Mean-shift trajectories over the built set, the loop inside the library (tknnMeanShift): every seed moves to the
+        kernel-weighted mean of the built points within ``radius`` of it (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius; the sums
+        are over the offsets p - x) until its shift is at most ``tol``, it has no neighbours, or ``max_iterations`` steps are taken.
+        ``seeds``: numpy (m,2|3) or a contiguous float32 tensor (m,3) on the engine's device; None: the set's own points, results
+        by row.  ``kernel``: "flat" (sklearn's), "gauss" (exp(-d^2 / (2 bandwidth^2)), truncated at the radius) or "epanechnikov"
+        (1 - d^2 / r^2).  ``radius`` defaults to ``bandwidth``, for "gauss" to 3 ``bandwidth``; ``tol`` to 1e-3 ``bandwidth``
+        (sklearn's).  Returns dict(modes (m,3) float32, counts (m,) int32 and wsum (m,) float32 of the seed's last walk, shift (m,)
+        float32 (+inf where no step was taken), iterations (m,) int32, status (m,) uint8 -- 0 still moving at max_iterations, 1
+        converged, 2 no neighbours, 3 a NaN --, info)."""
+        torch = self._torch
+        if kernel not in _meanshift_lib.KERNELS:
+            raise ValueError("mean_shift_modes: kernel must be one of %s" % ", ".join(sorted(_meanshift_lib.KERNELS)))
+        bandwidth = float(bandwidth)
+        if radius is None:
+            radius = 3.0 * bandwidth if kernel == "gauss" else bandwidth
+        if tol is None:
+            tol = 1e-3 * bandwidth
+        if seeds is not None:
+            seeds = self._queries(seeds, "mean_shift_modes")
+        m = self.n if seeds is None else int(seeds.shape[0])
+        with torch.cuda.device(self.device):
+            out = {"modes": torch.empty((m, 3), dtype=torch.float32, device=self.device),
+                   "counts": torch.empty((m,), dtype=torch.int32, device=self.device),
+                   "wsum": torch.empty((m,), dtype=torch.float32, device=self.device),
+                   "shift": torch.empty((m,), dtype=torch.float32, device=self.device),
+                   "iterations": torch.empty((m,), dtype=torch.int32, device=self.device),
+                   "status": torch.empty((m,), dtype=torch.uint8, device=self.device)}
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            opt = _meanshift_lib.MeanShiftOptions()
+            opt.m, opt.radius, opt.bandwidth, opt.tol = m, float(radius), bandwidth, float(tol)
+            opt.weight, opt.max_iterations = _meanshift_lib.KERNELS[kernel], int(max_iterations)
+            opt.d_seeds = None if seeds is None else _address(seeds, spare)
+            for name in _meanshift_lib.OUTPUTS:
+                setattr(opt, "d_" + name, _address(out[name], spare))
+            info = _meanshift_lib.MeanShiftInfo()
+            _lib.check(_meanshift_lib.load().tknnMeanShift(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
+    def mean_shift(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300, merge_radius=None, cluster_all=True,
+                   min_count=1, points=None):
+        """Mean-shift clustering of the built set, sklearn's ``MeanShift``: ``mean_shift_modes`` for the trajectories, then the
+        existing calls for the rest.  The candidates are the seeds that converged with at least ``min_count`` neighbours; among
+        candidates within ``merge_radius`` (default: ``bandwidth``) of each other the one with the larger score -- its neighbour
+        count, for "gauss" and "epanechnikov" its weight sum -- stays, the smaller row among equal scores (``radius_nms`` on a tree
+        of the modes); ``centers`` are the kept modes by descending score, then ascending candidate row.  ``labels``: the nearest
+        centre of every point (``knn`` at k = 1 against a tree of the centres); with ``cluster_all`` False only within
+        ``bandwidth`` (``radius_knn``), -1 otherwise; a point with a NaN is -1.  ``points``: the built set again, by the caller's
+        row (numpy or a tensor on the engine's device) -- the engine keeps no copy by row.  ``seeds`` None: the points themselves.
+        Returns dict(centers (c,3) float32, labels (n,) int64, scores (c,) float32, modes, the arrays of ``mean_shift_modes``, info)."""
+        torch = self._torch
+        if points is None:
+            raise ValueError("mean_shift: give points, the built set by the caller's row (the labels are theirs)")
+        points = self._points(points)
+        if points.shape[0] != self.n:
+            raise ValueError("mean_shift: points must be the built set, one row per built point")
+        res = self.mean_shift_modes(bandwidth, seeds=seeds, kernel=kernel, radius=radius, tol=tol, max_iterations=max_iterations)
+        with torch.cuda.device(self.device):
+            cand = torch.nonzero((res["status"] == _meanshift_lib.MS_CONVERGED) & (res["counts"] >= int(min_count))).reshape(-1)
+            res["centers"] = torch.empty((0, 3), dtype=torch.float32, device=self.device)
+            res["scores"] = torch.empty((0,), dtype=torch.float32, device=self.device)
+            res["labels"] = torch.full((self.n,), -1, dtype=torch.int64, device=self.device)
+            if cand.numel() == 0:
+                return res
+            modes = res["modes"][cand].contiguous()
+            scores = (res["counts"] if kernel == "flat" else res["wsum"])[cand].to(torch.float32).contiguous()
+            other = TrueKNN(device=self.device.index)
+            try:
+                other.build(modes)
+                kept = other.radius_nms(float(bandwidth if merge_radius is None else merge_radius), scores=scores, want_cover=False)["idx"]
+                order = torch.sort(scores[kept], descending=True, stable=True).indices  # (kept ascends by candidate row)
+                res["centers"], res["scores"] = modes[kept[order]].contiguous(), scores[kept[order]]
+                other.build(res["centers"])
+                if cluster_all:
+                    near = other.knn(points, k=1, want_dist=False)["idx"]
+                else:
+                    near = other.radius_knn(points, 1, radius=float(bandwidth), want_dist=False)["idx"]
+                res["labels"] = near[:, 0].to(torch.int64)
+            finally:
+                other.close()
+        return res
+
     def _is_batched(self):
         """Whether the engine's tree is a batched one (tknnBatchLayout answers for those only)."""
         nb = ctypes.c_int32(0)
@@ -1394,6 +1478,44 @@ def local_pca(points, queries, radius=None, k=None, ids=None, batch=None, **kw):
 def icp(target, source, max_dist, **kw):
     """One-shot helper: build over ``target`` and register ``source`` to it (TrueKNN.icp), results as numpy arrays."""
     return _one_shot(target, lambda eng: eng.icp(source, max_dist, **kw))
+
+
+def bin_seeds(points, bin_size, min_bin_freq=1):
+    """The seeds sklearn's ``get_bin_seeds`` gives, made on the device: the points (numpy (n,2|3) or a float32 (n,3) CUDA tensor;
+    rows with a coordinate that is not finite are left out) are binned onto the grid round(p / bin_size) in fp32, the bins with at
+    least ``min_bin_freq`` points are kept (torch.unique on a packed int64 key, with counts), and a seed is its bin times
+    ``bin_size``.  Returns a float32 (s,3) tensor on the points' device, the seeds in ascending (x, y, z) bin order: the result
+    does not depend on the order of the points."""
+    import torch
+
+    if isinstance(points, np.ndarray):
+        points = torch.from_numpy(pad_to_3d(np.asarray(points, np.float32))).to("cuda")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_cuda:
+        raise ValueError("bin_seeds: points must be float32 (n,3) on the GPU")
+    if not float(bin_size) > 0:
+        raise ValueError("bin_seeds: bin_size must be > 0")
+    size = torch.tensor(float(bin_size), dtype=torch.float32, device=points.device)  # (a tensor: a true division, not a reciprocal)
+    points = points[torch.isfinite(points).all(dim=1)]
+    if points.shape[0] == 0:
+        return torch.empty((0, 3), dtype=torch.float32, device=points.device)
+    bins = torch.round(points / size).to(torch.int64)
+    lo = bins.min(dim=0).values
+    span = (bins.max(dim=0).values - lo + 1).tolist()
+    if span[0] * span[1] * span[2] >= 2 ** 62:
+        raise ValueError("bin_seeds: the grid of bins does not fit an int64 key; choose a larger bin_size")
+    rel = bins - lo
+    key = (rel[:, 0] * span[1] + rel[:, 1]) * span[2] + rel[:, 2]
+    uniq, freq = torch.unique(key, return_counts=True)  # ascending
+    uniq = uniq[freq >= int(min_bin_freq)]
+    cell = torch.stack([uniq // (span[1] * span[2]), (uniq // span[2]) % span[1], uniq % span[2]], dim=1) + lo
+    return (cell.to(torch.float32) * size).contiguous()
+
+
+def mean_shift(points, bandwidth, seeds=None, **kw):
+    """One-shot helper: build over ``points`` and cluster them by mean shift from ``seeds`` (None: the points themselves;
+    ``bin_seeds(points, bandwidth)`` for sklearn's bin_seeding) as TrueKNN.mean_shift does, results as numpy arrays."""
+    points = pad_to_3d(np.asarray(points, np.float32))
+    return _one_shot(points, lambda eng: eng.mean_shift(bandwidth, seeds=seeds, points=points, **kw))
 
 
 def dbscan_query(points, queries, eps, min_pts):
