@@ -37,6 +37,14 @@ def local_pca(points, queries, radius=None, k=None, **kw):
     return _local_pca(points, queries, radius=radius, k=k, **kw)
 
 
+def fpfh(points, radius, normals=None, **kw):
+    """The 33-bin Fast Point Feature Histogram of every point from its normal and its neighbours' within ``radius``, no neighbour lists
+    written (trueknn.fpfh; loads the library)."""
+    from .trueknn import fpfh as _fpfh
+
+    return _fpfh(points, radius, normals=normals, **kw)
+
+
 def icp(target, source, max_dist, **kw):
     """Rigid registration of ``source`` to ``target`` by iterated closest points, point-to-point or point-to-plane, the loop and
     its fp64 sums inside the library (trueknn.icp; loads the library)."""

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -483,6 +483,19 @@ int tknnLocalPca(tknnEngine e, const tknnLocalPcaOptions *options, tknnLocalPcaI
     if (o.k > TKNN_MAX_K_REGISTERS) c.refuse(TKNN_E_UNSUPPORTED, "k out of range (1 .. " + std::to_string(TKNN_MAX_K_REGISTERS) + ")");
     zero(info);
     if (o.m > 0) e->impl.local_pca(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnFpfh(tknnEngine e, const tknnFpfhOptions *options, tknnFpfhInfo *info, void *stream) {
+  return api("tknnFpfh", e, stream, [&](const Call &c) {
+    const tknnFpfhOptions &o = c.record(options);
+    c.require(o.d_fpfh || o.d_spfh || o.d_spfh_counts || o.d_counts, "no output: give d_fpfh, d_spfh, d_spfh_counts or d_counts");
+    c.need(o.d_normals, "d_normals");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.positive(o.radius, "radius");
+    c.require((o.flags & ~TKNN_FPFH_NO_SELF_TERM) == 0u, "flags has a bit no flag of this call has");
+    zero(info);
+    if (e->impl.size() > 0) e->impl.fpfh(o, info, (hipStream_t)stream);
   });
 }
 

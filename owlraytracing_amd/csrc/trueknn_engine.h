@@ -12,6 +12,7 @@
 #include "owlknn_batch.h"
 #include "owlknn_debug.h"
 #include "owlknn_emst.h"
+#include "owlknn_fpfh.h"
 #include "owlknn_fps.h"
 #include "owlknn_hdbscan.h"
 #include "owlknn_icp.h"
@@ -198,6 +199,10 @@ class Engine {
   // kernel-weighted mean of the points within a radius of it until it stops, the loop and its shrinking work list on the device
   // (tknnMeanShift); m > 0, the tree a point tree
   void mean_shift(const tknnMeanShiftOptions &o, tknnMeanShiftInfo *info, hipStream_t s);
+  // fpfh.hip: the 33-bin point-feature histogram of each of the tree's own points from the caller's normals -- a walk that bins
+  // the pair features of every neighbour within the radius, a second that sums the neighbours' histograms by 1 / d^2 --, no
+  // lists written (tknnFpfh); n > 0, the tree a point tree
+  void fpfh(const tknnFpfhOptions &o, tknnFpfhInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

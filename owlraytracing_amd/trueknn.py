@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import (_batch_lib, _emst_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
+from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
                _reduce_lib)
 from .datasets import pad_to_3d
 
@@ -1053,6 +1053,45 @@ class TrueKNN:
         return self.local_pca(radius=radius, k=k, queries=queries, skip_self=skip_self, viewpoint=viewpoint, min_points=min_points,
                               want=("normals", "curvature", "counts"))
 
+    def fpfh(self, radius, normals=None, normal_radius=None, normal_k=None, self_term=True, want_spfh=False, want_counts=False):
+        """The 33-bin Fast Point Feature Histogram of every built point, without the lists (tknnFpfh): three histograms of 11 bins
+        over the angles between a point's normal and those of its neighbours within ``radius`` (``radius_query``'s row less the point
+        itself), blended with the neighbours' histograms by 1 / d^2 -- Open3D's ``compute_fpfh_feature``; with ``self_term`` False
+        PCL's ``FPFHEstimation``.  ``normals``: (n,3) float32 by the caller's row, numpy or a tensor on the engine's device, read as
+        given and not normalised; None: exactly one of ``normal_radius`` and ``normal_k`` is given and ``self.normals(...)``
+        supplies them.  Returns dict(fpfh (n,33) float32, spfh (n,33) float32 and spfh_counts (n,33) int32 [``want_spfh``],
+        counts (n,) int32 [``want_counts``], info)."""
+        torch = self._torch
+        if normals is None:
+            if (normal_radius is None) == (normal_k is None):
+                raise ValueError("fpfh: give normals, or exactly one of normal_radius and normal_k")
+            normals = self.normals(radius=normal_radius, k=normal_k)["normals"]
+        elif normal_radius is not None or normal_k is not None:
+            raise ValueError("fpfh: normal_radius and normal_k go without normals")
+        n = self.n
+        with torch.cuda.device(self.device):
+            if isinstance(normals, torch.Tensor) and normals.device != self.device:
+                raise ValueError("fpfh: normals are on %s, the engine on %s" % (normals.device, self.device))
+            normals = torch.as_tensor(normals, device=self.device).to(torch.float32).contiguous()
+            if normals.dim() != 2 or tuple(normals.shape) != (n, 3):
+                raise ValueError("fpfh: normals must be (n,3), one row per built point")
+            out = {"fpfh": torch.empty((n, _fpfh_lib.FPFH_BINS), dtype=torch.float32, device=self.device)}
+            if want_spfh:
+                out["spfh"] = torch.empty((n, _fpfh_lib.FPFH_BINS), dtype=torch.float32, device=self.device)
+                out["spfh_counts"] = torch.empty((n, _fpfh_lib.FPFH_BINS), dtype=torch.int32, device=self.device)
+            if want_counts:
+                out["counts"] = torch.empty((n,), dtype=torch.int32, device=self.device)
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            opt = _fpfh_lib.FpfhOptions()
+            opt.radius, opt.flags = float(radius), 0 if self_term else _fpfh_lib.FPFH_NO_SELF_TERM
+            opt.d_normals = _address(normals, spare)
+            opt.d_fpfh, opt.d_spfh, opt.d_spfh_counts = _address(out["fpfh"], spare), _address(out.get("spfh"), spare), _address(out.get("spfh_counts"), spare)
+            opt.d_counts = _address(out.get("counts"), spare)
+            info = _fpfh_lib.FpfhInfo()
+            _lib.check(_fpfh_lib.load().tknnFpfh(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        out["info"] = info.as_dict()
+        return out
+
     def icp(self, source, max_dist, init=None, method="point_to_point", target_normals=None, max_iterations=30, rel_fitness=1e-6,
             rel_rmse=1e-6, robust=None, robust_scale=None, want_correspondences=False, want_aligned=False):
         """Rigid registration of ``source`` to the built points by iterated closest points, the loop inside the library (tknnIcp):
@@ -1473,6 +1512,11 @@ def local_pca(points, queries, radius=None, k=None, ids=None, batch=None, **kw):
         return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
     finally:
         eng.close()
+
+
+def fpfh(points, radius, normals=None, **kw):
+    """One-shot helper: build over ``points`` and describe every point by its FPFH as TrueKNN.fpfh does, results as numpy arrays."""
+    return _one_shot(points, lambda eng: eng.fpfh(radius, normals=normals, **kw))
 
 
 def icp(target, source, max_dist, **kw):
