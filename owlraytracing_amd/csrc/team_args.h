@@ -47,6 +47,7 @@ struct TeamArgs {
   int first_ext;   // ... and whether that gather also lists the blocks of the level after them (see the level loop)
   int merge_ext;   // ... and whether the step's SELECT pass serves that level, too (1; 0: in a turn of its own -- TKNN_TEAM_MERGE=0, measurements)
   int count_flat_max;  // a COUNT round whose longest list is at most this long (<= 12 blocks) has all its block loads in flight at once (team_pass)
+  int lite;        // SELECT rounds whose queries all finish inside the step with <= 16 others take the pass's light path (1; 0: TKNN_TEAM_LITE=0, measurements and tests)
   float tie_span;  // sqrt(number of axes along which the points differ), rounded up: d <= tie_span * Chebyshev distance
   int diag;        // TKNN_DIAG_BUILD only: 1 skip inserts, 2 skip SELECT passes, 4 skip COUNT passes, 8 skip per-block query tests,
                    // 16 / 32 step and gather statistics (atomics: slow), 64 every block visit of a query reads its first listed block

@@ -189,6 +189,21 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     const bool on = r0 + team < n_list;
     int qi = 0;
     if (on) qi = L.qlist[r0 + team];
+    // (SELECT, k <= 16) bit 8 of the entry: a light query -- it finishes inside the step with at most sixteen others in its
+    // box (exact from COUNT), on a front list of at most a.count_flat_max blocks; see the light round below
+    bool lite_q = false;
+    if (SELECT && NREG == 1) {
+      lite_q = (qi >> 8) != 0;
+      qi &= 0xff;
+    }
+    if (TKNN_DIAG_BUILD && SELECT && (a.diag & 128)) {  // SELECT rounds, their queries, the light ones among them
+      const unsigned long long q_m = __ballot(on && tl == 0), l_m = __ballot(on && tl == 0 && lite_q);
+      if (lane == 0) {
+        atomicAdd(&a.counters[18], 1ull);
+        atomicAdd(&a.counters[19], (unsigned long long)__popcll(q_m));
+        atomicAdd(&a.counters[20], (unsigned long long)__popcll(l_m));
+      }
+    }
     const float *rec = L.qrec + qi * kQrecStride;
     const float t_qx = rec[0], t_qy = rec[1], t_qz = rec[2];
     const int32_t t_qid = __float_as_int(rec[3]);
@@ -256,8 +271,20 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     // one group of prefetch, name the all-NaN block.
     const int steps4 = (steps + 3) & ~3;
     int32_t *my_ent = L.ent + team * kEntStride;
-    for (int base = 0; base < steps4 + 4; base += 16)
-      if (base + tl < kEntStride) my_ent[base + tl] = list_entry(base + tl);
+    // A LIGHT round: every team with a query serves a light one (the pass list has them first: build_qlist) and the longest
+    // list has at most a.count_flat_max (<= 12) blocks.  Wave-uniform.  Its entries are the list as it is, as COUNT's: a light
+    // query has no back part, nothing is gated, so the order of the visits buys nothing.  One store per lane: sixteen entries
+    // are the at most twelve blocks and the group of prefetch behind them (the all-NaN block).
+    const bool lite_round = SELECT && NREG == 1 && steps <= a.count_flat_max && __ballot(on && !lite_q) == 0ull;
+    if (lite_round) {
+      static_assert(4 * kCountFlatGroups + 4 <= 16, "one entry per lane of the team, the group of prefetch included");
+      int32_t e = L.blk[mine[tl]];
+      if (TKNN_DIAG_BUILD && (a.diag & 64)) e = L.blk[mine[0]];
+      my_ent[tl] = resolve_entry<HALO>(tl <= last ? e : nan_block);
+    } else {
+      for (int base = 0; base < steps4 + 4; base += 16)
+        if (base + tl < kEntStride) my_ent[base + tl] = list_entry(base + tl);
+    }
     t_wave_sync();
     uint32_t cnt = 0;
     uint32_t bd[NREG], bi[NREG];  // register j of lane t holds list entry 16 j + t (indices are compile-time: stays in VGPRs)
@@ -388,7 +415,72 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     // code per number of groups -- no back edge to carry buffers over, every s_waitcnt counts exactly, no group past the list's
     // end is loaded -- and the pass has the registers: no list, no keys, no merge.  Whole 16-byte points as in the ring: loads
     // of the three words the count reads measured the same mean and three times the spread (profiles/count_flat_ab.json).
-    if (!SELECT && steps <= a.count_flat_max) {
+    if (lite_round) {
+      // SELECT for queries whose boxes hold at most sixteen others, all of them on a short list: every point in the box
+      // but the query itself is a neighbour, so nothing can be pruned -- no gate, no own block first, no merge while the
+      // round runs.  Every candidate goes to the team's buffer (at most sixteen arrive: COUNT has counted them with this
+      // very test on these very blocks), and ONE sort makes the list.  The query is told from its neighbours by its id on
+      // every block: in list order its own block is anywhere.
+      auto lite_test = [&](const LbvhPoint &p) {
+        const float dx = p.x - t_qx, dy = p.y - t_qy, dz = p.z - t_qz;
+        const float t = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
+        const unsigned long long in_m = in_box(p, t, t_r, in_below, in_upto);
+        cnt = t_count_keep(cnt, in_m, p.id);
+        const float d2 = t_dist2(dx, dy, dz);
+        unsigned long long pm = in_m & __ballot(p.id != t_qid);  // deviceCode.cu:103
+        if (TKNN_DIAG_BUILD && (a.diag & 1)) pm = 0;
+        if (pm) {
+          const uint32_t mine16 = (uint32_t)(pm >> (team << 4)) & 0xffffu;
+          if ((mine16 >> tl) & 1u) {
+            const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (uint32_t)p.id;
+            // (masked: whatever the counts say, a slot lies inside the team's buffer)
+            L.cand[team * kCandCap + ((fill_n + __popc(mine16 & ((1u << tl) - 1u))) & (uint32_t)(kCandCap - 1))] = key;
+          }
+          fill_n += __popc(mine16);
+        }
+      };
+      // Loads as the ring below has them, four blocks in flight and the next group's entries read a group ahead (positions past
+      // the list's end name the all-NaN block): the registers of the ring, which is what SELECT has to spare -- eight or twelve
+      // blocks in flight, as in COUNT's flat path, spilled the level loop's registers around both passes and cost the ordinary
+      // rounds 4 % (profiles/HISTORY.md).
+      {
+        t_point4 b0, b1, b2, b3;
+        {
+          const t_int4 g = my_groups[0];
+          b0 = fetch(g.x);
+          b1 = fetch(g.y);
+          b2 = fetch(g.z);
+          b3 = fetch(g.w);
+        }
+        for (int it = 0; it < steps; it += 4) {
+          const t_int4 g = my_groups[(it >> 2) + 1];  // entries it+4 .. it+7
+          lite_test(unpack(b0));
+          b0 = fetch(g.x);
+          lite_test(unpack(b1));
+          b1 = fetch(g.y);
+          lite_test(unpack(b2));
+          b2 = fetch(g.z);
+          lite_test(unpack(b3));
+          b3 = fetch(g.w);
+          TP_LAP(it == 0 ? 1 : 2);
+        }
+      }
+      // the list: the buffered keys, sorted (t_merge_rows' first half: there is no list to merge them into), empty keys
+      // in the lanes past the last.  The buffer is next written after the following round's set-up has synchronised.
+      t_wave_sync();
+      const unsigned long long *my_buf = L.cand + team * kCandCap;
+      const bool have = (uint32_t)tl < fill_n;
+      const unsigned long long key = have ? my_buf[tl] : 0ull;
+      t_sorted_row((uint32_t)(key >> 32), (uint32_t)key, have, tl, [&](int from) { return my_buf[from]; }, bd[0], bi[0]);
+      if (TKNN_DIAG_BUILD && (a.diag & 128)) {
+        const unsigned long long served = __ballot(on && tl == 0);
+        if (lane == 0) {
+          atomicAdd(&a.counters[16], 1ull);                                    // light rounds
+          atomicAdd(&a.counters[17], (unsigned long long)__popcll(served));  // ... and the queries they served
+        }
+      }
+      TP_LAP(2);
+    } else if (!SELECT && steps <= a.count_flat_max) {
       auto flat = [&](auto groups_c) {
         constexpr int kBlocks = 4 * decltype(groups_c)::value;
         LbvhPoint c[kBlocks];  // (indices are compile-time: registers)
@@ -534,7 +626,13 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
             int2 *rec8 = (int2 *)(a.out_fb + o);
             rec8[0] = make_int2(prim, __float_as_int(d));
             rec8[1] = make_int2(j == 0 ? 0 : a.k, 0);
-            if (j != 0) rec8[2] = make_int2(0, 0);
+            if (j != 0) {
+              // (a zero made here: as a constant the compiler keeps the pair in registers over the whole kernel, spills it,
+              // and reloads it from scratch at this point of the pass loop)
+              int zero;
+              asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+              rec8[2] = make_int2(zero, zero);
+            }
           }
         }
       }
@@ -997,8 +1095,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       // The four teams of a pass step through their lists in lockstep, so a group of four queries
       // costs the longest of its lists: the pass lists are ordered by list length (buckets of 4
       // blocks), which lifts the teams' occupancy from ~77 % to ~95 % on uniform data.
-      auto build_qlist = [&](bool sel, int nblk) -> int {
-        const int bucket = nblk >> 2;  // <= kMaxPerQuery / 4 < 32
+      // The SELECT pass's list has the light queries (`lite`, see below) first, in buckets of their own and marked by bit 8
+      // of their entries: the pass takes a round of light queries alone down a shorter path, a mixed round -- at most one
+      // per pass -- down the usual one.
+      constexpr int kLiteBuckets = NREG == 1 ? kCountFlatGroups + 1 : 0;  // lists of 0 .. 4 * kCountFlatGroups blocks
+      static_assert(kMaxPerQuery / 4 + kLiteBuckets < 32, "list-length buckets of the pass lists are one bit each of a 32-bit word");
+      auto build_qlist = [&](bool sel, int nblk, bool lite) -> int {
+        const int bucket = lite ? nblk >> 2 : (nblk >> 2) + kLiteBuckets;  // <= kMaxPerQuery / 4 + kLiteBuckets < 32
         if (lane == 0) qlist[64] = 0;
         t_wave_sync();
         if (sel) __hip_atomic_fetch_or((uint32_t *)&qlist[64], 1u << bucket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -1013,12 +1116,12 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
           if (mine) pos = base + t_rank(bm);
           base += __popcll(bm);
         }
-        if (sel) qlist[pos] = lane;
+        if (sel) qlist[pos] = lite ? lane | 0x100 : lane;
         t_wave_sync();
         return base;
       };
       {
-        const int n_count = build_qlist(count_first, my_nblk);
+        const int n_count = build_qlist(count_first, my_nblk, false);
         if (!(TKNN_DIAG_BUILD && (a.diag & 4))) {
           if (m > 1)
             team_pass<false, HALO, NREG, false, true>(a, L, n_count, g * 64, own_pts, halo_pts, lane);
@@ -1054,13 +1157,23 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       }
       const bool select_now = speculate || fin_at >= 0;
       if (m > 1 && fin_at == 0) qrec[lane * kQrecStride + 4] = r_in0;  // finishing inside the step: SELECT works in the inner box
+      // A LIGHT query finishes inside the step (counted, so neither speculating nor served at the extension level) with at
+      // most sixteen others in its finishing box -- one row of keys, every one of them a neighbour -- on a list without a
+      // back part that the flat loads of a round can hold (team_pass).  Read from the record: nothing more lives across the passes.
+      bool lite = false;
+      if (NREG == 1 && a.lite && fin_at >= 0 && fin_at < m) {
+        const int pk = __float_as_int(qrec[lane * kQrecStride + 5]);
+        lite = (fin_at == 0 ? c0 : c1) - selfc <= 16u && (pk & 0xff0000) == 0 && (pk & 0xff) <= a.count_flat_max;
+      }
       {
         t_wave_sync();
-        const int n_select = build_qlist(select_now, sel_nblk);
+        const int n_select = build_qlist(select_now, sel_nblk, lite);
         if (!(TKNN_DIAG_BUILD && (a.diag & 2))) team_pass<true, HALO, NREG, FULL, false>(a, L, n_select, g * 64, own_pts, halo_pts, lane);
         t_wave_sync();
       }
       PHASE_END(3);
+      // (the SELECT pass counts a light query's box once more: the count its path relies on)
+      if (TKNN_DIAG_BUILD && lite && qcnt[lane * 2 + 0] != (fin_at == 0 ? c0 : c1)) atomicAdd(&a.counters[21], 1ull);
       const bool ext_sel = fin_at == m;  // served at the extension level
       bool finished = fin_at >= 0 && !ext_sel;
       uint32_t last_others = prev_others;  // (a query served a turn ago keeps its count)
@@ -1223,6 +1336,9 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
     // COUNT rounds of up to so many blocks take the pass's flat path; measurements and tests: 0 = the ring for every round
     a.count_flat_max = 4 * kCountFlatGroups;
     if (const char *e = getenv("TKNN_TEAM_COUNT_FLAT")) a.count_flat_max = std::max(0, std::min(atoi(e), 4 * kCountFlatGroups));
+    // SELECT rounds of light queries take the pass's light path; measurements and tests: 0 = the usual path for every round
+    a.lite = 1;
+    if (const char *e = getenv("TKNN_TEAM_LITE")) a.lite = atoi(e) > 0 ? 1 : 0;
   }
   {
     // axes along which the built points differ at all (2-D inputs carry z = 0, hostCode.cpp:115-118);
@@ -1318,6 +1434,11 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
         fprintf(stderr, "[team diag] %s pass, wave time: %.3g cycles in all; set-up %.1f%%  first group %.1f%%  other groups %.1f%%  epilogue %.1f%%\n",
                 pass ? "SELECT" : "COUNT", tt, 100 * t4[0] / tt, 100 * t4[1] / tt, 100 * t4[2] / tt, 100 * t4[3] / tt);
       }
+      unsigned long long lt[6];  // light rounds, their queries | SELECT rounds, their queries, the light ones among them | count mismatches
+      OWLMI_HIP(hipMemcpy(lt, counters_ + 16, sizeof lt, hipMemcpyDeviceToHost));
+      fprintf(stderr, "[team diag] SELECT rounds: %.4g with %.4g queries, %.4g of them light; light rounds: %.4g (%.1f%% of the rounds) with %.4g queries; "
+                      "light queries whose SELECT count differs from COUNT's: %llu\n",
+              (double)lt[2], (double)lt[3], (double)lt[4], (double)lt[0], lt[2] ? 100.0 * (double)lt[0] / (double)lt[2] : 0.0, (double)lt[1], lt[5]);
     }
     if (a.diag & 32) {
       unsigned long long g[2];
