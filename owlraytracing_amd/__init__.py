@@ -53,6 +53,30 @@ def icp(target, source, max_dist, **kw):
     return _icp(target, source, max_dist, **kw)
 
 
+def match_features(source_feat, target_feat, **kw):
+    """Nearest and second-nearest target descriptor of every source descriptor, D <= 64, by brute force in literal fp32, with the
+    mutual and ratio filters (trueknn.match_features; loads the library)."""
+    from .trueknn import match_features as _match_features
+
+    return _match_features(source_feat, target_feat, **kw)
+
+
+def ransac(source, target, pairs, max_dist, **kw):
+    """RANSAC over correspondences on the device: the rigid transform most pairs agree with, refitted to its inliers
+    (trueknn.ransac; loads the library)."""
+    from .trueknn import ransac as _ransac
+
+    return _ransac(source, target, pairs, max_dist, **kw)
+
+
+def global_registration(target, source, feature_radius, max_dist, **kw):
+    """Two unaligned clouds registered on the device from end to end: normals, FPFH, feature matching, RANSAC and ICP
+    (trueknn.global_registration; loads the library)."""
+    from .trueknn import global_registration as _global_registration
+
+    return _global_registration(target, source, feature_radius, max_dist, **kw)
+
+
 def mean_shift(points, bandwidth, seeds=None, **kw):
     """Mean-shift clustering, sklearn's ``MeanShift``: the trajectories on the GPU inside the library, modes merged within a radius,
     every point labelled by its nearest centre (trueknn.mean_shift; loads the library)."""

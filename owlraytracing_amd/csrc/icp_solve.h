@@ -1,5 +1,5 @@
 // icp_solve.h -- the host half of tknnIcp (include/owlknn_icp.h): one step's rigid transform from the moments the device summed, and
-// the update of T.  Plain C++ with no HIP in it: icp.hip includes it, and tests/icp_solve_host.py compiles it with the host compiler.
+// the update of T.  Plain C++ with no HIP in it but ICP_HD: icp.hip and ransac.hip include it, and tests/icp_solve_host.py compiles it with the host compiler.
 //
 // A moment row is kIcpMoments doubles, the coordinates taken relative to a centre c (the centre of the target's scene box):
 //   [0] N, the pairs          [1] sum of d^2          [2] pairs left out of the system (normal not finite)
@@ -9,18 +9,25 @@
 #pragma once
 #include <cmath>
 
+// tknnRansac solves a trial's sample on the device with the same code: the functions are host and device under hipcc
+#if defined(__HIPCC__)
+#define ICP_HD __host__ __device__
+#else
+#define ICP_HD
+#endif
+
 namespace owlmi {
 
 constexpr int kIcpMoments = 32;
 enum { kIcpPairs = 0, kIcpSumD2 = 1, kIcpSkipped = 2, kIcpPositive = 3, kIcpSystem = 4, kIcpPlaneRhs = 25 };
 constexpr int kIcpPointWords = 20, kIcpPlaneWords = 31;  // the words of a row each method uses
 
-inline void icp_identity(double *T) {
+ICP_HD inline void icp_identity(double *T) {
   for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
 }
 
 // C = A B, 4 x 4 row-major (C may be neither A nor B)
-inline void icp_mul(const double *A, const double *B, double *C) {
+ICP_HD inline void icp_mul(const double *A, const double *B, double *C) {
   for (int i = 0; i < 4; i++)
     for (int j = 0; j < 4; j++) {
       double s = 0;
@@ -30,11 +37,11 @@ inline void icp_mul(const double *A, const double *B, double *C) {
 }
 
 // the top three rows of T as the device applies them
-inline void icp_round_rows(const double *T, float *Tf) {
+ICP_HD inline void icp_round_rows(const double *T, float *Tf) {
   for (int i = 0; i < 12; i++) Tf[i] = (float)T[i];
 }
 
-inline void icp_rigid(const double R[3][3], const double t[3], double *dT) {
+ICP_HD inline void icp_rigid(const double R[3][3], const double t[3], double *dT) {
   for (int i = 0; i < 3; i++) {
     for (int j = 0; j < 3; j++) dT[4 * i + j] = R[i][j];
     dT[4 * i + 3] = t[i];
@@ -44,7 +51,7 @@ inline void icp_rigid(const double R[3][3], const double t[3], double *dT) {
 }
 
 // Cyclic Jacobi on a symmetric 4 x 4: A becomes diagonal, the columns of V its eigenvectors.
-inline void icp_jacobi4(double A[4][4], double V[4][4]) {
+ICP_HD inline void icp_jacobi4(double A[4][4], double V[4][4]) {
   for (int i = 0; i < 4; i++)
     for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 64; sweep++) {
@@ -82,7 +89,7 @@ inline void icp_jacobi4(double A[4][4], double V[4][4]) {
 // of Horn's 4 x 4 matrix of H; it is V diag(1, 1, det(V U^T)) U^T of H = U S V^T, a proper rotation by construction.  The
 // eigenvalues are s1 + s2 + s3', s1 - s2 - s3', -s1 + s2 - s3', -s1 - s2 + s3' (s3' = +-s3, the sign of det H), so the singular
 // values the degeneracy rule needs are sums of two of them.  false: degenerate, dT untouched.
-inline bool icp_solve_point(const double *mom, const double *c, double *dT) {
+ICP_HD inline bool icp_solve_point(const double *mom, const double *c, double *dT) {
   const double W = mom[kIcpSystem];
   if (!(mom[kIcpPositive] >= 3.0) || !(W > 0.0)) return false;
   for (int i = kIcpSystem; i < kIcpPointWords; i++)
@@ -128,7 +135,7 @@ inline bool icp_solve_point(const double *mom, const double *c, double *dT) {
 // Point-to-plane.  The system is the one the sums were taken for, J = [a x n, n] with a = s' - c: the step turns about c, so its
 // condition does not depend on where the cloud sits; at the origin it is x -> dR (x - c) + c + t.  Cholesky in double; false: a
 // pivot not above 2^-40 times its diagonal entry (0 up to the rounding of the sums), or not finite.
-inline bool icp_solve_plane(const double *mom, const double *c, double *dT) {
+ICP_HD inline bool icp_solve_plane(const double *mom, const double *c, double *dT) {
   double Ao[6][6], b[6];
   int w = kIcpSystem;
   for (int i = 0; i < 6; i++)

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -524,6 +524,43 @@ int tknnIcp(tknnEngine e, const tknnIcpOptions *options, tknnIcpInfo *info, void
     } else {
       for (int i = 0; i < 16; i++) info->transform[i] = o.init ? o.init[i] : (i % 5 == 0 ? 1.0 : 0.0);
     }
+  });
+}
+
+int tknnFeatureMatch(tknnEngine e, const tknnFeatureMatchOptions *options, tknnFeatureMatchInfo *info, void *stream) {
+  return api("tknnFeatureMatch", e, stream, [&](const Call &c) {
+    const tknnFeatureMatchOptions &o = c.record(options);
+    c.need(info, "info");
+    c.require(o.d_best || o.d_best_d2 || o.d_second_d2, "no output: give d_best, d_best_d2 or d_second_d2");
+    if (o.m > 0) c.need(o.d_source, "d_source");
+    if (o.n > 0) c.need(o.d_target, "d_target");
+    c.require(o.D >= 1 && o.D <= TKNN_MATCH_MAX_D, "D must be 1 .. 64");
+    c.count(o.m, "m");
+    c.count(o.n, "n");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    zero(info);
+    if (o.m > 0) e->impl.feature_match(o, info, (hipStream_t)stream);
+  });
+}
+
+int tknnRansac(tknnEngine e, const tknnRansacOptions *options, tknnRansacInfo *info, void *stream) {
+  return api("tknnRansac", e, stream, [&](const Call &c) {
+    const tknnRansacOptions &o = c.record(options);
+    c.need(info, "info");
+    if (o.ms > 0) c.need(o.d_source, "d_source");
+    if (o.mt > 0) c.need(o.d_target, "d_target");
+    if (o.c > 0) c.need(o.d_pairs, "d_pairs");
+    c.require(o.ransac_n == 3 || o.ransac_n == 4, "ransac_n must be 3 or 4");
+    c.positive(o.max_dist, "max_dist");
+    c.require(o.edge_similarity >= 0.f && o.edge_similarity <= 1.f, "edge_similarity must be 0 .. 1 (0: no edge check)");
+    c.require(o.confidence > 0.0 && o.confidence <= 1.0, "confidence must be in (0, 1] (1: never stop early)");
+    c.require(o.max_trials >= 1, "max_trials must be at least 1");
+    c.require(o.refit_rounds >= 0 && o.refit_rounds <= 8, "refit_rounds must be 0 .. 8");
+    c.count(o.ms, "ms");
+    c.count(o.mt, "mt");
+    c.count(o.c, "c");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    e->impl.ransac(o, info, (hipStream_t)stream);  // (refuses a pair row out of range itself, and writes info at its end only)
   });
 }
 

@@ -14,6 +14,7 @@
 #include "owlknn_emst.h"
 #include "owlknn_fpfh.h"
 #include "owlknn_fps.h"
+#include "owlknn_global.h"
 #include "owlknn_hdbscan.h"
 #include "owlknn_icp.h"
 #include "owlknn_knn.h"
@@ -203,6 +204,13 @@ class Engine {
   // the pair features of every neighbour within the radius, a second that sums the neighbours' histograms by 1 / d^2 --, no
   // lists written (tknnFpfh); n > 0, the tree a point tree
   void fpfh(const tknnFpfhOptions &o, tknnFpfhInfo *info, hipStream_t s);
+  // feature_match.hip: the nearest and second-nearest target row of m source rows in D <= 64 dimensions, dense brute force through
+  // registers and LDS (tknnFeatureMatch); m > 0, needs no tree
+  void feature_match(const tknnFeatureMatchOptions &o, tknnFeatureMatchInfo *info, hipStream_t s);
+  // ransac.hip: RANSAC over c correspondences in batches of trials -- sample, edge check, solve (icp_solve.h on the device), score
+  // against every record, stop by confidence, refit -- (tknnRansac); needs no tree.  An ArgError of TKNN_E_ARG, with nothing the
+  // caller can see written, when a pair names a row out of range
+  void ransac(const tknnRansacOptions &o, tknnRansacInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
+from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _global_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
                _reduce_lib)
 from .datasets import pad_to_3d
 
@@ -1152,6 +1152,107 @@ class TrueKNN:
         """``icp`` with no step taken: fitness, inlier_rmse and correspondences of ``source`` under ``init`` (None: as it is)."""
         return self.icp(source, max_dist, init=init, max_iterations=0)
 
+    def _features(self, feat, who, name):
+        """The descriptor rows ``name`` of ``who`` as the library takes them: a contiguous float32 (rows, D) tensor on the engine's
+        device; numpy is uploaded."""
+        torch = self._torch
+        if isinstance(feat, np.ndarray):
+            feat = torch.from_numpy(np.ascontiguousarray(feat, dtype=np.float32)).to(self.device)
+        if not isinstance(feat, torch.Tensor) or feat.dtype != torch.float32 or feat.dim() != 2:
+            raise ValueError("%s: %s must be float32 (rows, D), numpy or a tensor" % (who, name))
+        if feat.device != self.device:
+            raise ValueError("%s: %s is on %s, the engine on %s" % (who, name, feat.device, self.device))
+        return feat.contiguous()
+
+    def _match(self, a, b):
+        """tknnFeatureMatch of the rows ``a`` against the rows ``b``: (best, best_d2, second_d2, info)."""
+        torch = self._torch
+        m, n, D = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+        best = torch.empty((m,), dtype=torch.int32, device=self.device)
+        best_d2 = torch.empty((m,), dtype=torch.float32, device=self.device)
+        second_d2 = torch.empty((m,), dtype=torch.float32, device=self.device)
+        spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+        opt = _global_lib.FeatureMatchOptions()
+        opt.m, opt.n, opt.D = m, n, D
+        opt.d_source, opt.d_target = _address(a, spare), _address(b, spare)
+        opt.d_best, opt.d_best_d2, opt.d_second_d2 = _address(best, spare), _address(best_d2, spare), _address(second_d2, spare)
+        info = _global_lib.FeatureMatchInfo()
+        _lib.check(_global_lib.load().tknnFeatureMatch(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        return best, best_d2, second_d2, info.as_dict()
+
+    def match_features(self, source_feat, target_feat, mutual=False, ratio=None, want_dist=False):
+        """The nearest and second-nearest row of ``target_feat`` (n, D) for every row of ``source_feat`` (m, D), D <= 64, by brute
+        force in literal fp32 (tknnFeatureMatch; no tree is needed): the matching step between ``fpfh`` and ``ransac``.  Rows are
+        numpy or float32 tensors on the engine's device; a row with an entry that is not finite matches nobody.
+        ``mutual``: a second call with the roles swapped, and only the rows i with best_t[best_s[i]] == i are kept.
+        ``ratio``: only the rows with best_d2 <= ratio^2 * second_d2 are kept (Lowe's test on the distances).
+        Returns dict(pairs (c,2) int32 on the device: source row, target row of the rows kept, in row order; best (m,) int32,
+        -1 for no match; best_d2, second_d2 (m,) float32 squared distances; info[, dist (c,) float32: the distance of each pair,
+        ``want_dist``])."""
+        torch = self._torch
+        with torch.cuda.device(self.device):
+            a, b = self._features(source_feat, "match_features", "source_feat"), self._features(target_feat, "match_features", "target_feat")
+            if a.shape[1] != b.shape[1]:
+                raise ValueError("match_features: source_feat has %d channels, target_feat %d" % (a.shape[1], b.shape[1]))
+            best, best_d2, second_d2, info = self._match(a, b)
+            keep = best >= 0
+            if mutual:
+                back, _, _, info_back = self._match(b, a)
+                rows = torch.arange(a.shape[0], dtype=torch.int32, device=self.device)
+                if b.shape[0] > 0:  # (no target rows: nobody has a best, and there is nothing to index)
+                    keep &= back[best.clamp(min=0).long()] == rows
+                info["swapped"] = info_back
+            if ratio is not None:
+                keep &= best_d2 <= float(np.float32(float(ratio) ** 2)) * second_d2  # (ratio^2 rounded to fp32, the product fp32)
+            rows = torch.nonzero(keep).reshape(-1)
+            out = {"pairs": torch.stack([rows.to(torch.int32), best[rows]], dim=1).contiguous(), "best": best, "best_d2": best_d2, "second_d2": second_d2,
+                   "info": info}
+            if want_dist:
+                out["dist"] = torch.sqrt(best_d2[rows])
+        return out
+
+    def ransac(self, source, target, pairs, max_dist, ransac_n=3, edge_similarity=0.9, max_trials=100000, confidence=0.999, seed=0, refit_rounds=2,
+               want_mask=False, want_trials=False):
+        """RANSAC over correspondences on the device (tknnRansac; no tree is needed): the rigid transform that maps ``source`` rows
+        onto the ``target`` rows ``pairs`` (c,2) int32 names them with, up to ``max_dist``, for the most pairs.  Trials run in
+        batches of 4096: a sample of ``ransac_n`` (3 or 4) pairs drawn by a counter-based hash of ``seed`` and the trial, rejected
+        early unless its edge lengths agree within ``edge_similarity`` (0: no check), solved by Kabsch / Horn in double, and scored
+        against every pair; the loop stops once ``confidence`` is reached or after ``max_trials``; the best is refitted to its
+        inliers up to ``refit_rounds`` times.  ``source``, ``target``: numpy (rows,2|3) or contiguous float32 tensors (rows,3) on the
+        engine's device.  Returns dict(transform (4,4) float64 CPU tensor -- ``icp``'s ``init`` --, best_trial (-1: no sample
+        survived, transform is the identity), inliers, fitness, inlier_rmse, trials_run, batches, status_counts by
+        _global_lib.STATUS, refits_kept, the times; mask (c,) uint8 under the final transform [``want_mask``]; trial_status and
+        trial_inliers (max_trials,) int32, -1 where not run or not scored [``want_trials``])."""
+        torch = self._torch
+        source, target = self._queries(source, "ransac"), self._queries(target, "ransac")
+        with torch.cuda.device(self.device):
+            if isinstance(pairs, np.ndarray):
+                pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(self.device)
+            if not isinstance(pairs, torch.Tensor) or pairs.dim() != 2 or pairs.shape[1] != 2:
+                raise ValueError("ransac: pairs must be (c,2): source row, target row")
+            self._written_in_place("ransac", "pairs", pairs, tuple(pairs.shape), torch.int32)
+            c, trials = int(pairs.shape[0]), int(max_trials)
+            spare = torch.empty((4,), dtype=torch.int32, device=self.device)
+            mask = torch.empty((c,), dtype=torch.uint8, device=self.device) if want_mask else None
+            status = torch.empty((max(trials, 0),), dtype=torch.int32, device=self.device) if want_trials else None
+            inliers = torch.empty((max(trials, 0),), dtype=torch.int32, device=self.device) if want_trials else None
+            opt = _global_lib.RansacOptions()
+            opt.ms, opt.mt, opt.c = int(source.shape[0]), int(target.shape[0]), c
+            opt.d_source, opt.d_target, opt.d_pairs = _address(source, spare), _address(target, spare), _address(pairs, spare)
+            opt.ransac_n, opt.max_dist, opt.edge_similarity = int(ransac_n), float(max_dist), float(edge_similarity)
+            opt.max_trials, opt.confidence, opt.seed, opt.refit_rounds = trials, float(confidence), int(seed) & 0xFFFFFFFF, int(refit_rounds)
+            opt.d_inlier_mask, opt.d_trial_status, opt.d_trial_inliers = _address(mask, spare), _address(status, spare), _address(inliers, spare)
+            info = _global_lib.RansacInfo()
+            _lib.check(_global_lib.load().tknnRansac(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        res = info.as_dict()
+        res["transform"] = torch.tensor(list(info.transform), dtype=torch.float64).reshape(4, 4)
+        res["status_counts"] = dict(zip(_global_lib.STATUS, info.status_counts))
+        if want_mask:
+            res["mask"] = mask
+        if want_trials:
+            res["trial_status"], res["trial_inliers"] = status, inliers
+        return res
+
     def mean_shift_modes(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300):
         """Mean-shift trajectories over the built set, the loop inside the library (tknnMeanShift): every seed moves to the
         kernel-weighted mean of the built points within ``radius`` of it (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius; the sums
@@ -1522,6 +1623,61 @@ def fpfh(points, radius, normals=None, **kw):
 def icp(target, source, max_dist, **kw):
     """One-shot helper: build over ``target`` and register ``source`` to it (TrueKNN.icp), results as numpy arrays."""
     return _one_shot(target, lambda eng: eng.icp(source, max_dist, **kw))
+
+
+def _treeless(call):
+    """An engine without a tree for the one ``call(engine)``: its results as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        return {name: (t.cpu().numpy() if hasattr(t, "cpu") else t) for name, t in call(eng).items()}
+    finally:
+        eng.close()
+
+
+def match_features(source_feat, target_feat, **kw):
+    """One-shot helper: match the descriptor rows (TrueKNN.match_features), results as numpy arrays.  No point set is needed."""
+    return _treeless(lambda eng: eng.match_features(np.asarray(source_feat), np.asarray(target_feat), **kw))
+
+
+def ransac(source, target, pairs, max_dist, **kw):
+    """One-shot helper: RANSAC over the correspondences (TrueKNN.ransac), results as numpy arrays.  No tree is built."""
+    return _treeless(lambda eng: eng.ransac(np.asarray(source, dtype=np.float32), np.asarray(target, dtype=np.float32), np.asarray(pairs), max_dist, **kw))
+
+
+def global_registration(target, source, feature_radius, max_dist, normal_k=16, mutual=True, icp=True, target_viewpoint=None, source_viewpoint=None,
+                        **kw):
+    """Registration of two unaligned clouds, on the device from end to end: an engine per cloud, ``fpfh(feature_radius,
+    normal_k=normal_k)`` on both, ``match_features(mutual=mutual)``, ``ransac(max_dist, **kw)`` and, with ``icp``,
+    ``icp(max_dist, init=...)`` on the target's engine.  An FPFH is not invariant under a flip of the normals, and a normal
+    without a viewpoint takes its sign from its largest component, which a rotation of the cloud changes: give each cloud the
+    position it was seen from (``target_viewpoint``, ``source_viewpoint``, each in its own frame) and its normals are turned
+    towards it (``normals(k=normal_k, viewpoint=...)``) before the FPFH.  Returns dict(ransac, ransac_eval, pairs (c,2) numpy,
+    match_info[, icp, icp_eval], transform): the results of the calls, and ``evaluate_registration`` of each transform on the full
+    clouds; transform: ICP's with ``icp``, else RANSAC's."""
+    et, es = TrueKNN(), TrueKNN()
+
+    def describe(eng, viewpoint):
+        if viewpoint is None:
+            return eng.fpfh(feature_radius, normal_k=normal_k)["fpfh"]
+        return eng.fpfh(feature_radius, normals=eng.normals(k=normal_k, viewpoint=viewpoint)["normals"])["fpfh"]
+
+    try:
+        et.build(target)
+        es.build(source)
+        ft, fs = describe(et, target_viewpoint), describe(es, source_viewpoint)
+        match = es.match_features(fs, ft, mutual=mutual)
+        src, tgt = es._queries(source, "global_registration"), et._queries(target, "global_registration")
+        rs = es.ransac(src, tgt, match["pairs"], max_dist, **kw)
+        out = {"ransac": rs, "pairs": match["pairs"].cpu().numpy(), "match_info": match["info"], "transform": rs["transform"],
+               "ransac_eval": et.evaluate_registration(src, max_dist, init=rs["transform"])}
+        if icp:
+            out["icp"] = et.icp(src, max_dist, init=rs["transform"])
+            out["transform"] = out["icp"]["transform"]
+            out["icp_eval"] = et.evaluate_registration(src, max_dist, init=out["transform"])
+        return out
+    finally:
+        et.close()
+        es.close()
 
 
 def bin_seeds(points, bin_size, min_bin_freq=1):
