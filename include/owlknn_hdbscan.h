@@ -123,7 +123,7 @@ typedef struct {
   int32_t *d_parent;        /* 2n - 1, may be NULL */
   int32_t *d_left, *d_right, *d_size; /* n - 1 each, may be NULL */
   double *d_lambda;         /* n, may be NULL */
-  double *d_stability;      /* n - 1, may be NULL */
+  double *d_stability;      /* n - 1, may be NULL; 0 behind info.edges: no node there heads a cluster */
 } tknnHdbscanOptions;
 typedef struct {
   tknnHdbscanLabelsInfo labels; /* solve_ms in here: the whole call */

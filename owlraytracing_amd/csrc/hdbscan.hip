@@ -475,6 +475,11 @@ void Engine::hdbscan(const tknnHdbscanOptions &o, tknnHdbscanInfo *info, hipStre
   lo.d_lambda = o.d_lambda, lo.d_stability = o.d_stability;
   tknnHdbscanLabelsInfo labels_info;
   std::memset(&labels_info, 0, sizeof labels_info);
+  // d_stability holds n - 1 entries here and is no linkage array: the entries behind the records head no cluster, which is a 0
+  // (tknnHdbscanLabels writes the first `edges` of them)
+  if (o.d_stability && edges < n - 1) {
+    OWLMI_HIP(hipMemsetAsync(o.d_stability + edges, 0, (size_t)(n - 1 - edges) * sizeof(double), s));
+  }
   hdbscan_labels(lo, &labels_info, s);
   t1.record(s);
   OWLMI_HIP(hipStreamSynchronize(s));

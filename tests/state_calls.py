@@ -13,6 +13,13 @@ times.  The trees are the spec modules' sets, reduced to what every scenario nee
   n1025b3  reduce_spec n1025     three batches in one tree
   n1       reduce_spec n1        one point: no internal node
   n4097    uniform               257 leaf blocks, the last of one point; five boxes on the second pyramid level
+
+`<tree>q<m>` (n1025q1, n1025q63, n1025q65, n1025b3q65) is the tree with the first m of its queries: one query, one short of a wave,
+one more than a wave.  The CPU references are cached by the tree's name, so a variant has its own.
+
+TABLE is what tests/test_engine_state_gpu.py runs.  GUARDED_ONLY holds the scenarios that only tests/test_output_bounds_gpu.py
+reads (they would lengthen the other file's chain): the calls whose state files bring their own point sets, the row-writing calls
+at the register lists' capacities, and the calls that document a region they do not write.
 """
 import os
 import sys
@@ -49,7 +56,26 @@ MARGIN = 1e-6  # tests/test_hdbscan_expectations.py: the excess-of-mass margin a
 
 
 # ---- the trees ---------------------------------------------------------------------------------------------------------------------
+def _variant(name):
+    """The tree `<base>q<m>`: the base tree with the first m of its queries."""
+    base, m = name.rsplit("q", 1)
+    t = dict(tree(base))
+    m = int(m)
+    assert 0 < m < len(t["Q"])
+    t["name"] = name
+    t["Q"] = np.ascontiguousarray(t["Q"][:m])
+    t["Qf"] = np.ascontiguousarray(t["Q"][~np.isnan(t["Q"]).any(axis=1)])
+    t["qbatch"] = np.ascontiguousarray(t["qbatch"][:m])
+    for a in (t["Q"], t["Qf"], t["qbatch"]):
+        a.setflags(write=False)
+    return t
+
+
 def _tree(name):
+    if name == "own":  # the scenario brings its own set and builds it (GUARDED_ONLY)
+        return {"name": "own", "n": 0, "nan": False, "batch": None, "ids": None}
+    if name.rsplit("q", 1)[-1].isdigit() and "q" in name:
+        return _variant(name)
     ids = batch = None
     if name == "n4097":
         P = datasets.uniform3d(4097, seed=97)
@@ -135,8 +161,8 @@ def differing(got, want, skip=()):
 
 
 # ---- solve, repair, query ------------------------------------------------------------------------------------------------------------
-def _solve_k(t, big):
-    return K_BIG if big else min(K_SMALL, t["n"] - 1)
+def _solve_k(t, big, k=None):
+    return K_BIG if big else min(K_SMALL if k is None else k, t["n"] - 1)
 
 
 def _global(t):
@@ -146,12 +172,14 @@ def _global(t):
     return G, t["names"]
 
 
-def _solve(kernel, big=False, levels=False):
+def _solve(kernel, big=False, levels=False, k=None):
+    want_k = k
+
     def run(eng, t):
-        return eng.solve(_solve_k(t, big), float(t["r0"]), kernel=kernel, want_levels=levels)
+        return eng.solve(_solve_k(t, big, want_k), float(t["r0"]), kernel=kernel, want_levels=levels)
 
     def check(t, f):
-        k = _solve_k(t, big)
+        k = _solve_k(t, big, want_k)
         G, rows = _global(t)
         ref = shared(("solve", t["name"], k), lambda: oracle.trueknn(G, k, float(t["r0"])))
         assert np.array_equal(f["idx"], ref["idx"][rows]) and np.array_equal(bits(f["dist"]), bits(ref["dist"][rows])), "rows differ from the replay"
@@ -177,13 +205,15 @@ def _repair():
     return run, check
 
 
-def _query():
+def _query(k=K_SMALL):
+    want_k = k
+
     def run(eng, t):
-        return eng.query(np.array(t["Qf"]), min(K_SMALL, t["n"]), float(t["r0"]), want_levels=True)
+        return eng.query(np.array(t["Qf"]), min(want_k, t["n"]), float(t["r0"]), want_levels=True)
 
     def check(t, f):
-        k = min(K_SMALL, t["n"])
-        want = shared(("query", t["name"]), lambda: qs.query_rows(t["P"], t["Qf"], [k], float(t["r0"]), ids=t["ids"])[k])
+        k = min(want_k, t["n"])
+        want = shared(("query", t["name"], k), lambda: qs.query_rows(t["P"], t["Qf"], [k], float(t["r0"]), ids=t["ids"])[k])
         for name in ("idx", "intersections", "levels"):
             assert np.array_equal(f[name], want[name]), name
         assert np.array_equal(bits(f["dist"]), bits(want["dist"]))
@@ -284,42 +314,42 @@ def _skip(t):
     return np.where(np.arange(m) % 3 == 0, t["names"][np.arange(m) % t["n"]], -1).astype(np.int32)
 
 
-def _radius_knn():
+def _radius_knn(k=8):
     def run(eng, t):
-        return eng.radius_knn(np.array(t["Q"]), 8, radius=float(t["r"]), skip_ids=_skip(t))
+        return eng.radius_knn(np.array(t["Q"]), k, radius=float(t["r"]), skip_ids=_skip(t))
 
     def check(t, f):
-        _rows_equal(f, shared(("radius_knn", t["name"]), lambda: rk.knn_rows(t["P"], t["Q"], 8, radius=t["r"], skip=_skip(t), ids=t["ids"])))
+        _rows_equal(f, shared(("radius_knn", t["name"], k), lambda: rk.knn_rows(t["P"], t["Q"], k, radius=t["r"], skip=_skip(t), ids=t["ids"])))
     return run, check
 
 
-def _knn(own):
+def _knn(own, k=8):
     def run(eng, t):
-        return eng.knn(None if own else np.array(t["Q"]), k=8)
+        return eng.knn(None if own else np.array(t["Q"]), k=k)
 
     def check(t, f):
-        _rows_equal(f, shared(("knn", own, t["name"]), lambda: kn.self_rows(t["P"], 8, ids=t["ids"]) if own else kn.knn_rows(t["P"], t["Q"], 8, ids=t["ids"])))
+        _rows_equal(f, shared(("knn", own, t["name"], k), lambda: kn.self_rows(t["P"], k, ids=t["ids"]) if own else kn.knn_rows(t["P"], t["Q"], k, ids=t["ids"])))
     return run, check
 
 
 CELL = ((0.0, 0.0, 0.0), (1.0, 1.0, 0.0))  # x and y periodic, z open: every set here lies in [0, 1)
 
 
-def _periodic_knn():
+def _periodic_knn(k=8):
     def run(eng, t):
-        return eng.periodic_knn(np.array(t["Q"]), k=8, lo=CELL[0], period=CELL[1], radius=float(t["r"]))
+        return eng.periodic_knn(np.array(t["Q"]), k=k, lo=CELL[0], period=CELL[1], radius=float(t["r"]))
 
     def check(t, f):
-        _rows_equal(f, shared(("periodic", t["name"]), lambda: pp.knn_rows(t["P"], t["Q"], 8, CELL[0], CELL[1], radius=t["r"], ids=t["ids"])))
+        _rows_equal(f, shared(("periodic", t["name"], k), lambda: pp.knn_rows(t["P"], t["Q"], k, CELL[0], CELL[1], radius=t["r"], ids=t["ids"])))
     return run, check
 
 
-def _batch_knn():
+def _batch_knn(k=8):
     def run(eng, t):
-        return eng.batch_knn(np.array(t["Q"]), k=8, batch=np.array(t["qbatch"]))
+        return eng.batch_knn(np.array(t["Q"]), k=k, batch=np.array(t["qbatch"]))
 
     def check(t, f):
-        _rows_equal(f, shared(("batch", t["name"]), lambda: bs.knn_rows(t["P"], t["batch"], t["Q"], t["qbatch"], 8, ids=t["ids"])))
+        _rows_equal(f, shared(("batch", t["name"], k), lambda: bs.knn_rows(t["P"], t["batch"], t["Q"], t["qbatch"], k, ids=t["ids"])))
     return run, check
 
 
@@ -476,7 +506,9 @@ def _reduce(weight, C, own):
     return run, check
 
 
-def _pca(hood, own):
+def _pca(hood, own, k=None):
+    """hood: (whether the radius bounds the neighbourhood, the k that does or None); `k` replaces the hood's in the k mode."""
+    hood = hood if k is None or hood[1] is None else (hood[0], k)
     radius, k = hood
 
     def run(eng, t):
@@ -627,11 +659,158 @@ def _phases(poison_between=False):
     return run, check
 
 
+# ---- what a batched build made ---------------------------------------------------------------------------------------------------------
+def _batch_layout():
+    def run(eng, t):
+        return eng.batch_layout()
+
+    def check(t, f):
+        clean = ~np.isnan(t["P"]).any(axis=1)
+        sizes = np.bincount(t["batch"][clean], minlength=t["num_batches"])
+        assert f["num_batches"][0] == t["num_batches"] and np.array_equal(f["starts"], np.concatenate([[0], np.cumsum(sizes)]))
+    return run, check
+
+
+# ---- rows that a call documents as not written -------------------------------------------------------------------------------------------
+def _level_cap(t, k):
+    """(levels of the replay by row, the last level a capped solve still serves): one below the deepest, so that some rows stay."""
+    G, rows = _global(t)
+    lv = shared(("levels", t["name"], k), lambda: trueknn_numpy(G, k, float(t["r0"]))["level"])[rows]
+    return lv, int(lv.max()) - 1
+
+
+def _solve_unfinished():
+    def run(eng, t):
+        k = _solve_k(t, False)
+        return eng.solve(k, float(t["r0"]), kernel=_lib.KERNEL_TEAM, max_rounds=_level_cap(t, k)[1] + 1, allow_unfinished=True)
+
+    def check(t, f):
+        k = _solve_k(t, False)
+        G, rows = _global(t)
+        lv, cap = _level_cap(t, k)
+        fin = lv <= cap
+        assert 0 < fin.sum() < len(fin), "some rows finish and some do not"
+        ref = shared(("solve", t["name"], k), lambda: oracle.trueknn(G, k, float(t["r0"])))
+        assert np.array_equal(f["levels"], np.where(fin, lv, -1)) and f["info.unfinished"][0] == (~fin).sum()
+        assert np.array_equal(f["idx"][fin], ref["idx"][rows][fin]) and np.array_equal(bits(f["dist"][fin]), bits(ref["dist"][rows][fin]))
+        assert np.array_equal(f["intersections"][fin], ref["intersections"][rows][fin])
+    return run, check
+
+
+QUERY_ROUNDS = 2  # of the capped query: rows that need a third radius, and the NaN query, stay unfinished
+
+
+def _query_unfinished():
+    def run(eng, t):
+        return eng.query(np.array(t["Q"]), min(K_SMALL, t["n"]), float(t["r0"]), max_rounds=QUERY_ROUNDS, allow_unfinished=True)
+
+    def check(t, f):
+        k = min(K_SMALL, t["n"])
+        want = shared(("query_capped", t["name"]), lambda: qs.query_rows(t["P"], t["Q"], [k], float(t["r0"]), ids=t["ids"], max_rounds=QUERY_ROUNDS)[k])
+        fin = want["levels"] >= 0
+        assert 0 < fin.sum() < len(fin), "some rows finish and some do not"
+        assert np.array_equal(f["levels"], want["levels"]) and f["info.unfinished"][0] == want["unfinished"]
+        assert np.array_equal(f["idx"][fin], want["idx"][fin]) and np.array_equal(bits(f["dist"][fin]), bits(want["dist"][fin]))
+        assert np.array_equal(f["intersections"][fin], want["intersections"][fin])
+    return run, check
+
+
+# ---- the calls whose state files bring their own sets: their runners and their comparisons ------------------------------------------------
+def _mean_shift_modes(kernel, own=False):
+    def run(eng, t):
+        import test_meanshift_state_gpu as m
+
+        P, S, Q, big = m.case()
+        eng.build(P)
+        return m.shift(eng, kernel, S, own=own)
+
+    def check(t, f):
+        info = f["info"]  # (iterations, walks, converged, empty, running, invalid): what that file's fresh results are held to
+        if not own:
+            assert info[0] >= 2 and info[1] < 1300 * info[0] and info[3] == 1 and info[5] == 1, "several passes, a shrinking list, an EMPTY and an INVALID seed"
+        assert info[2] + info[3] + info[4] + info[5] == len(f["status"]) and f["status"].max() <= 3
+    return run, check
+
+
+def _mean_shift():
+    """The clustering on top: tests/test_meanshift_gpu.py's comparison -- the merge and the labels are the spec's, applied to the
+    device's own modes and scores, exactly."""
+    import meanshift_spec as ms
+
+    def run(eng, t):
+        P, _ = ms.blobs()
+        eng.build(np.array(P))
+        return eng.mean_shift(ms.BLOB_KERNELS["flat"]["bandwidth"], points=np.array(P), max_iterations=10)
+
+    def check(t, f):
+        P, comp = ms.blobs()
+        want = ms.merge_and_label(P, f["modes"], f["counts"], f["status"], f["counts"], ms.BLOB_KERNELS["flat"]["bandwidth"])
+        assert np.array_equal(bits(f["centers"]), bits(want["centers"])) and np.array_equal(f["labels"], want["labels"])
+        assert np.array_equal(bits(f["scores"]), bits(want["scores"])) and len(f["centers"]) > 0
+    return run, check
+
+
+FPFH_BY_SPEC = ("fpfh", "spfh")  # tests/test_fpfh_state_gpu.py's rule: the floats inside the bound of the spec, the rest bit for bit
+
+
+def _fpfh():
+    def run(eng, t):
+        import fpfh_spec as fs
+        import test_fpfh_state_gpu as m
+
+        eng.build(np.array(fs.case(m.NAME)["P"]))
+        return m.describe(eng)
+
+    def check(t, f):
+        import test_fpfh_state_gpu as m
+
+        m.same(f, f, "against the spec")  # (the counts against themselves; what it adds is the floats against the spec's bound)
+    return run, check
+
+
+def _icp(method):
+    def run(eng, t):
+        import test_icp_state_gpu as m
+
+        P, nrm, S, Q = m.case()
+        eng.build(P)
+        return m.icp(eng, method, nrm, S)
+
+    def check(t, f):
+        assert f["counts"][2] >= 2 and f["counts"][0] > 1000 and f["corr"][5] == -1, "that file's: several iterations, pairs, no partner for the NaN"
+    return run, check
+
+
+def _global_calls(prefix):
+    """tests/test_global_state_gpu.py runs the two calls together, on an engine without a tree: the outputs of one of them."""
+    def run(eng, t):
+        import test_global_state_gpu as m
+
+        return {k: v for k, v in m.both(eng).items() if k.startswith(prefix)}
+
+    def check(t, f):
+        import global_spec as gs
+        import test_global_state_gpu as m
+
+        A, B, scene = m.cases()
+        if prefix == "match.":
+            best, b1, b2 = gs.match(A, B)
+            assert np.array_equal(f["match.best"], best) and np.array_equal(f["match.best_d2"], b1.view(np.int32))
+        else:
+            tr = gs.scene_trials(3)[1]  # tests/test_ransac_gpu.py: the statuses are the spec's, but for the trials it leaves open
+            held = np.flatnonzero(~tr["excluded"])
+            assert np.array_equal(f["ransac.trial_status"][:gs.TRIALS][held], tr["status"][held])
+            assert f["ransac.mask"].sum() == f["ransac.info"][1] > 0
+    return run, check
+
+
 # ---- the table ---------------------------------------------------------------------------------------------------------------------
 class Scenario:
-    def __init__(self, name, call, fns, fallback=None, trees=("n1025", "n17ids", "nan700"), applies=None, bare=False):
+    def __init__(self, name, call, fns, fallback=None, trees=("n1025", "n17ids", "nan700"), applies=None, bare=False, by_spec=(), k=None):
+        """by_spec: the float outputs that the family's own file does not compare bit for bit but holds to the spec (the check).
+        k: the row width, where the scenario was made for one (the guarded test's account of what it ran)."""
         self.name, self.call, (self.run, self.check), self.fallback, self.trees, self.bare = name, call, fns, fallback, trees, bare
-        self._applies = applies
+        self._applies, self.by_spec, self.k = applies, tuple(by_spec), k
 
     def applies(self, t):
         return self._applies is None or bool(self._applies(t))
@@ -681,9 +860,62 @@ TABLE = (
     Scenario("local_pca_k", "local_pca", _pca((None, 16), True), "TKNN_PCA_FORCE_FALLBACK"),
     Scenario("local_pca_both", "local_pca", _pca((True, 16), False), "TKNN_PCA_FORCE_FALLBACK"),
     Scenario("halo_select", "halo_select", _halo_select()),
-    Scenario("halo_select_fixed", "halo_select", _halo_select_fixed()),
+    Scenario("halo_select_fixed", "halo_select_fixed", _halo_select_fixed()),
     Scenario("halo_phases", "halo_phases", _phases(), trees=PLAIN, applies=lambda t: _solvable(t) and t["batch"] is None),
     Scenario("halo_phases_poisoned_between", "halo_phases", _phases(True), trees=PLAIN, applies=lambda t: _solvable(t) and t["batch"] is None),
 )
 BY_NAME = {s.name: s for s in TABLE}
 assert len(BY_NAME) == len(TABLE)
+
+# ---- what only the guarded-output test reads -------------------------------------------------------------------------------------------
+QUERY_COUNTS = (1, 63, 65)  # of n1025's 96 queries: one, one short of a wave, one more than a wave
+TAKES_QUERIES = ("query", "dbscan_query", "radius_query_sorted", "radius_query_unsorted", "radius_knn", "knn", "periodic_knn", "batch_knn",
+                 "radius_reduce_gauss5", "local_pca_radius", "local_pca_both")
+
+
+def query_trees(s):
+    """The query-count variants the scenario also runs on: those of n1025 (of the batched tree for batch_knn), if it takes queries."""
+    if s.name not in TAKES_QUERIES:
+        return ()
+    return tuple("%sq%d" % ("n1025b3" if s.call == "batch_knn" else "n1025", m) for m in QUERY_COUNTS)
+
+
+ROW_KS = (1, 16, 17, 64)  # the register lists' capacities and their borders: where a list wider than the row is written out
+OWN = ("own",)
+MS_FALLBACK, FPFH_FALLBACK, ICP_FALLBACK = "TKNN_MEANSHIFT_FORCE_FALLBACK", "TKNN_FPFH_FORCE_FALLBACK", "TKNN_ICP_FORCE_FALLBACK"
+
+
+def _at_every_k():
+    out = []
+    for k in ROW_KS:
+        own, asked = dict(trees=("n1025",), k=k), dict(trees=("n1025q65",), k=k)
+        out += [Scenario("solve_lane_k%d" % k, "solve", _solve(_lib.KERNEL_LANE, k=k), applies=_solvable, **own),
+                Scenario("solve_wave_k%d" % k, "solve", _solve(_lib.KERNEL_WAVE, k=k), applies=_solvable, **own),
+                Scenario("solve_team_k%d" % k, "solve", _solve(_lib.KERNEL_TEAM, k=k), applies=_solvable, **own),
+                Scenario("query_k%d" % k, "query", _query(k), "TKNN_QUERY_FORCE_FALLBACK", **asked),
+                Scenario("radius_knn_k%d" % k, "radius_knn", _radius_knn(k), RKNN, **asked),
+                Scenario("knn_k%d" % k, "knn", _knn(False, k), "TKNN_KNN_FORCE_FALLBACK", **asked),
+                Scenario("knn_own_k%d" % k, "knn", _knn(True, k), "TKNN_KNN_FORCE_FALLBACK", **own),
+                Scenario("periodic_knn_k%d" % k, "periodic_knn", _periodic_knn(k), "TKNN_PERIODIC_KNN_FORCE_FALLBACK", **asked),
+                Scenario("batch_knn_k%d" % k, "batch_knn", _batch_knn(k), "TKNN_BATCH_KNN_FORCE_FALLBACK", trees=("n1025b3q65",), k=k),
+                Scenario("local_pca_k%d" % k, "local_pca", _pca((None, 16), False, k=k), "TKNN_PCA_FORCE_FALLBACK", **asked)]
+    return out
+
+
+GUARDED_ONLY = tuple(_at_every_k()) + (
+    Scenario("batch_layout", "batch_layout", _batch_layout(), trees=("n1025b3",)),
+    Scenario("solve_unfinished", "solve", _solve_unfinished(), trees=PLAIN, applies=_solvable),
+    Scenario("query_unfinished", "query", _query_unfinished(), "TKNN_QUERY_FORCE_FALLBACK", trees=("n1025", "nan700")),  # (of n17ids no query is served in two rounds)
+    Scenario("mean_shift_modes_flat", "mean_shift_modes", _mean_shift_modes("flat"), MS_FALLBACK, trees=OWN, bare=True),
+    Scenario("mean_shift_modes_gauss", "mean_shift_modes", _mean_shift_modes("gauss"), MS_FALLBACK, trees=OWN, bare=True),
+    Scenario("mean_shift_modes_own", "mean_shift_modes", _mean_shift_modes("flat", own=True), MS_FALLBACK, trees=OWN, bare=True),
+    Scenario("mean_shift", "mean_shift", _mean_shift(), MS_FALLBACK, trees=OWN, bare=True),
+    Scenario("fpfh", "fpfh", _fpfh(), FPFH_FALLBACK, trees=OWN, bare=True, by_spec=FPFH_BY_SPEC),
+    Scenario("icp_point_to_point", "icp", _icp("point_to_point"), ICP_FALLBACK, trees=OWN, bare=True),
+    Scenario("icp_point_to_plane", "icp", _icp("point_to_plane"), ICP_FALLBACK, trees=OWN, bare=True),
+    Scenario("match_features", "match_features", _global_calls("match."), trees=OWN, bare=True),
+    Scenario("ransac", "ransac", _global_calls("ransac."), trees=OWN, bare=True),
+)
+GUARDED = TABLE + GUARDED_ONLY
+GUARDED_BY_NAME = {s.name: s for s in GUARDED}
+assert len(GUARDED_BY_NAME) == len(GUARDED)
