@@ -21,6 +21,14 @@ def radius_nms(points, radius, scores=None, batch=None, **kw):
     return _radius_nms(points, radius, scores=scores, batch=batch, **kw)
 
 
+def voxel_down_sample(points, voxel_size, **kw):
+    """Voxel-grid downsampling per cloud: one point per occupied grid cell -- centroid, first row, nearest row or cell centre --,
+    values averaged with it (trueknn.voxel_down_sample; loads the library)."""
+    from .trueknn import voxel_down_sample as _voxel_down_sample
+
+    return _voxel_down_sample(points, voxel_size, **kw)
+
+
 def radius_reduce(points, queries, radius, **kw):
     """Counts, kernel-weight sums and weighted value sums over the points within ``radius`` of each query, no neighbour lists
     written (trueknn.radius_reduce; loads the library)."""

@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_voxel.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -561,6 +561,25 @@ int tknnRansac(tknnEngine e, const tknnRansacOptions *options, tknnRansacInfo *i
     c.count(o.c, "c");
     c.require(o.flags == 0u, "flags has a bit no flag of this call has");
     e->impl.ransac(o, info, (hipStream_t)stream);  // (refuses a pair row out of range itself, and writes info at its end only)
+  });
+}
+
+int tknnVoxelGrid(tknnEngine e, const tknnVoxelGridOptions *options, tknnVoxelGridInfo *info, void *stream) {
+  return api("tknnVoxelGrid", e, stream, [&](const Call &c) {
+    const tknnVoxelGridOptions &o = c.record(options);
+    c.need(info, "info");
+    if (o.n > 0) c.need(o.d_points, "d_points");
+    if (o.channels > 0) c.need(o.d_values, "d_values (channels > 0)");
+    c.require(!(o.d_value_mean && o.channels == 0), "d_value_mean is given with channels = 0");
+    c.count(o.n, "n");
+    c.positive(o.voxel, "voxel");
+    c.require(std::isfinite(o.origin[0]) && std::isfinite(o.origin[1]) && std::isfinite(o.origin[2]), "origin must be finite");
+    c.require(o.num_batches >= 1 && o.num_batches <= TKNN_MAX_BATCHES, "num_batches must be 1 .. 32768");
+    c.require(o.d_batch || o.num_batches == 1, "num_batches must be 1 without d_batch");
+    c.require(o.channels >= 0 && o.channels <= TKNN_VOXEL_MAX_CHANNELS, "channels must be 0 .. 16");
+    c.count(o.capacity, "capacity");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    e->impl.voxel_grid(o, info, (hipStream_t)stream);  // (refuses voxels beyond the capacity itself, and writes info at its end only)
   });
 }
 

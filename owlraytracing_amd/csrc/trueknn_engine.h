@@ -23,6 +23,7 @@
 #include "owlknn_pca.h"
 #include "owlknn_periodic.h"
 #include "owlknn_reduce.h"
+#include "owlknn_voxel.h"
 
 namespace owlmi {
 
@@ -211,6 +212,10 @@ class Engine {
   // against every record, stop by confidence, refit -- (tknnRansac); needs no tree.  An ArgError of TKNN_E_ARG, with nothing the
   // caller can see written, when a pair names a row out of range
   void ransac(const tknnRansacOptions &o, tknnRansacInfo *info, hipStream_t s);
+  // voxel_grid.hip: one point per occupied grid cell of every cloud -- a cell key per row, a stable radix sort, head flags and a
+  // scan, fp64 sums per voxel by a lane or by a wave -- (tknnVoxelGrid); needs no tree.  An ArgError of TKNN_E_ARG, with nothing
+  // the caller can see written, when the voxels outnumber the capacity
+  void voxel_grid(const tknnVoxelGridOptions &o, tknnVoxelGridInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

@@ -10,10 +10,20 @@ import ctypes
 import numpy as np
 
 from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _global_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
-               _reduce_lib)
+               _reduce_lib, _voxel_lib)
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
+
+
+def _voxel_outputs(torch, device, wanted):
+    """The outputs of one tknnVoxelGrid call: {name: an uninitialised tensor} for ``wanted`` = {name: (shape, dtype)}, and "spare",
+    the address an empty one stands for.  ``torch`` is the engine's handle (TrueKNN._torch), so what stands in for it in the
+    tests -- tests/guarded_outputs.py -- sees every one of them (tests/test_voxel_gpu.py runs the wrapper under it)."""
+    out = {name: torch.empty(shape, dtype=dtype, device=device) for name, (shape, dtype) in wanted.items()}
+    spare = torch.empty((4,), dtype=torch.int32, device=device)
+    out["spare"] = spare
+    return out
 
 
 def _address(t, spare=None):
@@ -1253,6 +1263,106 @@ class TrueKNN:
             res["trial_status"], res["trial_inliers"] = status, inliers
         return res
 
+    def voxel_down_sample(self, points, voxel_size, batch=None, values=None, origin=None, reduce="mean", want_map=False, want_cells=False,
+                          max_voxels=None, num_batches=None):
+        """One point per occupied cell of a grid of edge ``voxel_size``, inside each cloud (tknnVoxelGrid; no tree is needed, and a
+        built one is left alone): Open3D's ``voxel_down_sample``, PCL's ``VoxelGrid``, torch-cluster's ``grid_cluster`` followed by
+        ``avg_pool``.  ``points``: numpy (n,2|3) or a contiguous float32 (n,3) tensor on the engine's device.  The cell of a row is
+        floorf((p - origin) / voxel_size) per axis in fp32; a row with a coordinate that is not finite, with a label outside
+        [0, num_batches) or with a cell outside [0, 2^21) is left out.  ``batch``: (n,) int32 labels in any order, no voxel spans
+        two clouds (``num_batches`` defaults to the largest label + 1).  ``values``: (n, C) float32, C <= 16, reduced with the
+        points.  ``origin``: the grid's corner; None: the minimum of the finite points minus ``voxel_size / 2`` (Open3D's).
+        ``reduce``: "mean" -- the fp64 centroid of the cell's rows and the mean of their values, rounded once; "first" -- the cell's
+        smallest row; "nearest" -- its row nearest to the centroid, ties to the smaller row; "center" -- origin + (cell + 0.5) *
+        voxel_size, the values averaged.  Voxels are ordered by (label, cx, cy, cz), whatever the order of the rows.
+        ``max_voxels``: the capacity of the outputs (more voxels: the call is refused); None: n, and views of the first V rows come
+        back -- one call, one sort.
+        Returns dict(points (V,3) float32, counts (V,) int32, offsets (num_batches + 1,) int64: the voxels of each cloud, info
+        [, values (V,C); rows (V,) int32, the rows kept, for "first" and "nearest"; batch (V,) int32 with ``batch``; map (n,) int32,
+        the voxel of each row, -1 for a row left out, ``want_map``; cells (V,3) int32, ``want_cells``]), tensors on the device."""
+        torch = self._torch
+        if reduce not in ("mean", "first", "nearest", "center"):
+            raise ValueError('voxel_down_sample: reduce must be "mean", "first", "nearest" or "center"')
+        if not float(voxel_size) > 0 or not np.isfinite(np.float32(voxel_size)):
+            raise ValueError("voxel_down_sample: voxel_size must be finite and > 0")
+        points = self._queries(points, "voxel_down_sample")
+        n = int(points.shape[0])
+        with torch.cuda.device(self.device):
+            B = 1
+            if batch is not None:
+                batch = self._labels(batch, n, "voxel_down_sample", "batch", "point")
+                B = int(num_batches) if num_batches is not None else (int(batch.max()) + 1 if n > 0 else 1)
+                B = max(B, 1)  # (a negative label is left out by the library)
+            elif num_batches is not None:
+                raise ValueError("voxel_down_sample: num_batches goes with batch")
+            C = 0
+            if values is not None:
+                values = self._features(values, "voxel_down_sample", "values")
+                C = int(values.shape[1])
+                if values.shape[0] != n or C < 1 or C > _voxel_lib.VOXEL_MAX_CHANNELS:
+                    raise ValueError("voxel_down_sample: values must be (n, C) with 1 <= C <= %d" % _voxel_lib.VOXEL_MAX_CHANNELS)
+            voxel = torch.tensor(float(voxel_size), dtype=torch.float32, device=self.device)
+            if origin is None:
+                finite = torch.isfinite(points).all(dim=1, keepdim=True)
+                if n > 0 and bool(finite.any()):
+                    lo = torch.where(finite, points, torch.full_like(points, float("inf"))).min(dim=0).values
+                    origin = (lo - voxel / 2).tolist()
+                else:
+                    origin = [0.0, 0.0, 0.0]
+            origin = [float(np.float32(x)) for x in origin]
+            if len(origin) != 3:
+                raise ValueError("voxel_down_sample: origin must have three entries")
+            cap = n if max_voxels is None else int(max_voxels)
+            mean = reduce in ("mean", "center")
+
+            wanted = {"counts": ((cap,), torch.int32), "offsets": ((B + 1,), torch.int64)}
+            if reduce == "mean":
+                wanted["centroid"] = ((cap, 3), torch.float32)
+            if want_cells or reduce == "center":
+                wanted["cells"] = ((cap, 3), torch.int32)
+            if C > 0 and mean:
+                wanted["value_mean"] = ((cap, C), torch.float32)
+            if not mean:
+                wanted["rows"] = ((cap,), torch.int32)
+            if batch is not None:
+                wanted["labels"] = ((cap,), torch.int32)
+            if want_map:
+                wanted["map"] = ((n,), torch.int32)
+            bufs = _voxel_outputs(torch, self.device, wanted)
+            counts, centroid, cells, value_mean, rows = (bufs.get(k) for k in ("counts", "centroid", "cells", "value_mean", "rows"))
+            labels, offsets, vmap, spare = (bufs.get(k) for k in ("labels", "offsets", "map", "spare"))
+            opt = _voxel_lib.VoxelGridOptions()
+            opt.n, opt.d_points, opt.d_batch, opt.d_values = n, _address(points, spare), _address(batch, spare), _address(values, spare)
+            opt.voxel, opt.num_batches, opt.channels, opt.capacity = float(voxel_size), B, C, cap
+            for axis in range(3):
+                opt.origin[axis] = origin[axis]
+            opt.d_count, opt.d_centroid, opt.d_cell, opt.d_value_mean = _address(counts, spare), _address(centroid, spare), _address(cells, spare), _address(value_mean, spare)
+            opt.d_first = _address(rows, spare) if reduce == "first" else None
+            opt.d_nearest = _address(rows, spare) if reduce == "nearest" else None
+            opt.d_voxel_label, opt.d_offsets, opt.d_map = _address(labels, spare), _address(offsets, spare), _address(vmap, spare)
+            info = _voxel_lib.VoxelGridInfo()
+            _lib.check(_voxel_lib.load().tknnVoxelGrid(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+            res = info.as_dict()
+            V = int(info.voxels)
+            if reduce == "mean":
+                pts = centroid[:V]
+            elif reduce == "center":
+                pts = torch.tensor(origin, dtype=torch.float32, device=self.device) + (cells[:V].to(torch.float32) + 0.5) * voxel
+            else:
+                pts = points[rows[:V].long()]
+            result = {"points": pts, "counts": counts[:V], "offsets": offsets, "info": res}
+            if C > 0:
+                result["values"] = value_mean[:V] if mean else values[rows[:V].long()]
+            if not mean:
+                result["rows"] = rows[:V]
+            if batch is not None:
+                result["batch"] = labels[:V]
+            if want_map:
+                result["map"] = vmap
+            if want_cells:
+                result["cells"] = cells[:V]
+        return result
+
     def mean_shift_modes(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300):
         """Mean-shift trajectories over the built set, the loop inside the library (tknnMeanShift): every seed moves to the
         kernel-weighted mean of the built points within ``radius`` of it (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius; the sums
@@ -1644,8 +1754,14 @@ def ransac(source, target, pairs, max_dist, **kw):
     return _treeless(lambda eng: eng.ransac(np.asarray(source, dtype=np.float32), np.asarray(target, dtype=np.float32), np.asarray(pairs), max_dist, **kw))
 
 
+def voxel_down_sample(points, voxel_size, **kw):
+    """One-shot helper: one point per occupied grid cell of edge ``voxel_size``, per cloud of the labels ``batch`` where given
+    (TrueKNN.voxel_down_sample), results as numpy arrays.  No tree is built."""
+    return _treeless(lambda eng: eng.voxel_down_sample(pad_to_3d(np.asarray(points, np.float32)), voxel_size, **kw))
+
+
 def global_registration(target, source, feature_radius, max_dist, normal_k=16, mutual=True, icp=True, target_viewpoint=None, source_viewpoint=None,
-                        **kw):
+                        voxel_size=None, **kw):
     """Registration of two unaligned clouds, on the device from end to end: an engine per cloud, ``fpfh(feature_radius,
     normal_k=normal_k)`` on both, ``match_features(mutual=mutual)``, ``ransac(max_dist, **kw)`` and, with ``icp``,
     ``icp(max_dist, init=...)`` on the target's engine.  An FPFH is not invariant under a flip of the normals, and a normal
@@ -1653,8 +1769,13 @@ def global_registration(target, source, feature_radius, max_dist, normal_k=16, m
     position it was seen from (``target_viewpoint``, ``source_viewpoint``, each in its own frame) and its normals are turned
     towards it (``normals(k=normal_k, viewpoint=...)``) before the FPFH.  Returns dict(ransac, ransac_eval, pairs (c,2) numpy,
     match_info[, icp, icp_eval], transform): the results of the calls, and ``evaluate_registration`` of each transform on the full
-    clouds; transform: ICP's with ``icp``, else RANSAC's."""
+    clouds; transform: ICP's with ``icp``, else RANSAC's.
+    ``voxel_size``: both clouds are first reduced to the centroids of a voxel grid of that edge (``voxel_down_sample``); normals,
+    FPFH, matching and RANSAC run on those -- ``pairs`` then names their rows, and ``target_down``, ``source_down`` are the
+    numbers of points left --, ICP and both evaluations on the full clouds.  None: nothing is reduced."""
     et, es = TrueKNN(), TrueKNN()
+    if voxel_size is not None:
+        ed, esd = TrueKNN(), TrueKNN()  # the engines of the reduced clouds; et holds the full target for ICP and the evaluations
 
     def describe(eng, viewpoint):
         if viewpoint is None:
@@ -1663,13 +1784,23 @@ def global_registration(target, source, feature_radius, max_dist, normal_k=16, m
 
     try:
         et.build(target)
-        es.build(source)
-        ft, fs = describe(et, target_viewpoint), describe(es, source_viewpoint)
-        match = es.match_features(fs, ft, mutual=mutual)
         src, tgt = es._queries(source, "global_registration"), et._queries(target, "global_registration")
-        rs = es.ransac(src, tgt, match["pairs"], max_dist, **kw)
+        if voxel_size is None:
+            es.build(source)
+            ft, fs = describe(et, target_viewpoint), describe(es, source_viewpoint)
+            src_few, tgt_few = src, tgt
+        else:
+            tgt_few = ed.voxel_down_sample(tgt, voxel_size)["points"].contiguous()
+            src_few = esd.voxel_down_sample(src, voxel_size)["points"].contiguous()
+            ed.build(tgt_few)
+            esd.build(src_few)
+            ft, fs = describe(ed, target_viewpoint), describe(esd, source_viewpoint)
+        match = es.match_features(fs, ft, mutual=mutual)
+        rs = es.ransac(src_few, tgt_few, match["pairs"], max_dist, **kw)
         out = {"ransac": rs, "pairs": match["pairs"].cpu().numpy(), "match_info": match["info"], "transform": rs["transform"],
                "ransac_eval": et.evaluate_registration(src, max_dist, init=rs["transform"])}
+        if voxel_size is not None:
+            out["target_down"], out["source_down"] = int(tgt_few.shape[0]), int(src_few.shape[0])
         if icp:
             out["icp"] = et.icp(src, max_dist, init=rs["transform"])
             out["transform"] = out["icp"]["transform"]
@@ -1678,6 +1809,9 @@ def global_registration(target, source, feature_radius, max_dist, normal_k=16, m
     finally:
         et.close()
         es.close()
+        if voxel_size is not None:
+            ed.close()
+            esd.close()
 
 
 def bin_seeds(points, bin_size, min_bin_freq=1):
