@@ -248,17 +248,19 @@ def check(rc):
 # only the C ABI's argument checks and messages (tknn_api.hip, which holds no kernel) change
 _NOT_TEAM = ("dbscan.hip", "dbscan_core.hip", "dbscan_union.hip", "dbscan_label.hip", "db_device.h", "db_call.h", "halo_select.hip", "radius_query.hip", "radius_walk.h",
              "radius_knn.hip", "radius_knn_walk.h", "knn_seed.hip", "owlknn_knn.h", "periodic_knn.hip", "periodic_metric.h", "owlknn_periodic.h", "batch_knn.hip", "owlknn_batch.h",
-             "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp")
+             "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp",
+             "debug_lanes.hip")  # (the lane harness of tknnDebugTeamLanes: kernels of its own around the shared headers)
 # RT-DBSCAN's kernels are in three files by pass; dbscan.hip, the host side that decides their grids and arguments, counts for all
 _NOT_DB = ("trueknn_team.hip", "trueknn_tail.hip", "trueknn_bigk.hip", "trueknn_wave.hip", "halo_select.hip", "radius_query.hip", "radius_walk.h", "radius_knn.hip",
            "radius_knn_walk.h", "knn_seed.hip", "owlknn_knn.h", "periodic_knn.hip", "periodic_metric.h", "owlknn_periodic.h", "batch_knn.hip",
-           "owlknn_batch.h", "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp")
+           "owlknn_batch.h", "emst.hip", "owlknn_emst.h", "linkage.hip", "linkage.h", "hdbscan.hip", "owlknn_hdbscan.h", "tknn_api.hip", "owl_runtime.cpp",
+           "debug_lanes.hip", "bigk_keys.h")
 _NOT_DB_CORE, _NOT_DB_UNION = _NOT_DB + ("dbscan_union.hip", "dbscan_label.hip"), _NOT_DB + ("dbscan_core.hip", "dbscan_label.hip")
 _NOT_IN = {
-    "team_walk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),  # trueknn_tail.hip
-    "tie_fix_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip"),
+    "team_walk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip", "bigk_keys.h"),  # trueknn_tail.hip
+    "tie_fix_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_bigk.hip", "bigk_keys.h"),
     "bigk_": _NOT_TEAM + ("trueknn_team.hip", "trueknn_tail.hip"),  # trueknn_bigk.hip
-    "team_": _NOT_TEAM + ("trueknn_tail.hip", "trueknn_bigk.hip"),  # trueknn_team.hip: team_kernel, team_prep_kernel
+    "team_": _NOT_TEAM + ("trueknn_tail.hip", "trueknn_bigk.hip", "bigk_keys.h"),  # trueknn_team.hip: team_kernel, team_prep_kernel
     "db_core_": _NOT_DB_CORE,  # dbscan_core.hip: db_core_kernel, db_core_pos_blocks_kernel, db_core_from_labels_kernel
     "db_flag_count_": _NOT_DB_CORE,
     "db_next_core_": _NOT_DB_CORE,

@@ -771,4 +771,17 @@ int tknnDebugThresholds(const float *d_q, const float *d_r, int64_t n, float *d_
   });
 }
 
+int tknnDebugTeamLanes(int op, int variant, const uint32_t *d_in, uint32_t *d_out, int64_t teams, void *stream) {
+  return guarded([&] {
+    const Call c{"tknnDebugTeamLanes", nullptr};
+    c.need(d_in, "d_in"), c.need(d_out, "d_out");
+    c.require(teams >= 0 && teams <= TKNN_LANES_MAX_TEAMS, "need 0 <= teams <= 2^20");
+    c.require(op >= 0 && op < TKNN_LANES_OPS, "no such op");
+    c.require(owlmi::debug_team_lanes_words(op, variant, nullptr, nullptr), "the op has no such variant");
+    if (teams == 0) return;
+    owlmi::debug_team_lanes(op, variant, d_in, d_out, teams, (hipStream_t)stream);
+    OWLMI_HIP(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+
 }  // extern "C"

@@ -117,6 +117,11 @@ void db_segment_min(const int32_t *d_seg, const int64_t *d_val, int64_t n, int64
 // test hook: the wave kernel's exact candidate thresholds for (q, r) pairs (trueknn_wave.hip)
 void debug_thresholds(const float *d_q, const float *d_r, int64_t n, float *d_lo, float *d_hi, hipStream_t s);
 
+// test hook (tknnDebugTeamLanes, include/owlknn_debug.h): one team helper on caller-supplied lanes (debug_lanes.hip).  The words
+// per lane that `op` with `variant` takes and returns, false if the op has no such variant or there is no such op
+bool debug_team_lanes_words(int op, int variant, int *win, int *wout);
+void debug_team_lanes(int op, int variant, const uint32_t *d_in, uint32_t *d_out, int64_t teams, hipStream_t s);
+
 class Engine {
  public:
   Engine();
