@@ -53,6 +53,14 @@ def fpfh(points, radius, normals=None, **kw):
     return _fpfh(points, radius, normals=normals, **kw)
 
 
+def orient_normals(points, normals, **kw):
+    """One consistent sign per normal with no viewpoint: Hoppe's propagation along the minimum spanning tree of the kNN graph weighted
+    by 1 - |n_i . n_j|, Open3D's ``orient_normals_consistent_tangent_plane`` (trueknn.orient_normals; loads the library)."""
+    from .trueknn import orient_normals as _orient_normals
+
+    return _orient_normals(points, normals, **kw)
+
+
 def icp(target, source, max_dist, **kw):
     """Rigid registration of ``source`` to ``target`` by iterated closest points, point-to-point or point-to-plane, the loop and
     its fp64 sums inside the library (trueknn.icp; loads the library)."""

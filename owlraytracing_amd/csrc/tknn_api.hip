@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_voxel.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_voxel.h, include/owlknn_orient.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -614,6 +614,22 @@ int tknnEmst(tknnEngine e, const tknnEmstOptions *options, tknnEmstInfo *info, v
     e->impl.emst(o, info, (hipStream_t)stream);
   });
   if (rc == TKNN_E_ROUNDS) g_last_error = "tknnEmst: max_rounds reached with components still merging (nothing was written)";
+  return rc;
+}
+
+int tknnOrientNormals(tknnEngine e, const tknnOrientOptions *options, tknnOrientInfo *info, void *stream) {
+  const int rc = api("tknnOrientNormals", e, stream, [&](const Call &c) {
+    const tknnOrientOptions &o = c.record(options);
+    c.require(o.d_out_normals || o.d_flip, "no output: give d_out_normals or d_flip");
+    c.need(o.d_normals, "d_normals");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    c.k_up_to(o.k, TKNN_MAX_K_REGISTERS, TKNN_E_ARG);
+    c.require((o.flags & ~TKNN_ORIENT_NO_EMST) == 0u, "flags has a bit no flag of this call has");
+    c.require(std::isfinite(o.direction[0]) && std::isfinite(o.direction[1]) && std::isfinite(o.direction[2]), "direction must be finite");
+    if (e->impl.size() * ((int64_t)o.k + 1) >= (1ll << 31)) c.refuse(TKNN_E_UNSUPPORTED, "need n * (k + 1) < 2^31");
+    e->impl.orient_normals(o, info, (hipStream_t)stream);  // (writes info at its end only)
+  });
+  if (rc == TKNN_E_ROUNDS) g_last_error = "tknnOrientNormals: max_rounds reached with components still merging (nothing was written)";
   return rc;
 }
 

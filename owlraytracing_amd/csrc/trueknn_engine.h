@@ -20,6 +20,7 @@
 #include "owlknn_knn.h"
 #include "owlknn_meanshift.h"
 #include "owlknn_nms.h"
+#include "owlknn_orient.h"
 #include "owlknn_pca.h"
 #include "owlknn_periodic.h"
 #include "owlknn_reduce.h"
@@ -221,6 +222,11 @@ class Engine {
   // scan, fp64 sums per voxel by a lane or by a wave -- (tknnVoxelGrid); needs no tree.  An ArgError of TKNN_E_ARG, with nothing
   // the caller can see written, when the voxels outnumber the capacity
   void voxel_grid(const tknnVoxelGridOptions &o, tknnVoxelGridInfo *info, hipStream_t s);
+  // orient.hip: one sign per normal, agreed along the minimum spanning forest of the kNN graph (and the EMST's records) weighted
+  // by 1 - |n_i . n_j| -- knn and emst, one sort of the candidates by the strict key, Boruvka rounds over the ranked list with the
+  // sign parity carried through the merges -- (tknnOrientNormals); the tree a point tree.  Throws RoundsExceeded, with nothing
+  // written, info included, when max_rounds rounds do not finish it
+  void orient_normals(const tknnOrientOptions &o, tknnOrientInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

@@ -9,17 +9,18 @@ import ctypes
 
 import numpy as np
 
-from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _global_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _pca_lib, _periodic_lib,
+from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _global_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _orient_lib, _pca_lib, _periodic_lib,
                _reduce_lib, _voxel_lib)
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
 
 
-def _voxel_outputs(torch, device, wanted):
-    """The outputs of one tknnVoxelGrid call: {name: an uninitialised tensor} for ``wanted`` = {name: (shape, dtype)}, and "spare",
-    the address an empty one stands for.  ``torch`` is the engine's handle (TrueKNN._torch), so what stands in for it in the
-    tests -- tests/guarded_outputs.py -- sees every one of them (tests/test_voxel_gpu.py runs the wrapper under it)."""
+def _call_outputs(torch, device, wanted):
+    """The outputs of one tknnVoxelGrid or tknnOrientNormals call: {name: an uninitialised tensor} for ``wanted`` = {name: (shape,
+    dtype)}, and "spare", the address an empty one stands for.  ``torch`` is the engine's handle (TrueKNN._torch), so what stands in
+    for it in the tests -- tests/guarded_outputs.py -- sees every one of them (tests/test_voxel_gpu.py and tests/test_orient_gpu.py
+    run the wrappers under it)."""
     out = {name: torch.empty(shape, dtype=dtype, device=device) for name, (shape, dtype) in wanted.items()}
     spare = torch.empty((4,), dtype=torch.int32, device=device)
     out["spare"] = spare
@@ -1328,7 +1329,7 @@ class TrueKNN:
                 wanted["labels"] = ((cap,), torch.int32)
             if want_map:
                 wanted["map"] = ((n,), torch.int32)
-            bufs = _voxel_outputs(torch, self.device, wanted)
+            bufs = _call_outputs(torch, self.device, wanted)
             counts, centroid, cells, value_mean, rows = (bufs.get(k) for k in ("counts", "centroid", "cells", "value_mean", "rows"))
             labels, offsets, vmap, spare = (bufs.get(k) for k in ("labels", "offsets", "map", "spare"))
             opt = _voxel_lib.VoxelGridOptions()
@@ -1362,6 +1363,70 @@ class TrueKNN:
             if want_cells:
                 result["cells"] = cells[:V]
         return result
+
+    def orient_normals(self, normals, k=16, direction=(0, 0, 1), emst=True, want=("normals", "flip"), in_place=False, max_rounds=0):
+        """One consistent sign per normal of the built set, with no viewpoint (tknnOrientNormals): Hoppe's propagation, Open3D's
+        ``orient_normals_consistent_tangent_plane(k)``.  The graph joins every point to its ``k`` nearest others (``knn``'s own rows)
+        and, with ``emst``, by the records of the Euclidean ``emst``, so that it is connected wherever that forest is; an edge weighs
+        1 - |n_i . n_j| in fp32, edges are ordered by (bits of the weight, smaller name, larger name), and along the unique minimum
+        spanning forest under that order every normal is flipped to agree with its tree parent.  The root of a component is its point
+        farthest along ``direction`` (the smallest row among equals), flipped iff its normal points against it.  ``normals``: (n,3)
+        float32 by the caller's row, numpy or a tensor on the engine's device, read as given; a point with a NaN coordinate or a normal
+        that is not finite takes no part and keeps its normal.  The result does not depend on the signs of the input.
+        ``want``: any of "normals", "flip", "components", "tree"; ``in_place`` writes the normals over ``normals`` (a contiguous
+        float32 tensor on the engine's device) and returns that tensor.  Returns dict(normals (n,3) float32, flip (n,) uint8,
+        components (n,) int32: the smallest row of the point's component of the graph, -1 for a point left out, u, v (tree_edges,)
+        int32 with u < v and w (tree_edges,) float32: the forest's records ascending by the key, info)."""
+        torch = self._torch
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - {"normals", "flip", "components", "tree"}
+        if unknown:
+            raise ValueError("orient_normals: want has %s; it takes normals, flip, components, tree" % sorted(unknown))
+        if in_place and "normals" not in want:
+            raise ValueError('orient_normals: in_place goes with "normals" in want')
+        if "normals" not in want and "flip" not in want:
+            raise ValueError('orient_normals: want needs "normals" or "flip"')
+        direction = [float(np.float32(x)) for x in direction]
+        if len(direction) != 3:
+            raise ValueError("orient_normals: direction must have three entries")
+        n = self.n
+        with torch.cuda.device(self.device):
+            if in_place:
+                self._written_in_place("orient_normals", "normals", normals, (n, 3), torch.float32)
+            else:
+                if isinstance(normals, torch.Tensor) and normals.device != self.device:
+                    raise ValueError("orient_normals: normals are on %s, the engine on %s" % (normals.device, self.device))
+                normals = torch.as_tensor(normals, device=self.device).to(torch.float32).contiguous()
+                if normals.dim() != 2 or tuple(normals.shape) != (n, 3):
+                    raise ValueError("orient_normals: normals must be (n,3), one row per built point")
+            rows = max(n - 1, 0)
+            wanted = {}
+            if "normals" in want and not in_place:
+                wanted["normals"] = ((n, 3), torch.float32)
+            if "flip" in want:
+                wanted["flip"] = ((n,), torch.uint8)
+            if "components" in want:
+                wanted["components"] = ((n,), torch.int32)
+            if "tree" in want:
+                wanted.update({"u": ((rows,), torch.int32), "v": ((rows,), torch.int32), "w": ((rows,), torch.float32)})
+            out = _call_outputs(torch, self.device, wanted)
+            spare = out.pop("spare")
+            if in_place:
+                out["normals"] = normals
+            opt = _orient_lib.OrientOptions()
+            opt.d_normals = _address(normals, spare)
+            opt.k, opt.flags, opt.max_rounds = int(k), 0 if emst else _orient_lib.ORIENT_NO_EMST, int(max_rounds)
+            for axis in range(3):
+                opt.direction[axis] = direction[axis]
+            opt.d_out_normals, opt.d_flip, opt.d_component = _address(out.get("normals"), spare), _address(out.get("flip"), spare), _address(out.get("components"), spare)
+            opt.d_u, opt.d_v, opt.d_w = _address(out.get("u"), spare), _address(out.get("v"), spare), _address(out.get("w"), spare)
+            info = _orient_lib.OrientInfo()
+            _lib.check(_orient_lib.load().tknnOrientNormals(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        if "tree" in want:
+            edges = int(info.tree_edges)
+            out["u"], out["v"], out["w"] = out["u"][:edges], out["v"][:edges], out["w"][:edges]
+        out["info"] = info.as_dict()
+        return out
 
     def mean_shift_modes(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300):
         """Mean-shift trajectories over the built set, the loop inside the library (tknnMeanShift): every seed moves to the
@@ -1728,6 +1793,12 @@ def local_pca(points, queries, radius=None, k=None, ids=None, batch=None, **kw):
 def fpfh(points, radius, normals=None, **kw):
     """One-shot helper: build over ``points`` and describe every point by its FPFH as TrueKNN.fpfh does, results as numpy arrays."""
     return _one_shot(points, lambda eng: eng.fpfh(radius, normals=normals, **kw))
+
+
+def orient_normals(points, normals, **kw):
+    """One-shot helper: build over ``points``, one consistent sign per normal with no viewpoint (TrueKNN.orient_normals), results as
+    numpy arrays."""
+    return _one_shot(points, lambda eng: eng.orient_normals(normals, **kw))
 
 
 def icp(target, source, max_dist, **kw):
