@@ -61,6 +61,14 @@ def orient_normals(points, normals, **kw):
     return _orient_normals(points, normals, **kw)
 
 
+def segment_plane(points, distance_threshold, **kw):
+    """The dominant plane of a cloud by RANSAC on the device, every hypothesis scored through the box pyramid: Open3D's
+    ``segment_plane``, PCL's ``SACSegmentation`` with a plane model (trueknn.segment_plane; loads the library)."""
+    from .trueknn import segment_plane as _segment_plane
+
+    return _segment_plane(points, distance_threshold, **kw)
+
+
 def icp(target, source, max_dist, **kw):
     """Rigid registration of ``source`` to ``target`` by iterated closest points, point-to-point or point-to-plane, the loop and
     its fp64 sums inside the library (trueknn.icp; loads the library)."""

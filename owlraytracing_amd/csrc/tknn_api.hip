@@ -1,4 +1,4 @@
-// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_voxel.h, include/owlknn_orient.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
+// tknn_api.hip -- the C ABI of include/owlknn.h, include/owlknn_knn.h, include/owlknn_periodic.h, include/owlknn_batch.h, include/owlknn_emst.h, include/owlknn_fps.h, include/owlknn_nms.h, include/owlknn_reduce.h, include/owlknn_pca.h, include/owlknn_fpfh.h, include/owlknn_global.h, include/owlknn_voxel.h, include/owlknn_orient.h, include/owlknn_plane.h, include/owlknn_icp.h, include/owlknn_meanshift.h, include/owlknn_hdbscan.h and include/owlknn_debug.h and nothing else: every entry point checks its arguments and hands over to
 // the Engine (trueknn_engine.h).  No kernel is in here and none depends on this file.
 //
 // What every entry point keeps to: a NULL engine is refused before any device is touched; then the engine's device is made
@@ -631,6 +631,24 @@ int tknnOrientNormals(tknnEngine e, const tknnOrientOptions *options, tknnOrient
   });
   if (rc == TKNN_E_ROUNDS) g_last_error = "tknnOrientNormals: max_rounds reached with components still merging (nothing was written)";
   return rc;
+}
+
+int tknnSegmentPlane(tknnEngine e, const tknnPlaneOptions *options, tknnPlaneInfo *info, void *stream) {
+  return api("tknnSegmentPlane", e, stream, [&](const Call &c) {
+    const tknnPlaneOptions &o = c.record(options);
+    c.need(info, "info");
+    if (!e->impl.built() || !e->impl.tree().has_points()) c.refuse(TKNN_E_STATE, "call tknnBuild first (the engine has no point tree)");
+    if (e->impl.ids_given()) c.refuse(TKNN_E_UNSUPPORTED, "the tree was built with ids: a row is named by the caller's row, build with tknnBuild");
+    if (e->impl.size() > 0x7fffffffLL - 64) c.refuse(TKNN_E_UNSUPPORTED, "need n <= 2^31 - 65 (the slots, padded to whole blocks, are counted in 31 bits)");
+    c.positive(o.distance_threshold, "distance_threshold");
+    c.require(o.max_trials >= 1, "max_trials must be at least 1");
+    c.require(o.confidence > 0.0 && o.confidence <= 1.0, "confidence must be in (0, 1] (1: never stop early)");
+    c.require(o.refit_rounds >= 0 && o.refit_rounds <= 8, "refit_rounds must be 0 .. 8");
+    c.require(std::isfinite(o.axis[0]) && std::isfinite(o.axis[1]) && std::isfinite(o.axis[2]), "axis must be finite");
+    if (o.axis[0] != 0.f || o.axis[1] != 0.f || o.axis[2] != 0.f) c.require(o.min_cos > 0.f && o.min_cos <= 1.f, "min_cos must be in (0, 1] with an axis");
+    c.require(o.flags == 0u, "flags has a bit no flag of this call has");
+    e->impl.segment_plane(o, info, (hipStream_t)stream);  // (writes info at its end only)
+  });
 }
 
 // the forest of tknnLinkage and tknnHdbscanLabels

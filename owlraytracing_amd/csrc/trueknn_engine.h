@@ -23,6 +23,7 @@
 #include "owlknn_orient.h"
 #include "owlknn_pca.h"
 #include "owlknn_periodic.h"
+#include "owlknn_plane.h"
 #include "owlknn_reduce.h"
 #include "owlknn_voxel.h"
 
@@ -227,6 +228,11 @@ class Engine {
   // sign parity carried through the merges -- (tknnOrientNormals); the tree a point tree.  Throws RoundsExceeded, with nothing
   // written, info included, when max_rounds rounds do not finish it
   void orient_normals(const tknnOrientOptions &o, tknnOrientInfo *info, hipStream_t s);
+  // plane.hip: the plane most active rows of the built set lie within a distance of, by RANSAC in batches of trials -- the active
+  // list and its prefixes, a lane per trial for the planes, a wave per plane walking the box pyramid with the slab as its query (or
+  // sweeping every row: the fallback), stop by confidence, refit by the inliers' fp64 moments (plane_solve.h) -- (tknnSegmentPlane);
+  // the tree a point tree without ids
+  void segment_plane(const tknnPlaneOptions &o, tknnPlaneInfo *info, hipStream_t s);
   // The top of every call (tknn_api.hip): a DBSCAN call that threw between its side launch and its rejoin has left
   // db_border_walk_kernel running on the workspace and the counters; `s` waits for it before the call touches either.
   void join_side(hipStream_t s);

@@ -48,6 +48,19 @@ def gaussian_mixture3d(n, components=64, sigma=0.02, seed=1):
     return pts.astype(np.float32)
 
 
+def room3d(n, floor=0.4, wall=0.15, noise=0.002, seed=3):
+    """A scanned room in the unit cube: the floor z = 0 carries ``floor`` of the points, the walls x = 0 and y = 0 ``wall`` each, all
+    with Gaussian noise of ``noise`` across the surface, the rest is uniform clutter; rows shuffled.  The floor's mean point spacing
+    is 1 / sqrt(floor * n)."""
+    rng = np.random.default_rng(seed)
+    nf, nw = int(floor * n), int(wall * n)
+    pts = rng.random((n, 3))
+    pts[:nf, 2] = noise * rng.standard_normal(nf)
+    pts[nf:nf + nw, 0] = noise * rng.standard_normal(nw)
+    pts[nf + nw:nf + 2 * nw, 1] = noise * rng.standard_normal(nw)
+    return pts[rng.permutation(n)].astype(np.float32)
+
+
 def taxi_like2d(n, components=256, dup_fraction=0.05, seed=2):
     """C5: heavy-tailed 2-D mixture (log-normal sigmas) with exact duplicates; returned (n,2)."""
     rng = np.random.default_rng(seed)

@@ -10,14 +10,14 @@ import ctypes
 import numpy as np
 
 from . import (_batch_lib, _emst_lib, _fpfh_lib, _fps_lib, _global_lib, _hdbscan_lib, _icp_lib, _knn_lib, _lib, _meanshift_lib, _nms_lib, _orient_lib, _pca_lib, _periodic_lib,
-               _reduce_lib, _voxel_lib)
+               _plane_lib, _reduce_lib, _voxel_lib)
 from .datasets import pad_to_3d
 
 NEIGH_BYTES = 24  # GeomTypes.h:22-28
 
 
 def _call_outputs(torch, device, wanted):
-    """The outputs of one tknnVoxelGrid or tknnOrientNormals call: {name: an uninitialised tensor} for ``wanted`` = {name: (shape,
+    """The outputs of one tknnVoxelGrid, tknnOrientNormals or tknnSegmentPlane call: {name: an uninitialised tensor} for ``wanted`` = {name: (shape,
     dtype)}, and "spare", the address an empty one stands for.  ``torch`` is the engine's handle (TrueKNN._torch), so what stands in
     for it in the tests -- tests/guarded_outputs.py -- sees every one of them (tests/test_voxel_gpu.py and tests/test_orient_gpu.py
     run the wrappers under it)."""
@@ -1428,6 +1428,104 @@ class TrueKNN:
         out["info"] = info.as_dict()
         return out
 
+    def segment_plane(self, distance_threshold, num_iterations=1000, confidence=0.999, seed=0, active=None, axis=None, max_angle=None, refit_rounds=1,
+                      want=("plane", "inliers"), return_info=False):
+        """The plane most rows of the built set lie within ``distance_threshold`` of, by RANSAC on the device (tknnSegmentPlane): Open3D's
+        ``segment_plane(distance_threshold, 3, num_iterations)``, PCL's ``SACSegmentation`` with ``SACMODEL_PLANE`` and, with ``axis``
+        and ``max_angle`` (radians between the plane's normal and the axis), ``SACMODEL_PERPENDICULAR_PLANE``.  Trials run in batches
+        of 1024: three rows drawn by a counter-based hash of ``seed`` and the trial, the plane through them, its inliers counted by a
+        walk of the box pyramid that skips boxes outside the slab and counts boxes inside it by arithmetic; the loop stops once
+        ``confidence`` is reached (1: never early) or after ``num_iterations``; the best plane is refitted to its inliers up to
+        ``refit_rounds`` times.  ``active``: (n,) uint8 or bool by row, numpy or a tensor on the engine's device -- only rows with a
+        nonzero entry (and finite coordinates) are sampled, scored and reported; the tree is never rebuilt.
+        Returns (plane, rows): plane a (4,) float64 CPU tensor (a, b, c, d) with a*x + b*y + c*z + d = 0 and a unit normal turned
+        towards ``axis`` (without one: its first nonzero entry positive), all zero when no sample gave a plane; rows the (inliers,)
+        int32 inlier rows ascending, on the device.  ``return_info``: a dict instead -- plane, rows [``"inliers"`` in ``want``], mask
+        (n,) uint8 [``"mask"``], trial_status and trial_inliers (num_iterations,) int32, -1 where not run or not scored
+        [``"trials"``], info (best_trial, inliers, active, fitness, inlier_rmse, status_counts by _plane_lib.STATUS, the work
+        counters, the times)."""
+        torch = self._torch
+        want = (want,) if isinstance(want, str) else tuple(want)
+        unknown = set(want) - {"plane", "inliers", "mask", "trials"}
+        if unknown:
+            raise ValueError("segment_plane: want has %s; it takes plane, inliers, mask, trials" % sorted(unknown))
+        if (axis is None) != (max_angle is None):
+            raise ValueError("segment_plane: axis and max_angle go together")
+        n, trials = self.n, int(num_iterations)
+        with torch.cuda.device(self.device):
+            if active is not None:
+                if isinstance(active, torch.Tensor) and active.device != self.device:
+                    raise ValueError("segment_plane: active is on %s, the engine on %s" % (active.device, self.device))
+                active = torch.as_tensor(active, device=self.device)
+                if active.dim() != 1 or active.shape[0] != n or active.dtype not in (torch.uint8, torch.bool):
+                    raise ValueError("segment_plane: active must be (n,) uint8 or bool, one entry per built point")
+                active = active.to(torch.uint8).contiguous()
+            wanted = {}
+            if "inliers" in want:
+                wanted["rows"] = ((n,), torch.int32)
+            if "mask" in want:
+                wanted["mask"] = ((n,), torch.uint8)
+            if "trials" in want:
+                wanted.update({"trial_status": ((max(trials, 0),), torch.int32), "trial_inliers": ((max(trials, 0),), torch.int32)})
+            out = _call_outputs(torch, self.device, wanted)
+            spare = out.pop("spare")
+            opt = _plane_lib.PlaneOptions()
+            opt.d_active = _address(active, spare)
+            opt.distance_threshold, opt.max_trials, opt.confidence = float(distance_threshold), trials, float(confidence)
+            opt.seed, opt.refit_rounds = int(seed) & 0xFFFFFFFF, int(refit_rounds)
+            if axis is not None:
+                axis = [float(np.float32(x)) for x in axis]
+                if len(axis) != 3 or not any(axis):
+                    raise ValueError("segment_plane: axis must have three entries, not all zero")
+                for i in range(3):
+                    opt.axis[i] = axis[i]
+                opt.min_cos = float(np.cos(float(max_angle)))
+            opt.d_inlier_rows, opt.d_inlier_mask = _address(out.get("rows"), spare), _address(out.get("mask"), spare)
+            opt.d_trial_status, opt.d_trial_inliers = _address(out.get("trial_status"), spare), _address(out.get("trial_inliers"), spare)
+            info = _plane_lib.PlaneInfo()
+            _lib.check(_plane_lib.load().tknnSegmentPlane(self._h, ctypes.byref(opt), ctypes.byref(info), self._stream()))
+        res = info.as_dict()
+        plane = torch.tensor(list(info.plane), dtype=torch.float64)
+        res["plane"], res["normal"], res["anchor"] = list(info.plane), list(info.normal), list(info.anchor)
+        res["status_counts"] = dict(zip(_plane_lib.STATUS, info.status_counts))
+        if "inliers" in want:
+            out["rows"] = out["rows"][:int(info.inliers)]
+        if not return_info:
+            return plane, out.get("rows")
+        out["plane"], out["info"] = plane, res
+        return out
+
+    def segment_planes(self, distance_threshold, max_planes, min_inliers, active=None, **kw):
+        """Up to ``max_planes`` planes of the built set, the largest first: ``segment_plane(distance_threshold, active=..., **kw)``
+        again and again, each plane's inliers cleared from an active mask this call owns (a copy of ``active``; None: every row)
+        before the next; the tree is never rebuilt.  It stops at the first plane with fewer than ``min_inliers`` inliers, which is
+        not reported.  Returns (planes, labels): planes a list of (plane, rows) as ``segment_plane`` returns them, labels (n,) int32
+        on the device, the index of the row's plane in that list, -1 for a row in none."""
+        torch = self._torch
+        if "want" in kw or "return_info" in kw:
+            raise ValueError("segment_planes: want and return_info are segment_plane's")
+        n = self.n
+        with torch.cuda.device(self.device):
+            if active is None:
+                mask = torch.ones((n,), dtype=torch.uint8, device=self.device)
+            else:
+                if isinstance(active, torch.Tensor) and active.device != self.device:
+                    raise ValueError("segment_planes: active is on %s, the engine on %s" % (active.device, self.device))
+                mask = torch.as_tensor(active, device=self.device)
+                if mask.dim() != 1 or mask.shape[0] != n or mask.dtype not in (torch.uint8, torch.bool):
+                    raise ValueError("segment_planes: active must be (n,) uint8 or bool, one entry per built point")
+                mask = (mask != 0).to(torch.uint8)  # (a copy: the caller's stays as it is)
+            labels = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            planes = []
+            while len(planes) < int(max_planes):
+                plane, rows = self.segment_plane(distance_threshold, active=mask, **kw)
+                if rows.shape[0] < max(int(min_inliers), 1):
+                    break
+                labels[rows.long()] = len(planes)
+                mask[rows.long()] = 0
+                planes.append((plane, rows))
+        return planes, labels
+
     def mean_shift_modes(self, bandwidth, seeds=None, kernel="flat", radius=None, tol=None, max_iterations=300):
         """Mean-shift trajectories over the built set, the loop inside the library (tknnMeanShift): every seed moves to the
         kernel-weighted mean of the built points within ``radius`` of it (fp32 sqrt((dx*dx + dy*dy) + dz*dz) <= radius; the sums
@@ -1799,6 +1897,20 @@ def orient_normals(points, normals, **kw):
     """One-shot helper: build over ``points``, one consistent sign per normal with no viewpoint (TrueKNN.orient_normals), results as
     numpy arrays."""
     return _one_shot(points, lambda eng: eng.orient_normals(normals, **kw))
+
+
+def segment_plane(points, distance_threshold, **kw):
+    """One-shot helper: build over ``points`` and take its dominant plane (TrueKNN.segment_plane): (plane, rows) as numpy arrays, or
+    with ``return_info=True`` the dict, its tensors as numpy arrays."""
+    eng = TrueKNN()
+    try:
+        eng.build(points)
+        res = eng.segment_plane(distance_threshold, **kw)
+        if isinstance(res, dict):
+            return {name: (v.cpu().numpy() if hasattr(v, "cpu") else v) for name, v in res.items()}
+        return tuple(v.cpu().numpy() for v in res)
+    finally:
+        eng.close()
 
 
 def icp(target, source, max_dist, **kw):
