@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "lbvh.h"
 #include "owlknn.h"  // tknnNeigh
@@ -83,5 +84,87 @@ struct TeamArgs {
   // [5] error flags (1 max_rounds) [6] sum levels [7] unfinished [8] handed over [9] min hand-over level
   unsigned long long *counters;
 };
+
+// The packet kernel's argument block for a PLAIN solve (team_kernel<..., PLAIN = true>, trueknn_team.hip): one own tree, k <= 16,
+// rows into idx, dist and intersections, and nothing else -- no frame buffer, no per-query start radii, no levels, no phase, no
+// halo tree, no measurement knob.  What such a solve never has is a constant of the type, under the name TeamArgs gives it: the
+// kernel's text reads `a.out_fb`, `a.skip`, `a.lite` for both blocks, and for this one the compiler folds the test away with
+// everything behind it.  What is left are the values the kernel reads, some 200 bytes against TeamArgs' 480: few enough that the
+// pass loops need not fetch any of them from the argument segment again.
+struct PlainTeamArgs {
+  struct {
+    const LbvhPoint *points;
+    const int32_t *prim_id;
+    int32_t n;
+  } bvh;
+  struct NoTree {
+    static constexpr const LbvhPoint *points = nullptr;
+    static constexpr int32_t n = 0;
+  };
+  static constexpr NoTree halo = {};
+  LbvhWideView wide[1];  // (the pyramid's table is read whole, by level: the gather)
+  float start_radius;
+  static constexpr const float *start_radii = nullptr;
+  int k;
+  int max_rounds;
+  int allow_unfinished;
+  int first_step;
+  int first_ext;
+  static constexpr int merge_ext = 1;
+  static constexpr int count_flat_max = 12;  // 4 * kCountFlatGroups (trueknn_team.hip asserts it)
+  static constexpr int lite = 1;
+  float tie_span;
+  static constexpr int diag = 0;
+  int32_t ngroups;
+  int32_t *out_idx;  // the three of them: never null
+  float *out_dist;
+  int64_t *out_isect;
+  static constexpr tknnNeigh *out_fb = nullptr;
+  static constexpr int32_t *out_level = nullptr;
+  uint8_t *done;
+  int64_t *isect_sorted;
+  int32_t *next_level;
+  uint8_t *tie;
+  int32_t *tie_list;
+  static constexpr const uint8_t *skip = nullptr;
+  static constexpr int32_t skip_is = 0;
+  unsigned long long *counters;
+};
+
+// whether a solve with this (complete) block is a plain one as far as the block says: the caller adds what the block does not
+// show -- that no measurement knob is set, and that k takes one list register
+inline bool plain_team_solve(const TeamArgs &a) {
+  return a.out_idx && a.out_dist && a.out_isect && !a.out_fb && !a.out_level && !a.start_radii && !a.skip && a.halo.n <= 0 && !a.halo.points &&
+         a.merge_ext == PlainTeamArgs::merge_ext && a.lite == PlainTeamArgs::lite && a.count_flat_max == PlainTeamArgs::count_flat_max &&
+         a.diag == PlainTeamArgs::diag;
+}
+// ... and the plain block of that solve: every field from the generic one, so the two cannot differ
+inline PlainTeamArgs plain_team_args(const TeamArgs &a) {
+  PlainTeamArgs p;
+  p.bvh.points = a.bvh.points;
+  p.bvh.prim_id = a.bvh.prim_id;
+  p.bvh.n = a.bvh.n;
+  p.wide[0] = a.wide[0];
+  p.start_radius = a.start_radius;
+  p.k = a.k;
+  p.max_rounds = a.max_rounds;
+  p.allow_unfinished = a.allow_unfinished;
+  p.first_step = a.first_step;
+  p.first_ext = a.first_ext;
+  p.tie_span = a.tie_span;
+  p.ngroups = a.ngroups;
+  p.out_idx = a.out_idx;
+  p.out_dist = a.out_dist;
+  p.out_isect = a.out_isect;
+  p.done = a.done;
+  p.isect_sorted = a.isect_sorted;
+  p.next_level = a.next_level;
+  p.tie = a.tie;
+  p.tie_list = a.tie_list;
+  p.counters = a.counters;
+  return p;
+}
+template <bool PLAIN>
+using TeamArgsOf = std::conditional_t<PLAIN, PlainTeamArgs, TeamArgs>;
 
 }  // namespace owlmi

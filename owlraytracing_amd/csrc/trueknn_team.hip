@@ -161,18 +161,63 @@ struct TeamLds {
   unsigned long long *cand;  // [4][kCandCap] per team: keys waiting to be merged into its list
 };
 
+// a value the compiler takes as it is from here on (it cannot make it again from where it came from)
+// (through a vector register and back: the compiler takes what an asm statement leaves in a scalar register for a per-lane value)
+__device__ __forceinline__ uint32_t t_hold_word(uint32_t w) {
+  asm volatile("" : "+v"(w));
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
+}
+template <class T>
+__device__ __forceinline__ void t_hold(T &v) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "a word or a pointer");
+  uint32_t w[sizeof(T) / 4];
+  memcpy(w, &v, sizeof(T));
+  for (size_t i = 0; i < sizeof(T) / 4; i++) w[i] = t_hold_word(w[i]);
+  memcpy(&v, w, sizeof(T));
+}
+
+// my lane, as a value the compiler cannot tell from a new one: what is made from it is made where it is used, not carried there
+__device__ __forceinline__ int t_lane_again(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// what the plain kernel holds for its passes (team_kernel); the generic kernel: nothing, its passes read the argument block
+template <bool PLAIN>
+struct TeamHeld {};
+template <>
+struct TeamHeld<true> {
+  int32_t *out_idx;
+  float *out_dist;
+  int64_t *out_isect;
+  uint8_t *tie;  // (and the start radius: read where a row has ties that may span two levels -- rare, but inside the SELECT rounds)
+  float start_radius;
+  int k;
+};
+
+template <bool PLAIN>
+__device__ __forceinline__ int team_k(const TeamArgsOf<PLAIN> &a, const TeamHeld<PLAIN> &held) {
+  if constexpr (PLAIN)
+    return held.k;
+  else
+    return a.k;
+}
+
 // One pass of the four teams over a compact list of queries.  SELECT = false: count candidates
 // (deviceCode.cu:74,103).  SELECT = true: also keep the k best (dist,index) keys, lane j of the
 // team holding the j-th, and write the row if the query turns out finished (>= k others).
 // NREG: list registers per lane -- the team's sorted list holds 16 * NREG keys (k <= 16: 1, k <= 32: 2, k <= 64: 4)
 // TWO: a COUNT pass that also counts the inner box of a two-level step (a template flag: as a run-time value the
 // compiler kept "m > 1" as a lane mask and re-derived a branch from it for every block)
-template <bool SELECT, bool HALO, int NREG, bool FULL, bool TWO>
-__device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, int n_list, int32_t first_slot,
+// PLAIN: the argument block is PlainTeamArgs (team_args.h) -- what a plain solve never has is a constant of that type, and its
+// three result arrays are there
+template <bool SELECT, bool HALO, int NREG, bool FULL, bool TWO, bool PLAIN = false>
+__device__ __forceinline__ void team_pass(const TeamArgsOf<PLAIN> &a, const TeamHeld<PLAIN> &held, const TeamLds &L, int n_list, int32_t first_slot,
                                           const LbvhPoint *own_pts, const LbvhPoint *halo_pts, int lane) {
   const int team = lane >> 4, tl = lane & 15;
   constexpr int kMaxPerQuery = TeamLayout<NREG>::kMaxPerQuery, kEntStride = TeamLayout<NREG>::kEntStride;
   static_assert(!(SELECT && TWO), "only a COUNT pass serves two levels");
+#define TEAM_K team_k<PLAIN>(a, held)  // (and the row's arrays below: held by the plain kernel, arguments of the generic one)
   n_list = __builtin_amdgcn_readfirstlane(n_list);  // wave-uniform by construction; says so to the compiler (scalar branches on it)
   [[maybe_unused]] unsigned long long tp[4] = {0, 0, 0, 0};  // TKNN_DIAG_BUILD, flag 128: setup | first group | other groups | epilogue
   for (int r0 = 0; r0 < n_list; r0 += 4) {
@@ -303,8 +348,8 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     auto kth_dist = [&]() -> float {
       uint32_t reg = bd[0];
 #pragma unroll
-      for (int j = 1; j < NREG; j++) reg = ((a.k - 1) >> 4) == j ? bd[j] : reg;
-      return __uint_as_float(t_lane_read(reg, (team << 4) + ((a.k - 1) & 15)));
+      for (int j = 1; j < NREG; j++) reg = ((TEAM_K - 1) >> 4) == j ? bd[j] : reg;
+      return __uint_as_float(t_lane_read(reg, (team << 4) + ((TEAM_K - 1) & 15)));
     };
     float tau2 = INFINITY;
     // Candidates that pass the gate wait in the team's LDS buffer and are merged into the sorted list sixteen at a time
@@ -575,7 +620,7 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
       for (int j = 0; j < NREG; j++) {
         uint32_t before = t_team_shr1(bd[j]);
         if (j > 0) before |= t_dpp<0x121>(bd[j - 1]) & (tl == 0 ? 0xffffffffu : 0u);
-        tie[j] = ((j > 0) | (tl >= 1)) & (16 * j + tl <= a.k) & (bd[j] == before);
+        tie[j] = ((j > 0) | (tl >= 1)) & (16 * j + tl <= TEAM_K) & (bd[j] == before);
         if (full && j == NREG - 1) tie[j] |= (tl == 15) & (left_out == bd[j]);
         any |= tie[j];
       }
@@ -583,17 +628,26 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
         const float qmax = fmaxf(fmaxf(fabsf(t_qx), fabsf(t_qy)), fabsf(t_qz));
         any = false;
         bool edge = false;
-        const float q_r0 = a.start_radii ? a.start_radii[a.bvh.prim_id[first_slot + qi]] : a.start_radius;
+        float q_r0;
+        if constexpr (PLAIN)
+          q_r0 = held.start_radius;
+        else
+          q_r0 = a.start_radii ? a.start_radii[a.bvh.prim_id[first_slot + qi]] : a.start_radius;
 #pragma unroll
         for (int j = 0; j < NREG; j++) {
           const bool t = tie[j] && tie_may_straddle(__uint_as_float(bd[j]), q_r0, t_r, qmax, a.tie_span);
           any |= t;
           // ... with a candidate that is not written: entry k of a list with room to spare, the best one left out of a full list
-          edge |= t && (16 * j + tl == a.k || (full && j == NREG - 1 && tl == 15 && left_out == bd[j]));
+          edge |= t && (16 * j + tl == TEAM_K || (full && j == NREG - 1 && tl == 15 && left_out == bd[j]));
         }
         // (said to knn_flag_tie through the flag byte itself, here in the rare branch: a second bit through the passes' count
         // words and the level loop moved the packet kernel's register allocation -- 0.6 % of the benchmark)
-        if (on && edge) knn_note_tie_edge(a.tie, first_slot + qi);
+        if (on && edge) {
+          if constexpr (PLAIN)
+            knn_note_tie_edge(held.tie, first_slot + qi);
+          else
+            knn_note_tie_edge(a.tie, first_slot + qi);
+        }
       }
       tied = ((uint32_t)(__ballot(any) >> (team * 16)) & 0xffffu) ? 1u : 0u;
     }
@@ -611,21 +665,26 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     if (SELECT) {
       // finished at this level (deviceCode.cu:118: k insertions happened): lane j < k stores neighbour j.
       // The query's own lane adds the intersection count and the level afterwards (team_kernel).
-      if (on && others >= (uint32_t)a.k) {
+      if (on && others >= (uint32_t)TEAM_K) {
 #pragma unroll
         for (int reg = 0; reg < NREG; reg++) {
           const int j = tl + 16 * reg;  // my entry of this register
-          if (j >= a.k) continue;
-          const int64_t o = (int64_t)out_row * a.k + j;
+          if (j >= TEAM_K) continue;
+          const int64_t o = (int64_t)out_row * TEAM_K + j;
           const int32_t prim = knn_key_prim(((uint64_t)bd[reg] << 32) | bi[reg]);
           const float d = __uint_as_float(bd[reg]);
-          if (a.out_idx) a.out_idx[o] = prim;
-          if (a.out_dist) a.out_dist[o] = d;
+          if constexpr (PLAIN) {
+            held.out_idx[o] = prim;
+            held.out_dist[o] = d;
+          } else {
+            if (a.out_idx) a.out_idx[o] = prim;
+            if (a.out_dist) a.out_dist[o] = d;
+          }
           if (a.out_fb) {
             // slot 0 of the row: everything but `intersections`, which only the query's lane writes
             int2 *rec8 = (int2 *)(a.out_fb + o);
             rec8[0] = make_int2(prim, __float_as_int(d));
-            rec8[1] = make_int2(j == 0 ? 0 : a.k, 0);
+            rec8[1] = make_int2(j == 0 ? 0 : TEAM_K, 0);
             if (j != 0) {
               // (a zero made here: as a constant the compiler keeps the pair in registers over the whole kernel, spills it,
               // and reloads it from scratch at this point of the pass loop)
@@ -644,8 +703,24 @@ __device__ __forceinline__ void team_pass(const TeamArgs &a, const TeamLds &L, i
     for (int i = 0; i < 4; i++) atomicAdd(&a.counters[(SELECT ? 36 : 28) + i], tp[i]);  // (32..34: the tie pass)
 }
 
-template <bool HALO, int NREG, bool FULL>
-__global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu(TKNN_TEAM_WAVES))) team_kernel(TeamArgs a) {
+template <bool HALO, int NREG, bool FULL, bool PLAIN = false>
+__global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu(TKNN_TEAM_WAVES))) team_kernel(TeamArgsOf<PLAIN> a) {
+  static_assert(!PLAIN || (!HALO && NREG == 1), "the plain kernel: one own tree, k <= 16");
+  static_assert(PlainTeamArgs::count_flat_max == 4 * kCountFlatGroups, "a plain solve's flat COUNT rounds are the generic solve's");
+  // The plain kernel reads what its pass loops need from the argument segment ONCE and holds it: an argument is a value the
+  // compiler may fetch again wherever it runs short of scalar registers, and it did -- the row's two pointers before every row's
+  // stores, a scalar load and its wait at the end of every SELECT round.  (The generic kernel reads its block as ever.)
+  TeamHeld<PLAIN> held;
+  if constexpr (PLAIN) {
+    held.out_idx = a.out_idx, held.out_dist = a.out_dist, held.out_isect = a.out_isect, held.tie = a.tie;
+    held.start_radius = a.start_radius, held.k = a.k;
+    t_hold(held.out_idx);
+    t_hold(held.out_dist);
+    t_hold(held.out_isect);
+    t_hold(held.tie);
+    t_hold(held.start_radius);
+    t_hold(held.k);
+  }
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;  // 0 with one wave per workgroup
@@ -909,7 +984,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         for (int w = 0; w < Lay::kHiWords; w++) qhi[lane * Lay::kHiWords + w] = 0u;  // (my own words: no lane but mine writes them)
       }
       int nb = 0, scanned = 0;
-      for (int tree = 0; tree < 2 && !too_big; tree++) {
+      for (int tree = 0; tree < (PLAIN ? 1 : 2) && !too_big; tree++) {
         const LbvhWideView &wv = a.wide[tree];
         const int32_t tree_n = tree == 0 ? a.bvh.n : a.halo.n;
         if (tree_n <= 0 || wv.levels <= 0) continue;
@@ -1049,9 +1124,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         if (__ballot(my_nblk > kMaxPerQuery) != 0ull) too_big = true;
         if (too_big) {
           if (active) {
-            a.done[slot] = 0;
-            a.isect_sorted[slot] = isect;
-            a.next_level[slot] = level;
+            // (plain: the three addresses made here -- made at the packet's start, for a store few packets ever make, they are
+            // three register pairs across the passes, two of them in scratch)
+            int32_t slot_now = slot;
+            if constexpr (PLAIN) slot_now = g * 64 + t_lane_again(lane);
+            a.done[slot_now] = 0;
+            a.isect_sorted[slot_now] = isect;
+            a.next_level[slot_now] = level;
             my_handed++;
           }
           wave_min_handover = min(wave_min_handover, level);
@@ -1089,7 +1168,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       // one round of the teams and one turn's bookkeeping less per packet.  If not (a query with hardly any others yet, a
       // speculation at the step's own level that failed) the turn runs for the queries left over, `served` keeping the
       // others out of its passes.  (`reuse` is set here exactly when this turn's gather has an extension.)
-      const bool speculate = m == 1 && active && !served && level > 0 && prev_others * 8u >= (uint32_t)(a.k + a.k / 2);
+      const bool speculate = m == 1 && active && !served && level > 0 && prev_others * 8u >= (uint32_t)(TEAM_K + TEAM_K / 2);
       const bool count_first = active && !served && !speculate;
       served = false;  // (set only on the way into a `reuse` turn)
       // The four teams of a pass step through their lists in lockstep, so a group of four queries
@@ -1124,9 +1203,9 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         const int n_count = build_qlist(count_first, my_nblk, false);
         if (!(TKNN_DIAG_BUILD && (a.diag & 4))) {
           if (m > 1)
-            team_pass<false, HALO, NREG, false, true>(a, L, n_count, g * 64, own_pts, halo_pts, lane);
+            team_pass<false, HALO, NREG, false, true, PLAIN>(a, held, L, n_count, g * 64, own_pts, halo_pts, lane);
           else
-            team_pass<false, HALO, NREG, false, false>(a, L, n_count, g * 64, own_pts, halo_pts, lane);
+            team_pass<false, HALO, NREG, false, false, PLAIN>(a, held, L, n_count, g * 64, own_pts, halo_pts, lane);
         }
         t_wave_sync();
       }
@@ -1140,13 +1219,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         const uint32_t w1 = qcnt[lane * 2 + 1];
         c1 = m > 1 ? (w1 & 0x3fffffffu) : 0u;
         selfc = w1 >> 31;
-        if (c0 - selfc >= (uint32_t)a.k)
+        if (c0 - selfc >= (uint32_t)TEAM_K)
           fin_at = 0;
-        else if (m > 1 && c1 - selfc >= (uint32_t)a.k)
+        else if (m > 1 && c1 - selfc >= (uint32_t)TEAM_K)
           fin_at = 1;
       }
       int sel_nblk = my_nblk;
-      if (reuse && a.merge_ext && count_first && fin_at < 0 && ((m > 1 ? c1 : c0) - selfc) * 8u >= (uint32_t)(a.k + a.k / 2)) {  // the rule of `speculate`, a turn early
+      if (reuse && a.merge_ext && count_first && fin_at < 0 && ((m > 1 ? c1 : c0) - selfc) * 8u >= (uint32_t)(TEAM_K + TEAM_K / 2)) {  // the rule of `speculate`, a turn early
         // my whole list, as the `reuse` turn would have it: front + back | own position | front length << 16 (bits 24..31
         // keep the back part's length until the statistics below have read it), and that level's radius
         fin_at = m;
@@ -1168,7 +1247,7 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       {
         t_wave_sync();
         const int n_select = build_qlist(select_now, sel_nblk, lite);
-        if (!(TKNN_DIAG_BUILD && (a.diag & 2))) team_pass<true, HALO, NREG, FULL, false>(a, L, n_select, g * 64, own_pts, halo_pts, lane);
+        if (!(TKNN_DIAG_BUILD && (a.diag & 2))) team_pass<true, HALO, NREG, FULL, false, PLAIN>(a, held, L, n_select, g * 64, own_pts, halo_pts, lane);
         t_wave_sync();
       }
       PHASE_END(3);
@@ -1180,13 +1259,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       if (speculate) {
         c0 = qcnt[lane * 2 + 0];
         selfc = qcnt[lane * 2 + 1] >> 31;
-        finished = c0 - selfc >= (uint32_t)a.k;
+        finished = c0 - selfc >= (uint32_t)TEAM_K;
         fin_at = finished ? 0 : -1;
       }
       uint32_t c_ext = 0, n_back = 0;  // candidates in my box at the extension level; blocks of my list it alone needs
       if (ext_sel) {
         c_ext = qcnt[lane * 2 + 0];
-        finished = c_ext - selfc >= (uint32_t)a.k;
+        finished = c_ext - selfc >= (uint32_t)TEAM_K;
         // (should the `reuse` turn run for others, it reads a list without a back part for me)
         const int pk = __float_as_int(qrec[lane * kQrecStride + 5]);
         n_back = ((uint32_t)pk >> 24) & 0xffu;
@@ -1211,11 +1290,26 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
       if (finished) {
         // the team wrote the row (SELECT pass); the counter and the level come from the query's lane
         my_isect_sum += (unsigned long long)isect;
-        if (a.out_isect) a.out_isect[row] = isect;
-        if (a.out_fb) a.out_fb[(int64_t)row * a.k].intersections = isect;
+        if constexpr (PLAIN) {
+          // (the row's address made HERE: made where the row is read -- it is the same over a packet's levels -- it is a pair of
+          // registers that lives across the passes, and did so in scratch: a load and its wait in front of this store)
+          int32_t row_now = row;
+          asm volatile("" : "+v"(row_now));
+          held.out_isect[row_now] = isect;
+        } else if (a.out_isect) {
+          a.out_isect[row] = isect;
+        }
+        if (a.out_fb) a.out_fb[(int64_t)row * TEAM_K].intersections = isect;
         const int fin_level = level + (fin_at > 0 ? fin_at : 0);
         if (a.out_level) a.out_level[row] = fin_level;
-        if ((qcnt[lane * 2 + 1] >> 30) & 1u) knn_flag_tie(a.tie, a.tie_list, a.counters, slot, fin_level, 2);  // SELECT saw exact-distance ties
+        if ((qcnt[lane * 2 + 1] >> 30) & 1u) {  // SELECT saw exact-distance ties
+          if constexpr (PLAIN) {
+            const int32_t slot_now = g * 64 + t_lane_again(lane);  // (as the row above; my slot, made again from my lane)
+            knn_flag_tie(held.tie, a.tie_list, a.counters, slot_now, fin_level, 2);
+          } else {
+            knn_flag_tie(a.tie, a.tie_list, a.counters, slot, fin_level, 2);
+          }
+        }
       }
       active = active && !finished;
       int m_done = m;  // levels behind the packet after this turn
@@ -1241,13 +1335,13 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
         const float pmax = t_wave_max(active ? (float)last_others : 0.f);
         float expect = pmax * 8.f;
         step = 1;
-        while (step < kMaxStep && expect < 0.5f * (float)a.k) {
+        while (step < kMaxStep && expect < 0.5f * (float)TEAM_K) {
           step++;
           expect *= 8.f;
         }
         // ... and list the blocks of the level after the step, too, unless even the best-off query will almost
         // surely finish inside it (a packet walks again as long as ONE of its 64 queries is unfinished)
-        ext_next = ext_ok && expect < 2.5f * (float)a.k ? 1 : 0;
+        ext_next = ext_ok && expect < 2.5f * (float)TEAM_K ? 1 : 0;
       }
     }
     if (active) my_unfinished++;
@@ -1278,6 +1372,8 @@ __global__ void __launch_bounds__(kTeamBlock) __attribute__((amdgpu_waves_per_eu
   }
 }
 
+
+#undef TEAM_K
 
 // Start-of-solve state of the packet kernel in one launch: done[] = 1 (a query is "done" unless handed
 // over), tie[] = 0, counters = 0 except [9] = ~0 (min hand-over level), levels[] = -1 if asked for.
@@ -1373,8 +1469,19 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
        {team_kernel<false, 3, false>, team_kernel<false, 3, true>}, {team_kernel<false, 4, false>, team_kernel<false, 4, true>}},
       {{team_kernel<true, 1, false>, team_kernel<true, 1, true>}, {team_kernel<true, 2, false>, team_kernel<true, 2, true>},
        {team_kernel<true, 3, false>, team_kernel<true, 3, true>}, {team_kernel<true, 4, false>, team_kernel<true, 4, true>}}};
-  const TeamEntry entry = entries[halo_count() > 0 ? 1 : 0][nreg - 1][full_list ? 1 : 0];
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)entry, kTeamBlock, lds) != hipSuccess) per_cu = 2;
+  // A PLAIN solve -- rows into idx, dist and intersections and nothing else of what TeamArgs can ask for (plain_team_solve), one list
+  // register, no measurement knob in the environment -- takes the instantiation that carries none of it, with an argument block of
+  // what is left (PlainTeamArgs).  Every other solve takes the generic kernel; TKNN_TEAM_PLAIN=0 (measurements and tests): every solve.
+  using PlainEntry = void (*)(PlainTeamArgs);
+  static const PlainEntry plain_entries[2] = {team_kernel<false, 1, false, true>, team_kernel<false, 1, true, true>};
+  bool plain = nreg == 1 && halo_count() == 0 && plain_team_solve(a);
+  for (const char *knob : {"TKNN_TEAM_MERGE", "TKNN_TEAM_LITE", "TKNN_TEAM_COUNT_FLAT", "TKNN_TEAM_EXT", "TKNN_TEAM_DIAG"})
+    if (getenv(knob)) plain = false;
+  if (const char *e = getenv("TKNN_TEAM_PLAIN")) plain = plain && atoi(e) > 0;
+  const PlainTeamArgs plain_a = plain_team_args(a);
+  if (getenv("TKNN_VERBOSE")) fprintf(stderr, "[team] packet kernel: the %s instantiation\n", plain ? "plain" : "generic");
+  const void *entry = plain ? (const void *)plain_entries[full_list ? 1 : 0] : (const void *)entries[halo_count() > 0 ? 1 : 0][nreg - 1][full_list ? 1 : 0];
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, entry, kTeamBlock, lds) != hipSuccess) per_cu = 2;
   // (the query divides the CU's LDS by the byte; the hardware hands it out in granules: scripts/microbench/lds_granule.hip --
   // a launch of more workgroups than fit would leave the surplus waiting for a slot and then for the last packets)
   per_cu = std::max(1, std::min(per_cu, lds_workgroups_per_cu(lds)));
@@ -1389,8 +1496,8 @@ bool Engine::solve_team(const SolveArgs &sa, tknnSolveInfo *info, hipStream_t s)
   hipLaunchKernelGGL(team_prep_kernel, dim3(cu_count_ * 4), dim3(256), 0, s, done_, tie_, n, counters_, sa.phase >= 2 ? nullptr : sa.d_levels);
   OWLMI_HIP(hipEventRecord(ev_a_, s));
   {
-    void *kargs[] = {(void *)&a};
-    OWLMI_HIP(hipLaunchKernel((const void *)entry, dim3(blocks), dim3(kTeamBlock), kargs, lds, s));
+    void *kargs[] = {plain ? (void *)&plain_a : (void *)&a};
+    OWLMI_HIP(hipLaunchKernel(entry, dim3(blocks), dim3(kTeamBlock), kargs, lds, s));
   }
   OWLMI_HIP(hipGetLastError());
   OWLMI_HIP(hipEventRecord(ev_b_, s));

@@ -1,6 +1,7 @@
 #!/bin/bash
 # gfx950 assembly of ONE kernel of a .hip file (no GPU needed):
-#   scripts/isa_of.sh owlraytracing_amd/csrc/trueknn_team.hip team_kernelILb0ELi1ELb0E [out.s] [extra hipcc flags...]
+#   scripts/isa_of.sh owlraytracing_amd/csrc/trueknn_team.hip team_kernelILb0ELi1ELb0ELb0E [out.s] [extra hipcc flags...]
+#     (<HALO, NREG, FULL, PLAIN>: ...ELb0ELb1E is the plain instantiation of the benchmark, ...ELb0ELb0E the generic one)
 #   scripts/isa_of.sh owlraytracing_amd/csrc/trueknn_tail.hip team_walk_kernelILb0ELi1E    (trueknn_bigk.hip: bigk_walk_kernel)
 #   scripts/isa_of.sh owlraytracing_amd/csrc/dbscan_union.hip db_group_union_kernel
 # <mangled-substring> selects the function whose "Begin function" line contains it.

@@ -10,5 +10,5 @@ for src in trueknn_team.hip trueknn_tail.hip trueknn_bigk.hip trueknn_query.hip;
     -Rpass-analysis=kernel-resource-usage -c $src -o /dev/null 2>&1 \
     | grep -A12 "Function Name:" | grep "Function Name\|  VGPRs:\|ScratchSize\|Occupancy\|LDS Size" | sed 's/.*remark: //; s/\[-Rpass.*//' | paste - - - - - \
     | sed 's/Function Name: //' | c++filt | grep "team_kernel\|team_walk_kernel\|tie_fix_kernel\|bigk_walk_kernel\|query_walk_kernel" \
-    | sed 's/owlmi::(anonymous namespace):://g; s/owlmi:://g; s/([A-Za-z]*Args[^)]*)//' | tr -s ' \t' ' ' | cut -c1-160
+    | sed 's/owlmi::(anonymous namespace):://g; s/owlmi:://g; s/([A-Za-z]*Args[^)]*)//; s/(std::conditional<[^)]*Args>::type)//' | tr -s ' \t' ' ' | cut -c1-160
 done
